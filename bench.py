@@ -36,6 +36,10 @@ Extra objects on the JSON line (definitions and formulas: DESIGN.md s5):
 `--single-process` renders the same frames through rt_render_multi instead (ONE process, one host thread per GPU inside librtamd,
 RCCL gather linked into the library -- what a Rust / C++ host calls); same JSON line, "launch": "single-process".  The default,
 and what the driver starts, is one process per GPU over torch.distributed.
+
+`--dump-outputs DIR`: after the timed steps, rank 0 writes the stitched f64 frame of the last timed step -- what a caller of the path
+receives -- as DIR/frame.npy (see dump_outputs).  The inputs depend on the arguments alone (committed scene file, --seed), so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -55,6 +59,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 N_SIMDS = 256 * 4      # 256 CUs x 4 SIMDs
 MAX_CLOCK_GHZ = 2.4    # MI355X max engine clock (MI355X_MICROARCH.md): the roofline PEAK is priced at it, not at the clock a profiled pass happened to hold
 CPU_BASELINE_THREADS = 16
+DUMP_BYTES_MAX = 64 * 2**20  # --dump-outputs writes at most this much
 
 
 def cpu_model():
@@ -96,6 +101,24 @@ def cpu_baseline(width, height, spp_cpu, seed):
         "reference_default": {"value": v_ref, "unit": "Msamples/s", "cores": ref_workers,
                               "sample": "same frame at %d spp (%.1f s) with the reference's default n_workers = 8 (main.rs:42)" % (spp_ref, dt_ref)},
     }
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: the frame [H, W, 3] as out_dir/frame.npy (float64).  A frame above DUMP_BYTES_MAX is written as a fixed sample
+    instead: flat pixel indices y * W + x drawn with seed 0 (frame_sample_pixels.npy, float64: exact below 2^53) and those pixels'
+    values (frame_sample.npy, [N, 3]), half the byte cap in all.  Returns the file names written."""
+    import numpy as np
+    frame = np.asarray(frame, dtype=np.float64)
+    if frame.nbytes <= DUMP_BYTES_MAX:
+        arrays = {"frame": frame}
+    else:
+        n_px = frame.shape[0] * frame.shape[1]
+        idx = np.unique(np.random.default_rng(0).integers(0, n_px, size=DUMP_BYTES_MAX // 64))  # 32 bytes per sampled pixel
+        arrays = {"frame_sample_pixels": idx.astype(np.float64), "frame_sample": frame.reshape(n_px, 3)[idx]}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(name + ".npy" for name in arrays)
 
 
 def visible_devices():
@@ -277,6 +300,8 @@ def single_process(args):
     if args.frame_out:
         import numpy as np
         np.save(args.frame_out, img)
+    if args.dump_outputs:
+        out["dumped_outputs"] = dump_outputs(args.dump_outputs, img)
     print(json.dumps(out))
     return 0
 
@@ -296,12 +321,16 @@ def main():
                     help="world 1 only: create the RCCL process group anyway and drive the N-rank exchange through it (init, gather of "
                          "the f64 device rows, barrier, all_reduce(MAX)); also RTAMD_BENCH_FORCE_PG=1")
     ap.add_argument("--frame-out", default=None, help="rank 0 writes the stitched f64 frame [H, W, 3] of the last step to this .npy file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed to DIR/<name>.npy (float64, at most 64 MB; see dump_outputs)")
     ap.add_argument("--single-process", action="store_true",
                     help="render through rt_render_multi: one process, one host thread per GPU inside librtamd, RCCL gather linked into the library")
     ap.add_argument("--devices", default=None, help="--single-process only: comma-separated HIP ordinals, one per rank (may repeat; default 0..gpus-1)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     if args.single_process:
         sys.exit(single_process(args))
@@ -456,9 +485,13 @@ def main():
             out["process_group"] = {"backend": backend + (" (RCCL)" if backend == "nccl" else ""), "world": world_size, "forced_at_world_1": bool(force_pg),
                                     "torch_rccl_version": nccl_v, "init_s_max": max(r[7] for r in per_rank),
                                     "calls": ["init_process_group", "gather", "barrier", "all_reduce(MAX)", "all_gather"]}
+        if args.frame_out or args.dump_outputs:
+            host_frame = frame.cpu().numpy().reshape(args.height, args.width, 3)
         if args.frame_out:
             import numpy as np
-            np.save(args.frame_out, frame.cpu().numpy().reshape(args.height, args.width, 3))
+            np.save(args.frame_out, host_frame)
+        if args.dump_outputs:
+            out["dumped_outputs"] = dump_outputs(args.dump_outputs, host_frame)
         if rehearse:
             out["rehearsal"] = "all %d ranks share HIP device 0, gather over gloo through host memory: NOT a scaling measurement" % world_size
         if world_size == 1 and args.cpu_spp > 0:

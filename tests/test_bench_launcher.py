@@ -42,6 +42,31 @@ def test_world_size_contradicting_gpus_is_an_error():
     assert r.returncode != 0 and "contradicts WORLD_SIZE=2" in r.stderr
 
 
+def test_steps_below_one_is_refused():
+    r = _run(["--gpus", "1", "--steps", "0"])
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr and r.stdout.strip() == ""
+
+
+def test_dump_outputs_writes_the_frame_or_a_fixed_sample(tmp_path, monkeypatch):
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    frame = np.random.default_rng(1).random((72, 96, 3))
+    assert bench.dump_outputs(str(tmp_path / "a"), frame) == ["frame.npy"]
+    got = np.load(tmp_path / "a" / "frame.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, frame)
+    # above the byte cap: a seeded sample of pixels, the same on every call, within the cap
+    cap = 64 * 1024
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", cap)
+    names = ["frame_sample.npy", "frame_sample_pixels.npy"]
+    for d in ("b", "c"):
+        assert bench.dump_outputs(str(tmp_path / d), frame) == names
+    px, vals = np.load(tmp_path / "b" / names[1]), np.load(tmp_path / "b" / names[0])
+    assert px.dtype == vals.dtype == np.float64 and 0 < len(px) and vals.shape == (len(px), 3) and px.nbytes + vals.nbytes <= cap
+    assert np.array_equal(vals, frame.reshape(-1, 3)[px.astype(np.int64)])
+    assert all(np.array_equal(np.load(tmp_path / "b" / n), np.load(tmp_path / "c" / n)) for n in names)
+
+
 def test_rank_command_is_the_drivers():
     sys.path.insert(0, ROOT)
     import bench
@@ -186,3 +211,23 @@ def test_single_process_mode_renders_through_rt_render_multi(tmp_path):
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in out, k
     assert np.array_equal(np.load(out_npy), _plain_frame(96, 72, 8))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("launch", ["one-process", "single-process"])
+def test_dump_outputs_holds_the_last_timed_steps_frame(launch, tmp_path):
+    """`--dump-outputs DIR`: the stitched f64 frame of the last timed step as DIR/frame.npy, bit-identical to the plain render;
+    --steps sets the number of timed steps and ms_per_step is the timed loop's wall time per step."""
+    import numpy as np
+    d = tmp_path / "out"
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "0", "--width", "96", "--height", "72", "--spp", "8", "--cpu-spp", "0", "--dump-outputs", str(d)]
+    if launch == "single-process":
+        args.append("--single-process")
+    r = _run(args)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 3 and sum(x["samples"] for x in out["ranks"]) == 96 * 72 * 8 * 3
+    assert out["ms_per_step"] == pytest.approx(out["wall_s"] * 1e3 / 3)
+    assert out["dumped_outputs"] == ["frame.npy"] and sorted(os.listdir(d)) == ["frame.npy"]
+    got = np.load(d / "frame.npy")
+    assert got.dtype == np.float64 and got.shape == (72, 96, 3) and np.array_equal(got, _plain_frame(96, 72, 8))

@@ -73,6 +73,8 @@ def lib():
     L.orc_render_sppm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64, c_int_p, C.c_double, C.c_int,
                                   c_double_p, c_double_p, c_u64_p]
     L.orc_hit.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, C.c_double, C.c_double, c_double_p]
+    L.orc_hit_batch.argtypes = [C.c_void_p, C.c_int64, c_double_p, C.c_double, C.c_double, C.c_int, c_double_p]
+    L.orc_camera_rays.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, c_double_p]
     L.orc_aabb_hit.argtypes = [c_double_p, c_double_p, c_double_p, C.c_double, C.c_double]
     L.orc_scatter.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, C.c_int, C.c_double, C.c_double,
                               C.c_uint64, C.c_uint64, C.c_uint64, c_double_p]
@@ -81,6 +83,10 @@ def lib():
     L.orc_rng_stream.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, c_u64_p]
     L.orc_rng_f64.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, c_double_p]
     L.orc_det_sin.restype = C.c_double
+    L.orc_det_acos.restype = C.c_double
+    L.orc_det_acos.argtypes = [C.c_double]
+    L.orc_det_atan2.restype = C.c_double
+    L.orc_det_atan2.argtypes = [C.c_double, C.c_double]
     L.orc_det_sin.argtypes = [C.c_double]
     L.orc_tex_noise.argtypes = [C.c_void_p, C.c_double, C.c_uint64]
     L.orc_noise_value.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p]
@@ -300,6 +306,17 @@ class Scene:
         return dict(t=out[1], p=np.array(out[2:5]), normal=np.array(out[5:8]), front_face=bool(out[8]), uv=(out[9], out[10]),
                     prim_id=int(out[11]))
 
+    def hit_batch(self, rays, t_min=1e-3, t_max=float("inf"), n_workers=None):
+        """hit() of the root for every row of rays [n, 6] (orig, dir) on n_workers threads: -> [n, 12] records, all zero on a miss
+        {hit, t, p[3], normal[3], front_face, u, v, prim_id} -- the layout of the product's World.debug_hit."""
+        if n_workers is None:
+            n_workers = os.cpu_count() or 1
+        r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        out = np.zeros((r.shape[0], 12), dtype=np.float64)
+        self._chk(self.L.orc_hit_batch(self.h, r.shape[0], r.ctypes.data_as(c_double_p), float(t_min), float(t_max), int(n_workers),
+                                       out.ctypes.data_as(c_double_p)), "hit_batch")
+        return out
+
     def scatter(self, mat, ray_o, ray_d, p, normal, front_face, uv=(0.0, 0.0), key=(1, 0, 0)):
         out = (C.c_double * 14)()
         ray6 = (C.c_double * 6)(*[float(x) for x in list(ray_o) + list(ray_d)])
@@ -312,6 +329,12 @@ class Scene:
         out = (C.c_double * 6)()
         self._chk(self.L.orc_camera_ray(self.h, width, height, x, y, int(seed), int(sample), out), "camera_ray")
         return np.array(out[:3]), np.array(out[3:])
+
+    def camera_rays(self, width, height, seed=1, sample=0):
+        """camera_ray() of every pixel of the frame: -> [height, width, 6] (orig, dir), y down"""
+        out = np.zeros((height, width, 6), dtype=np.float64)
+        self._chk(self.L.orc_camera_rays(self.h, int(width), int(height), int(seed), int(sample), out.ctypes.data_as(c_double_p)), "camera_rays")
+        return out
 
 
 # ---------------------------------------------------------------------------
@@ -365,6 +388,14 @@ def aabb_hit(box_min, box_max, orig, direction, t_min, t_max):
 
 def det_ln(x):
     return lib().orc_det_ln(float(x))
+
+
+def det_acos(x):
+    return lib().orc_det_acos(float(x))
+
+
+def det_atan2(y, x):
+    return lib().orc_det_atan2(float(y), float(x))
 
 
 def schlick(cosine, ref_idx):

@@ -34,6 +34,8 @@
 //   D8. ConstantMedium::hit's `.ln()` is the deterministic algorithm rtamd-ln-1 (det_ln below; < 1 ulp from libm's log),
 //       and the phase function is the reference's commented-out Isotropic (material.rs:213-231) classified as a
 //       pass-through (Specular) interaction.
+//   D10. Sphere::get_uv's acos / atan2 are the deterministic rtamd-acos-1 / rtamd-atan2-1 (det_acos / det_atan2 below;
+//       < 1 ulp from libm's), so that a sphere's uv -- an ImageTexture's texel -- matches the kernels' to the bit.
 //
 // Instrumentation: every AABB / primitive / transform test is counted so the
 // "algorithmic bytes per sample" of SURVEY.md s8d can be computed in the
@@ -644,14 +646,110 @@ struct HitableList : Hitable {
     }
 };
 
+// rtamd-acos-1 / rtamd-atan2-1 (D10): Sphere::get_uv's acos and atan2.  libm's last bit differs between glibc and the device library
+// and an ImageTexture turns uv into a texel, so oracle and kernel evaluate the same algorithm: the reductions and approximations
+// published for fdlibm's e_acos.c, s_atan.c and e_atan2.c, IEEE + - * / and sqrt only, no fused operations.  Restated here
+// independently of the product's csrc/common/detuv.h; tests/test_golden.py pins it against numpy to 1 ulp.
+static inline uint32_t hi32(double x) { uint64_t b; std::memcpy(&b, &x, 8); return (uint32_t)(b >> 32); }
+static inline uint32_t lo32(double x) { uint64_t b; std::memcpy(&b, &x, 8); return (uint32_t)b; }
+static inline double poly_r(double z) {  // e_acos.c's R(z) = p(z) / q(z)
+    static const double P[6] = {1.66666666666666657415e-01, -3.25565818622400915405e-01, 2.01212532134862925881e-01,
+                                -4.00555345006794114027e-02, 7.91534994289814532176e-04, 3.47933107596021167570e-05};
+    static const double Q[4] = {-2.40339491173441421878e+00, 2.02094576023350569471e+00, -6.88283971605453293030e-01, 7.70381505559019352791e-02};
+    double p = z * (P[0] + z * (P[1] + z * (P[2] + z * (P[3] + z * (P[4] + z * P[5])))));
+    double q = 1.0 + z * (Q[0] + z * (Q[1] + z * (Q[2] + z * Q[3])));
+    return p / q;
+}
+static double det_acos(double x) {
+    static const double PI_ = 3.14159265358979311600e+00, PIO2_HI = 1.57079632679489655800e+00, PIO2_LO = 6.12323399573676603587e-17;
+    uint32_t hx = hi32(x), ix = hx & 0x7fffffffu;
+    bool neg = (hx >> 31) != 0;
+    if (ix >= 0x3ff00000u) {
+        if (ix == 0x3ff00000u && lo32(x) == 0u) return neg ? PI_ + 2.0 * PIO2_LO : 0.0;
+        return std::numeric_limits<double>::quiet_NaN();
+    }
+    if (ix < 0x3fe00000u) {
+        if (ix <= 0x3c600000u) return PIO2_HI + PIO2_LO;
+        double r = poly_r(x * x);
+        return PIO2_HI - (x - (PIO2_LO - x * r));
+    }
+    if (neg) {
+        double z = (1.0 + x) * 0.5;
+        double r = poly_r(z);
+        double s = std::sqrt(z);
+        double w = r * s - PIO2_LO;
+        return PI_ - 2.0 * (s + w);
+    }
+    double z = (1.0 - x) * 0.5;
+    double s = std::sqrt(z);
+    uint64_t sb;
+    std::memcpy(&sb, &s, 8);
+    sb &= ~0xffffffffull;
+    double df;
+    std::memcpy(&df, &sb, 8);
+    double c = (z - df * df) / (s + df);
+    double r = poly_r(z);
+    return 2.0 * (df + (r * s + c));
+}
+static double det_atan(double x) {
+    static const double HI[4] = {4.63647609000806093515e-01, 7.85398163397448278999e-01, 9.82793723247329054082e-01, 1.57079632679489655800e+00};
+    static const double LO[4] = {2.26987774529616870924e-17, 3.06161699786838301793e-17, 1.39033110312309984516e-17, 6.12323399573676603587e-17};
+    static const double AT[11] = {3.33333333333329318027e-01, -1.99999999998764832476e-01, 1.42857142725034663711e-01, -1.11111104054623557880e-01,
+                                  9.09088713343650656196e-02, -7.69187620504482999495e-02, 6.66107313738753120669e-02, -5.83357013379057348645e-02,
+                                  4.97687799461593236017e-02, -3.65315727442169155270e-02, 1.62858201153657823623e-02};
+    uint32_t hx = hi32(x), ix = hx & 0x7fffffffu;
+    bool neg = (hx >> 31) != 0;
+    int id = -1;
+    if (ix >= 0x44100000u) {
+        if (x != x) return x + x;
+        return neg ? -HI[3] - LO[3] : HI[3] + LO[3];
+    }
+    if (ix < 0x3fdc0000u) {
+        if (ix < 0x3e200000u) return x;
+    } else {
+        x = std::fabs(x);
+        if (ix < 0x3fe60000u) { id = 0; x = (2.0 * x - 1.0) / (2.0 + x); }
+        else if (ix < 0x3ff30000u) { id = 1; x = (x - 1.0) / (x + 1.0); }
+        else if (ix < 0x40038000u) { id = 2; x = (x - 1.5) / (1.0 + 1.5 * x); }
+        else { id = 3; x = -1.0 / x; }
+    }
+    double z = x * x, w = z * z;
+    double s1 = z * (AT[0] + w * (AT[2] + w * (AT[4] + w * (AT[6] + w * (AT[8] + w * AT[10])))));
+    double s2 = w * (AT[1] + w * (AT[3] + w * (AT[5] + w * (AT[7] + w * AT[9]))));
+    if (id < 0) return x - x * (s1 + s2);
+    double r = HI[id] - ((x * (s1 + s2) - LO[id]) - x);
+    return neg ? -r : r;
+}
+static double det_atan2(double y, double x) {
+    static const double PI_O_4 = 7.8539816339744827900e-01, PI_O_2 = 1.5707963267948965580e+00, PI_ = 3.1415926535897931160e+00,
+                        PI_LO = 1.2246467991473531772e-16;
+    if (std::isnan(x) || std::isnan(y)) return x + y;
+    if (x == 1.0) return det_atan(y);
+    bool yneg = std::signbit(y), xneg = std::signbit(x);
+    if (y == 0.0) return xneg ? (yneg ? -PI_ : PI_) : y;
+    if (x == 0.0) return yneg ? -PI_O_2 : PI_O_2;
+    if (std::isinf(x)) {
+        if (std::isinf(y)) return xneg ? (yneg ? -3.0 * PI_O_4 : 3.0 * PI_O_4) : (yneg ? -PI_O_4 : PI_O_4);
+        return xneg ? (yneg ? -PI_ : PI_) : (yneg ? -0.0 : 0.0);
+    }
+    if (std::isinf(y)) return yneg ? -PI_O_2 : PI_O_2;
+    int k = ((int)(hi32(y) & 0x7fffffffu) - (int)(hi32(x) & 0x7fffffffu)) >> 20;
+    double z;
+    if (k > 60) z = PI_O_2 + 0.5 * PI_LO;
+    else if (xneg && k < -60) z = 0.0;
+    else z = det_atan(std::fabs(y / x));
+    if (!xneg) return yneg ? -z : z;
+    return yneg ? (z - PI_LO) - PI_ : PI_ - (z - PI_LO);
+}
+
 // Sphere -- raytracer/src/objects/sphere.rs:8-62
 struct Sphere : Hitable {
     Vec3 center;
     double radius;
     const Material* material;
     static void get_uv(Vec3 p, double& u, double& v) {  // :16-20
-        double theta = std::acos(-p.y);
-        double phi = std::atan2(-p.z, p.x) + PI;
+        double theta = det_acos(-p.y);             // D10: rtamd-acos-1 / rtamd-atan2-1 for libm's acos / atan2
+        double phi = det_atan2(-p.z, p.x) + PI;
         u = phi * FRAC_1_PI * 0.5;
         v = theta * FRAC_1_PI;
     }
@@ -1566,6 +1664,8 @@ int orc_mat_isotropic(void* s, int t) {
 }
 double orc_det_ln(double x) { return det_ln(x); }
 double orc_det_sin(double x) { return det_sin(x); }
+double orc_det_acos(double x) { return det_acos(x); }
+double orc_det_atan2(double y, double x) { return det_atan2(y, x); }
 // D9
 int orc_tex_noise(void* s, double scale, uint64_t seed) {
     Scene& sc = *(Scene*)s;
@@ -1853,6 +1953,29 @@ int orc_hit(void* s, int o, const double* orig, const double* dir, double t_min,
     }
     return ORC_OK;
 }
+// orc_hit of the root for n rays (rays n*6 = orig, dir) on n_workers threads, each over a contiguous share of the rays: out n*12 =
+// orc_hit's record per ray, all zero on a miss.  A UnitZero on any ray fails the whole call (ORC_ERR_UNIT_ZERO), as orc_hit does.
+int orc_hit_batch(void* s, int64_t n, const double* rays, double t_min, double t_max, int n_workers, double* out) {
+    Scene& sc = *(Scene*)s;
+    if (!sc.root || n < 0) return ORC_ERR_ARG;
+    if (n_workers < 1) n_workers = 1;
+    std::atomic<int> err{ORC_OK};
+    auto worker = [&](int64_t begin, int64_t end) {
+        for (int64_t i = begin; i < end; i++) {
+            double* q = out + 12 * i;
+            for (int k = 0; k < 12; k++) q[k] = 0.;
+            const double* ro = rays + 6 * i;
+            if (orc_hit(s, -1, ro, ro + 3, t_min, t_max, q) != ORC_OK) {
+                err.store(ORC_ERR_UNIT_ZERO);
+                return;
+            }
+        }
+    };
+    std::vector<std::thread> th;
+    for (int w = 0; w < n_workers; w++) th.emplace_back(worker, n * w / n_workers, n * (w + 1) / n_workers);
+    for (auto& t : th) t.join();
+    return err.load();
+}
 // The same with the RNG stream (seed, pixel, sample) in the context (ConstantMedium::hit draws from it); *draws = numbers consumed
 int orc_hit_rng(void* s, int o, const double* orig, const double* dir, double t_min, double t_max, uint64_t seed, uint64_t pixel, uint64_t sample,
                 double* out12, int* draws) {
@@ -1927,6 +2050,14 @@ int orc_camera_ray(void* s, int width, int height, int x, int y, uint64_t seed, 
     Ray r = sc.cam.get_ray(u, 1.0 - v, rng);
     out6[0] = r.orig.x; out6[1] = r.orig.y; out6[2] = r.orig.z;
     out6[3] = r.dir.x; out6[4] = r.dir.y; out6[5] = r.dir.z;
+    return ORC_OK;
+}
+// orc_camera_ray of every pixel of a width x height frame: out W*H*6, row-major (y down), [y*W + x] = orig[3], dir[3]
+int orc_camera_rays(void* s, int width, int height, uint64_t seed, uint64_t sample, double* out) {
+    Scene& sc = *(Scene*)s;
+    if (!sc.cam_set || width < 1 || height < 1) return ORC_ERR_ARG;
+    for (int y = 0; y < height; y++)
+        for (int x = 0; x < width; x++) orc_camera_ray(s, width, height, x, y, seed, sample, out + 6 * ((size_t)y * width + x));
     return ORC_OK;
 }
 

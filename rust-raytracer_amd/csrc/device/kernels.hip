@@ -32,6 +32,7 @@
 #include "../common/flat.h"
 #include "../common/detlog.h"
 #include "../common/detsin.h"
+#include "../common/detuv.h"
 #include "../common/rng.h"
 #include "../common/schedule.h"
 #include "device.h"
@@ -1329,13 +1330,14 @@ DEV D3 tex_color(const Acc& A, int tex, const Rec& rec) {  // material.rs:52-84
 
 DEV void sphere_uv(D3 outward, double& u, double& v) {  // get_uv, sphere.rs:16-20 (inline: a call here costs Cornell 4 %)
     const double PI = 3.14159265358979323846264338327950288, FRAC_1_PI = 0.318309886183790671537767526745028724;
-    double theta = acos(-outward.y);
-    double phi = atan2(-outward.z, outward.x) + PI;
+    double theta = det_acos(-outward.y);  // D10: rtamd-acos-1 / rtamd-atan2-1, bit-identical with the oracle (libm's last bit is not)
+    double phi = det_atan2(-outward.z, outward.x) + PI;
     u = phi * FRAC_1_PI * 0.5;
     v = theta * FRAC_1_PI;
 }
-// Build the HitRecord of the winning leaf only (the reference builds one per candidate).
-template <int GENERAL>
+// Build the HitRecord of the winning leaf only (the reference builds one per candidate).  uv is computed only where an ImageTexture
+// reads it, unless ALL_UV (the closest-hit diagnostic, which returns the whole record).
+template <int GENERAL, bool ALL_UV = false>
 DEV Rec materialize(const Acc& A, const Hit& h, D3 wo, D3 wd, int* err) {
     Rec rec;
     uint32_t kind = h.kp & NK_MASK, pl = h.kp >> NK_BITS;
@@ -1354,14 +1356,14 @@ DEV Rec materialize(const Acc& A, const Hit& h, D3 wo, D3 wd, int* err) {
         rec.mat = A.sphere_mat[pl];
         D3 p = add(o, muls(d, h.t));
         outward = divs(sub(p, mk(c0.x, c0.y, c1.x)), c1.y);
-        want_uv = A.texs[A.mats[rec.mat].tex].type == 2;
+        want_uv = ALL_UV || A.texs[A.mats[rec.mat].tex].type == 2;
         if (want_uv) sphere_uv(outward, rec.u, rec.v);  // get_uv, sphere.rs:16-20 (only an ImageTexture reads it)
     } else if (GENERAL == 2 && kind == NK_MSPHERE) {  // D9: outward_normal = (p - center(r.time)) / radius, get_uv as a sphere
         const double* q = A.msph + 10 * pl;
         rec.mat = (int)q[9];
         D3 p = add(o, muls(d, h.t));
         outward = divs(sub(p, msphere_center(q, ray_time(A))), q[8]);
-        want_uv = A.texs[A.mats[rec.mat].tex].type == 2;
+        want_uv = ALL_UV || A.texs[A.mats[rec.mat].tex].type == 2;
         if (want_uv) sphere_uv(outward, rec.u, rec.v);
     } else if (GENERAL && kind == NK_MEDIUM_END) {  // ConstantMedium: arbitrary normal (1,0,0), uv (0,0), phase function (medium.rs:43-49)
         rec.mat = A.media[pl].mat;
@@ -1383,7 +1385,7 @@ DEV Rec materialize(const Acc& A, const Hit& h, D3 wo, D3 wd, int* err) {
         }
         rec.mat = A.rect_mat[pl];
         outward = mk(axis == 0 ? 1. : 0., axis == 1 ? 1. : 0., axis == 2 ? 1. : 0.);
-        if (A.texs[A.mats[rec.mat].tex].type == 2) {
+        if (ALL_UV || A.texs[A.mats[rec.mat].tex].type == 2) {
             D3 p = add(o, muls(d, h.t));
             double a, b;
             if (axis == 2) { a = p.x; b = p.y; }
@@ -3472,8 +3474,7 @@ __global__ void hit_kernel(FlatView sv, int accel, size_t n, const double* rays,
     double* q = out + 12 * i;
     for (int k = 0; k < 12; k++) q[k] = 0.;
     if (h.node < 0) return;
-    Rec rec = materialize<true>(A, h, o, d, err);
-    // uv is materialised lazily (only for image textures); recompute it here for the diagnostic
+    Rec rec = materialize<true, true>(A, h, o, d, err);  // with uv for every primitive: the render kernels compute it only for image textures
     q[0] = 1.;
     q[1] = h.t;
     q[2] = rec.p.x; q[3] = rec.p.y; q[4] = rec.p.z;

@@ -264,7 +264,7 @@ def test_final_scene_as_named_bit_exact(kernel):
 @pytest.mark.gpu
 def test_final_scene_as_named_full_size_windows_match_the_oracle():
     """C5 exactly as BASELINE words it: 1600 x 1600, 4 000 spp, shutter [0, 1) -- 10.24 G samples in ONE launch.  Five 8 x 8 windows spread over
-    the frame equal the oracle's values bit for bit (the in-kernel fold in sample order at this size and length, the time draws, the
+    the frame, and the eight of seeded_windows.seeded_windows (corners, a tile corner, unaligned positions), equal the oracle's values bit for bit (the in-kernel fold in sample order at this size and length, the time draws, the
     MEDIA + book-2 kernel variant with the tables in L2); and the same frame rendered in eight instalments of 500 samples through the
     resumable entry point with the state held by the host (rt_render_accumulate / rt_accum_finalize) is that frame, bit for bit."""
     import oracle
@@ -280,7 +280,8 @@ def test_final_scene_as_named_full_size_windows_match_the_oracle():
     cam = rtamd.Camera((f, t), up, vfov, asp, ap, fd)
     img, st = w.render(cam, width=1600, height=1600, spp=4000, seed=1, shutter=shapes.FINAL_SCENE_SHUTTER)
     assert st["samples"] == 1600 * 1600 * 4000 and st["kernel_used"] == 2 and st["launches"] == 1 and np.isfinite(img).all()
-    for (x0, y0) in [(560, 440), (1040, 1000), (800, 1400), (320, 160), (1200, 600)]:
+    from seeded_windows import seeded_windows
+    for (x0, y0) in [(560, 440), (1040, 1000), (800, 1400), (320, 160), (1200, 600)] + seeded_windows(1600, 1600, 4000):
         exp, _ = o.render(1600, 1600, 4000, seed=1, window=(x0, y0, x0 + 8, y0 + 8), n_jobs=16)
         assert np.array_equal(img[y0:y0 + 8, x0:x0 + 8], exp), "window at (%d, %d)" % (x0, y0)
     p = rtamd.default_params(width=1600, height=1600, spp=4000, seed=1, time0=shapes.FINAL_SCENE_SHUTTER[0], time1=shapes.FINAL_SCENE_SHUTTER[1])

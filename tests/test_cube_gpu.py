@@ -119,7 +119,7 @@ def test_cube_hit_records_match_the_six_rectangle_scan(variant, as_list):
                 continue
             assert got[1] == h["t"], (i, k, got[1], h["t"])
             assert np.array_equal(got[2:5], h["p"]) and np.array_equal(got[5:8], h["normal"]) and bool(got[8]) == h["front_face"], (i, k)
-            if got[9] != 0.0 or got[10] != 0.0:                        # (the product computes uv only for a material that reads it: an ImageTexture)
+            if got[9] != 0.0 or got[10] != 0.0:                        # (the diagnostic computes uv for every primitive; a triangle's is 0)
                 assert (got[9], got[10]) == h["uv"], (i, k, got[9:11], h["uv"])   # uv of the winning SIDE (the rectangle's own formula)
                 nuv += k == 1
         nhit += h is not None

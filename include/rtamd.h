@@ -213,7 +213,11 @@ int rt_object_mesh(rt_scene* s, int n_vert, const double* positions, const doubl
                    int material, int synthesize_normals, uint64_t bvh_seed);
 /* Mesh::load_obj(path, material): tobj{single_index, triangulate} semantics, models[0] */
 int rt_object_mesh_obj(rt_scene* s, const char* obj_path, int material, int synthesize_normals, uint64_t bvh_seed);
-/* objects/transform.rs:17 Transform::new(rotate_in_degree, scale, translate, obj): M = T*S*Rx*Ry*Rz */
+/* objects/transform.rs:17 Transform::new(rotate_in_degree, scale, translate, obj): M = T*S*Rx*Ry*Rz
+ * Transforms may nest (a Transform whose object is, or contains, another Transform) up to 8 levels; rt_scene_commit refuses a deeper
+ * chain with RT_ERR_UNSUPPORTED.  A scene that nests renders through kernels 1 and 2 (the automatic choice is kernel 2) with every
+ * integrator; kernels 5 / 6 refuse it with RT_ERR_UNSUPPORTED (rt_scene_info.accel_compact = 0).  A light under a Transform is refused
+ * at commit; a ConstantMedium under a Transform, at any depth, renders through kernel 1 only, as at depth 1. */
 int rt_object_transform(rt_scene* s, const double rotate_deg[3], const double scale[3], const double translate[3], int object);
 /* Transform as the reference stores it (transform.rs:9-14: obj, trans, inverse_trans; row-major 4x4).  inverse_trans may be
  * NULL (computed as try_inverse does; RT_ERR_SINGULAR if there is none). */

@@ -23,8 +23,8 @@ enum NodeKind : uint32_t {
     NK_RECT_XZ = 3,      // constant axis 1 (XZRectangle)
     NK_RECT_XY = 4,      // constant axis 2 (XYRectangle)
     NK_TRI = 5,          // Triangle::hit; payload = triangle index
-    NK_XFORM_BEGIN = 6,  // Transform::hit entry: ray -> object space (transform.rs:153-156); payload = xform index
-    NK_XFORM_END = 7,    // leave the Transform: restore the world ray
+    NK_XFORM_BEGIN = 6,  // Transform::hit entry: ray -> object space (transform.rs:153-156); payload = xform index (nested scenes: chain id)
+    NK_XFORM_END = 7,    // leave the Transform: restore the world ray (nested scenes: payload = parent chain + 1, 0 = the world ray)
     // 8 = NK_INSTANCE (accel items only, below)
     // ConstantMedium::hit (medium.rs:25-53) = two closest-hit queries on the boundary, then one random draw.  The boundary's
     // subtree is emitted TWICE between three brackets; payload = medium index:
@@ -47,6 +47,21 @@ static const uint32_t NK_BITS = 4;
 static const uint32_t NK_MASK = 15;
 
 // per node: meta[2*n] = kind | payload << 4 ; meta[2*n+1] = skip
+//
+// Nested Transforms (a Transform whose child is, or contains, another Transform; transform.rs:152-165 level by level).  Every distinct
+// path of Transforms from the root is a CHAIN; a scene with a chain of two or more levels is "nested", and only then:
+//   - NK_XFORM_BEGIN's payload is the chain it enters, NK_XFORM_END's the parent chain + 1 (0: back to world space), and Hit::xf
+//     carries a chain id instead of an xform index;
+//   - the tie view (FlatView::off_tie_view, 8 words) is followed by one ChainRec per chain.
+// Scenes of depth <= 1 keep the blob they always had (payload = xform index, no chain records), so their fingerprints do not move.
+// The kernels select the chain walk (GENERAL == 3) from FlatScene::xf_nest; the accel is not built for nested scenes: kernel 1 renders.
+static const uint32_t XF_MAX_DEPTH = 8;  // deepest chain a scene may hold (commit refuses deeper ones)
+struct ChainRec {
+    uint32_t depth;       // levels, 1 .. XF_MAX_DEPTH
+    uint32_t inner;       // xform index of the innermost level (= xf[depth - 1]): what NK_XFORM_BEGIN applies to the parent's ray
+    uint32_t xf[XF_MAX_DEPTH];  // xform index per level, outermost first
+};
+static const uint32_t CHAIN_WORDS = sizeof(ChainRec) / 4;
 struct MediumDev {  // objects/medium.rs:9-13
     double neg_inv_density;  // -1 / d
     int32_t mat;             // phase function (an Isotropic material)

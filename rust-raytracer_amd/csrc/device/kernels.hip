@@ -527,6 +527,23 @@ DEV bool tie_flagged(int xf) { return (((uint32_t)xf >> 30) & 1u) != ((uint32_t)
 #define TIE_W (1.0 + 2.3283064365386963e-10)  // 1 + 2^-32
 #endif
 
+// Nested Transforms (GENERAL == 3; common/flat.h "Nested Transforms"): the chain records follow the tie view's eight words.  A chain's
+// ray is never kept per level (a per-lane, runtime-indexed array of rays lives in scratch memory): it is recomputed from the world ray
+// by applying the levels' inverses outermost first -- Transform::hit's own sequence of operations (transform.rs:153-156), so the bits
+// are the reference's.
+static const uint32_t CHAIN_ALL = XF_MAX_DEPTH;
+DEV const uint32_t* chain_rec(const Acc& A, uint32_t c) { return A.tie_view + 8 + CHAIN_WORDS * c; }
+// o, d (the world ray on entry) -> the ray the first min(levels, depth) levels of chain c hand to their child
+DEV void chain_ray(const Acc& A, uint32_t c, uint32_t levels, D3& o, D3& d) {
+    const uint32_t* C = chain_rec(A, c);
+    const uint32_t n = min(C[0], levels);
+    for (uint32_t l = 0; l < n; l++) {
+        const double* Minv = A.xforms + 32 * C[2 + l];
+        o = xf_point(Minv, o);
+        d = xf_dir(Minv, d);
+    }
+}
+
 // World::hit -> BVHNode::hit / Vec::hit / Transform::hit, flattened (common/flat.h).
 // Visits nodes in the reference's own order; a leaf is accepted when t_min <= t <= best
 // (inclusive, so a later leaf wins an exact tie -- sphere.rs:36, rectangle.rs:20, mesh.rs:96).
@@ -622,7 +639,7 @@ DEV Hit traverse(const Acc& A, D3 wo, D3 wd, double t_min, double t_max, Rng* rn
                     h.xf = cur_xf;
                     h.kp = m.x + (side << NK_BITS);
                 }
-            } else if (GENERAL == 2 && kind == NK_MSPHERE) {
+            } else if (GENERAL >= 2 && kind == NK_MSPHERE) {
                 double t;
                 if (msphere_hit(A.msph + 10 * pl, ray_time(A), o.x, o.y, o.z, d.x, d.y, d.z, a, t_min, h.t, &t)) {
                     h.t = t;
@@ -639,18 +656,25 @@ DEV Hit traverse(const Acc& A, D3 wo, D3 wd, double t_min, double t_max, Rng* rn
                     h.kp = m.x;
                 }
             } else if (kind == NK_XFORM_BEGIN) {  // transform.rs:153-156
-                const double* Minv = A.xforms + 32 * pl;
-                o = xf_point(Minv, wo);
-                d = xf_dir(Minv, wd);
+                if (GENERAL == 3) {  // chain pl: its innermost level applied to the PARENT's ray, which is the current one
+                    const double* Minv = A.xforms + 32 * chain_rec(A, pl)[1];
+                    o = xf_point(Minv, o);
+                    d = xf_dir(Minv, d);
+                } else {
+                    const double* Minv = A.xforms + 32 * pl;
+                    o = xf_point(Minv, wo);
+                    d = xf_dir(Minv, wd);
+                }
                 inv = mk(1.0 / d.x, 1.0 / d.y, 1.0 / d.z);
                 a = sqlen(d);
                 cur_xf = (int)pl;
             } else {  // NK_XFORM_END
                 o = wo;
                 d = wd;
+                if (GENERAL == 3 && pl != 0u) chain_ray(A, pl - 1u, CHAIN_ALL, o, d);  // back to the parent chain's ray
                 inv = mk(1.0 / d.x, 1.0 / d.y, 1.0 / d.z);
                 a = sqlen(d);
-                cur_xf = -1;
+                cur_xf = GENERAL == 3 ? (int)pl - 1 : -1;
             }
             n++;
         } else {
@@ -888,7 +912,9 @@ DEV Hit traverse2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, d
     if (resume) {  // a suspended walk goes on: its best hit so far, and the ray in the space of the instance it is inside of
         h = *h_in;
         cur_xf = ws->cur_xf;
-        if (GENERAL && cur_xf >= 0) {
+        if (GENERAL == 3 && cur_xf >= 0) {
+            chain_ray(A, (uint32_t)cur_xf, CHAIN_ALL, o, d);
+        } else if (GENERAL && cur_xf >= 0) {
             const double* Minv = A.xforms + 32 * cur_xf;
             o = xf_point(Minv, wo);
             d = xf_dir(Minv, wd);
@@ -1025,7 +1051,7 @@ DEV Hit traverse2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, d
                 } else if (GENERAL) {
                     if (kind == NK_RECT_YZ || kind == NK_RECT_XZ || kind == NK_RECT_XY) {
                         got = rect_hit(A.rects + 3 * pl, (int)kind - (int)NK_RECT_YZ, o, d, t_min, t_far, t);
-                    } else if (GENERAL == 2 && kind == NK_MSPHERE) {
+                    } else if (GENERAL >= 2 && kind == NK_MSPHERE) {
                         got = msphere_hit(A.msph + 10 * pl, ray_time(A), o.x, o.y, o.z, d.x, d.y, d.z, a, t_min, t_far, &t);
                     } else if (kind == NK_CUBE) {
                         PH_EV(12);
@@ -1071,18 +1097,27 @@ DEV Hit traverse2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, d
             }
             if (GENERAL && ENTER && enter != REF_DONE) {  // Transform::hit, transform.rs:153-156
                 uint2 in = A.inst2[enter];
-                const double* Minv = A.xforms + 32 * in.x;
-                o = xf_point(Minv, wo);
-                d = xf_dir(Minv, wd);
+                // GENERAL == 3: in.x is a chain; its innermost level maps the current (parent's) ray, and the restore marker
+                // carries the parent chain + 1 (0: world space) -- one marker per level on the stack
+                const uint32_t restore = GENERAL == 3 ? REF_RESTORE | (uint32_t)(cur_xf + 1) : REF_RESTORE;
+                if (GENERAL == 3) {
+                    const double* Minv = A.xforms + 32 * chain_rec(A, in.x)[1];
+                    o = xf_point(Minv, o);
+                    d = xf_dir(Minv, d);
+                } else {
+                    const double* Minv = A.xforms + 32 * in.x;
+                    o = xf_point(Minv, wo);
+                    d = xf_dir(Minv, wd);
+                }
                 a = sqlen(d);
                 cur_xf = (int)in.x;
                 r = make_ray32(o, d, t_min, TRACK ? track_bound(*track, h.t) : h.t);
                 if (WIDE) {
                     ray32_wide_addr(r, A.n2w_lds);
-                    *(AS_L uint32_t*)(uintptr_t)spw = REF_RESTORE;
+                    *(AS_L uint32_t*)(uintptr_t)spw = restore;
                     spw += spw_step;
                 } else {
-                    stk[sp] = REF_RESTORE;
+                    stk[sp] = restore;
                     sp += stride;
                 }
                 cur = WIDE ? wide_ref(in.y) : in.y;
@@ -1092,8 +1127,13 @@ DEV Hit traverse2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, d
         } else {  // REF_RESTORE: leave the Transform
             o = wo;
             d = wd;
-            a = sqlen(d);
             cur_xf = -1;
+            if (GENERAL == 3) {  // back to the parent chain's ray, recomputed from the world ray (see chain_ray)
+                const uint32_t pc = cur & ~(3u << REF_TAG_SHIFT);
+                if (pc != 0u) chain_ray(A, pc - 1u, CHAIN_ALL, o, d);
+                cur_xf = (int)pc - 1;
+            }
+            a = sqlen(d);
             r = make_ray32(o, d, t_min, TRACK ? track_bound(*track, h.t) : h.t);
             if (WIDE) ray32_wide_addr(r, A.n2w_lds);
         }
@@ -1315,7 +1355,7 @@ DEV D3 tex_color(const Acc& A, int tex, const Rec& rec) {  // material.rs:52-84
         type = 0;
     }
     if (type == 0) return mk(t->color[0], t->color[1], t->color[2]);
-    if (GENERAL == 2 && type == 3) {  // D9: noise_texture::value = color(1, 1, 1) * 0.5 * (1 + sin(scale p.z + 10 turb(p)))
+    if (GENERAL >= 2 && type == 3) {  // D9: noise_texture::value = color(1, 1, 1) * 0.5 * (1 + sin(scale p.z + 10 turb(p)))
         const double m = noise_marble(A.texels + t->texel_off, t->color[0], rec.p.x, rec.p.y, rec.p.z);
         return mk(1. * m, 1. * m, 1. * m);
     }
@@ -1342,7 +1382,9 @@ DEV Rec materialize(const Acc& A, const Hit& h, D3 wo, D3 wd, int* err) {
     Rec rec;
     uint32_t kind = h.kp & NK_MASK, pl = h.kp >> NK_BITS;
     D3 o = wo, d = wd;
-    if (GENERAL && h.xf >= 0) {
+    if (GENERAL == 3 && h.xf >= 0) {
+        chain_ray(A, (uint32_t)h.xf, CHAIN_ALL, o, d);  // the innermost level's object-space ray
+    } else if (GENERAL && h.xf >= 0) {
         const double* Minv = A.xforms + 32 * h.xf;
         o = xf_point(Minv, wo);
         d = xf_dir(Minv, wd);
@@ -1358,7 +1400,7 @@ DEV Rec materialize(const Acc& A, const Hit& h, D3 wo, D3 wd, int* err) {
         outward = divs(sub(p, mk(c0.x, c0.y, c1.x)), c1.y);
         want_uv = ALL_UV || A.texs[A.mats[rec.mat].tex].type == 2;
         if (want_uv) sphere_uv(outward, rec.u, rec.v);  // get_uv, sphere.rs:16-20 (only an ImageTexture reads it)
-    } else if (GENERAL == 2 && kind == NK_MSPHERE) {  // D9: outward_normal = (p - center(r.time)) / radius, get_uv as a sphere
+    } else if (GENERAL >= 2 && kind == NK_MSPHERE) {  // D9: outward_normal = (p - center(r.time)) / radius, get_uv as a sphere
         const double* q = A.msph + 10 * pl;
         rec.mat = (int)q[9];
         D3 p = add(o, muls(d, h.t));
@@ -1410,7 +1452,20 @@ DEV Rec materialize(const Acc& A, const Hit& h, D3 wo, D3 wd, int* err) {
     rec.p = add(o, muls(d, h.t));
     rec.front_face = dot(d, outward) < 0.;
     rec.normal = unit(rec.front_face ? outward : neg(outward), err);
-    if (GENERAL && h.xf >= 0) {  // Transform::hit, transform.rs:157-161 (Q7, Q8)
+    if (GENERAL == 3 && h.xf >= 0) {  // Transform::hit level by level, innermost first: each level's front_face is its own ray's (Q7, Q8)
+        const uint32_t* C = chain_rec(A, (uint32_t)h.xf);
+        for (uint32_t l = C[0]; l-- > 0u;) {
+            const double* M = A.xforms + 32 * C[2 + l] + 16;
+            D3 lo = wo, ld = wd;
+            if (l + 1u < C[0]) chain_ray(A, (uint32_t)h.xf, l + 1u, lo, ld);  // the ray of level l (the innermost one's is d)
+            else ld = d;
+            D3 on = xf_dir(M, rec.normal);
+            rec.p = xf_point(M, rec.p);
+            rec.front_face = dot(ld, on) < 0.;
+            D3 un = unit(on, err);
+            rec.normal = rec.front_face ? un : neg(un);
+        }
+    } else if (GENERAL && h.xf >= 0) {  // Transform::hit, transform.rs:157-161 (Q7, Q8)
         const double* M = A.xforms + 32 * h.xf + 16;
         D3 on = xf_dir(M, rec.normal);
         rec.p = xf_point(M, rec.p);
@@ -2068,7 +2123,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
 #pragma unroll
         for (int i = 0; i < 25; i++) cfg[CFG_LVL + i] = rk.lvl[i / 5][i % 5];
     }
-    if (GENERAL == 2 && rk.time_slots) A.time_lds = (uint32_t)(uintptr_t)(AS_L char*)(cfg + CFG_WORDS);  // (8-aligned: every section before it is)
+    if (GENERAL >= 2 && rk.time_slots) A.time_lds = (uint32_t)(uintptr_t)(AS_L char*)(cfg + CFG_WORDS);  // (8-aligned: every section before it is)
     __syncthreads();
     double* wring = ring + ((size_t)blockIdx.x * (PT_BLOCK / 64) + (size_t)wave) * RING_UNITS * UNIT_DOUBLES;
 
@@ -2158,10 +2213,10 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
                         double v = ((double)y + rng.gen_f64()) / (double)(rk.height - 1);
                         double st = 1.0 - v;
                         D3 rd = muls(random_in_unit_disk(rng), cam.lens_radius);  // drawn even for aperture 0 (Q4)
-                        if (GENERAL == 2 && rk.time1 > rk.time0) {  // D9: ray(origin + offset, .., random_double(time0, time1)), after the lens sample
+                        if (GENERAL >= 2 && rk.time1 > rk.time0) {  // D9: ray(origin + offset, .., random_double(time0, time1)), after the lens sample
                             const double tm = rng.gen_range(rk.time0, rk.time1);
                             if (A.time_lds) *(AS_L double*)(uintptr_t)(A.time_lds + 8u * threadIdx.x) = tm;
-                        } else if (GENERAL == 2 && A.time_lds) {
+                        } else if (GENERAL >= 2 && A.time_lds) {
                             *(AS_L double*)(uintptr_t)(A.time_lds + 8u * threadIdx.x) = rk.time0;
                         }
                         D3 offset = add(muls(cam.u, rd.x), muls(cam.v, rd.y));
@@ -3396,6 +3451,16 @@ __global__ void math_kernel(int op, size_t n, const double* a, const double* b, 
     if (i >= n) return;
     out[i] = (op == 0) ? sqrt(a[i]) : (op == 2) ? det_ln(a[i]) : (op == 3) ? det_sin(a[i]) : a[i] / b[i];
 }
+// one row of rt_debug_hit_device's output: {hit, t, p, normal, front_face, u, v, node}
+DEV void hit_row(double* q, const Hit& h, const Rec& rec) {
+    q[0] = 1.;
+    q[1] = h.t;
+    q[2] = rec.p.x; q[3] = rec.p.y; q[4] = rec.p.z;
+    q[5] = rec.normal.x; q[6] = rec.normal.y; q[7] = rec.normal.z;
+    q[8] = rec.front_face ? 1. : 0.;
+    q[9] = rec.u; q[10] = rec.v;
+    q[11] = (double)h.node;
+}
 __global__ void hit_kernel(FlatView sv, int accel, size_t n, const double* rays, double t_min, double t_max, double* out, int* err) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -3475,13 +3540,41 @@ __global__ void hit_kernel(FlatView sv, int accel, size_t n, const double* rays,
     for (int k = 0; k < 12; k++) q[k] = 0.;
     if (h.node < 0) return;
     Rec rec = materialize<true, true>(A, h, o, d, err);  // with uv for every primitive: the render kernels compute it only for image textures
-    q[0] = 1.;
-    q[1] = h.t;
-    q[2] = rec.p.x; q[3] = rec.p.y; q[4] = rec.p.z;
-    q[5] = rec.normal.x; q[6] = rec.normal.y; q[7] = rec.normal.z;
-    q[8] = rec.front_face ? 1. : 0.;
-    q[9] = rec.u; q[10] = rec.v;
-    q[11] = (double)h.node;
+    hit_row(q, h, rec);
+}
+// hit_kernel's kernels 1, 2 and 3 for scenes with nested Transforms (the chain walk, GENERAL == 3)
+__global__ void hit_kernel_nest(FlatView sv, int accel, size_t n, const double* rays, double t_min, double t_max, double* out, int* err) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    Acc A = make_acc(sv.base, sv.base, sv);
+    uint32_t stack_at = 0;
+    if (accel == 3) {  // the NodeW table, expanded as hit_kernel expands it
+        for (uint32_t k = threadIdx.x; k < sv.n_nodes2; k += blockDim.x) {
+            const uint4* nd = (const uint4*)(sv.base + sv.off_n2) + (size_t)k * NODE2_F4;
+            const uint4 a = nd[0], b = nd[1], c = nd[2], d4 = nd[3];
+            const uint32_t c0 = wide_ref(d4.x), c1 = wide_ref(d4.y);
+            char* w = smem + wide_ref(k);
+            const uint4 lo0 = make_uint4(a.x, a.y, a.z, a.w), lo1 = make_uint4(b.x, b.y, c0, c1);
+            const uint4 hi0 = make_uint4(b.z, b.w, c.x, c.y), hi1 = make_uint4(c.z, c.w, c0, c1);
+            ((uint4*)w)[0] = lo0; ((uint4*)w)[1] = lo1;
+            ((uint4*)(w + NODEW_FAR))[0] = hi0; ((uint4*)(w + NODEW_FAR))[1] = hi1;
+            ((uint4*)(w + 2 * NODEW_FAR))[0] = lo0; ((uint4*)(w + 2 * NODEW_FAR))[1] = lo1;
+        }
+        __syncthreads();
+        A.n2w_lds = (uint32_t)(uintptr_t)(AS_L char*)smem;
+        stack_at = nodew_bytes(sv.n_nodes2);
+    }
+    if (i >= n) return;
+    D3 o = mk(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]), d = mk(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
+    uint32_t* stk = (uint32_t*)(smem + stack_at) + threadIdx.x;
+    const Hit h = (accel == 3) ? traverse2<3, false, false, true>(A, stk, (int)blockDim.x, o, d, t_min, t_max)
+                : (accel == 2) ? traverse2<3, false, false>(A, stk, (int)blockDim.x, o, d, t_min, t_max)
+                               : traverse<3>(A, o, d, t_min, t_max);
+    double* q = out + 12 * i;
+    for (int k = 0; k < 12; k++) q[k] = 0.;
+    if (h.node < 0) return;
+    Rec rec = materialize<3, true>(A, h, o, d, err);
+    hit_row(q, h, rec);
 }
 
 // ------------------------------------------------------------ host side ---
@@ -3737,6 +3830,7 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
                                           std::to_string(s.flat.msph_t0_max) + ", " + std::to_string(s.flat.msph_t1_min) + "] for this scene): their boxes are built for that range");
     }
     const bool general = (view.kinds_mask & ~((1u << NK_BOX) | (1u << NK_SPHERE))) != 0 || book2;
+    const bool nest = s.flat.xf_nest != 0u;  // nested Transforms: the GENERAL == 3 variants (common/flat.h "Nested Transforms")
     const size_t lds_max = di.lds_max - (moving ? (size_t)PT_BLOCK * sizeof(double) : 0);
     // The accel kernels need the camera inside the region the f32 boxes were padded for (flatten.cpp: origin_limit2) and
     // t_min >= 0 (box32's proof); otherwise kernel 1 (reference order) renders.
@@ -3815,6 +3909,20 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
         fn = media ? ((kernel == 2) ? (lds ? pt_kernel<true, 2, 2, 0, true> : pt_kernel<false, 2, 2, 0, true>)
                                     : (lds ? pt_kernel<true, 2, 1, 0, true> : pt_kernel<false, 2, 1, 0, true>))
                    : ((kernel == 2) ? (lds ? pt_kernel<true, 2, 2, 0> : pt_kernel<false, 2, 2, 0>) : (lds ? pt_kernel<true, 2, 1, 0> : pt_kernel<false, 2, 1, 0>));
+    if (nest) {  // nested Transforms: the chain walk (GENERAL == 3) of kernels 1 and 2 (kernels 5 / 6 were refused: no compact data)
+        if (kernel == 1)
+            fn = media ? (lds ? pt_kernel<true, 3, 1, 0, true> : pt_kernel<false, 3, 1, 0, true>)
+               : (integ == 1) ? (lds ? pt_kernel<true, 3, 1, 1> : pt_kernel<false, 3, 1, 1>)
+               : (integ == 2) ? (lds ? pt_kernel<true, 3, 1, 2> : pt_kernel<false, 3, 1, 2>)
+                              : (lds ? pt_kernel<true, 3, 1, 0> : pt_kernel<false, 3, 1, 0>);
+        else if (kernel == 2)
+            fn = media ? (lds ? pt_kernel<true, 3, 2, 0, true> : pt_kernel<false, 3, 2, 0, true>)
+               : (integ == 1) ? (lds ? pt_kernel<true, 3, 2, 1> : pt_kernel<false, 3, 2, 1>)
+               : (integ == 2) ? (lds ? pt_kernel<true, 3, 2, 2> : pt_kernel<false, 3, 2, 2>)
+                              : (lds ? pt_kernel<true, 3, 2, 0> : pt_kernel<false, 3, 2, 0>);
+        else
+            throw RtError(RT_ERR_INTERNAL, "nested Transforms reached kernel " + std::to_string(kernel));
+    }
     // scene too large for LDS: spend what is left after the stacks on the shallowest BVH levels (the Node2 array is depth-sorted)
     int n_top = 0, n_topq = 0;
     if (kernel == 2 && !lds && lds_max > stack_bytes) {
@@ -3840,7 +3948,7 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
     const int grid = di.cus * blocks_per_cu;
     // a rank that owns fewer tiles than the launch has waves: single-unit jobs (below) folded out of order (next_unit_pool)
     const bool pool = POOL_MODE && SINGLE_UNITS_BELOW_WAVES && plan.tiles_owned < (int64_t)grid * (PT_BLOCK / 64) &&
-                      ((kernel == 2 && !media && !book2) || (kernel == 5 && fn_coop == fn_coop_early));
+                      ((kernel == 2 && !media && !book2 && !nest) || (kernel == 5 && fn_coop == fn_coop_early));
     if (pool && kernel == 2) {
         fn = pick_pt_kernel_pool(lds, general, integ);  // (same resources as the variant the occupancy was asked for)
         if (smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
@@ -4321,7 +4429,9 @@ void render_sppm(const rt_scene& s, const CameraDev& cam, RenderPlan plan, const
     FlatView view = s.flat.view;
     view.base = device_blob(s, dev);
     double cam_abs = std::fmax(std::fmax(std::fabs(cam.origin[0]), std::fabs(cam.origin[1])), std::fabs(cam.origin[2])) + std::fabs(cam.lens_radius);
-    const bool accel = view.accel_ok && cam_abs <= view.origin_limit2 && std::isfinite(cam_abs) && (size_t)view.stack2 * 256 * 4 <= di.lds_max;
+    bool accel = view.accel_ok && cam_abs <= view.origin_limit2 && std::isfinite(cam_abs) && (size_t)view.stack2 * 256 * 4 <= di.lds_max;
+    const bool nest = s.flat.xf_nest != 0u;  // nested Transforms: the photon / eye passes take kernel 1's chain walk (their accel walks have none)
+    if (nest) accel = false;
     const size_t smem = accel ? (size_t)view.stack2 * 256 * sizeof(uint32_t) : 0;
     // photon pass: stage the accel's hot tables into LDS when at least two 256-thread blocks still fit on a CU
     const size_t hot2 = (size_t)(view.stage2_end - view.stage2_begin);
@@ -4418,6 +4528,8 @@ void render_sppm(const rt_scene& s, const CameraDev& cam, RenderPlan plan, const
         else if (accel)
             hipLaunchKernelGGL((photon_kernel<true, false>), dim3(pblocks), dim3(256), smem, sp.s, view, skp, lk, g.b, c.b, (unsigned int*)d_cursor.p,
                                (int*)d_err_p.p);
+        else if (nest)  // nested Transforms: the chain walk (such scenes have no accel)
+            hipLaunchKernelGGL(photon_kernel_nest, dim3(pblocks), dim3(256), 0, sp.s, view, skp, lk, g.b, c.b, (unsigned int*)d_cursor.p, (int*)d_err_p.p);
         else
             hipLaunchKernelGGL((photon_kernel<false, false>), dim3(pblocks), dim3(256), 0, sp.s, view, skp, lk, g.b, c.b, (unsigned int*)d_cursor.p,
                                (int*)d_err_p.p);
@@ -4462,6 +4574,7 @@ void render_sppm(const rt_scene& s, const CameraDev& cam, RenderPlan plan, const
         sg.sort_into_grid(gg, ng, stream);
         sc.sort_into_grid(gc, nc, stream);
         if (accel) hipLaunchKernelGGL(eye_kernel<true>, dim3(eblocks), dim3(256), smem, stream, view, (const CamK*)d_cam.p, sk, (double*)d_gp.p, (int*)d_err.p);
+        else if (nest) hipLaunchKernelGGL(eye_kernel_nest, dim3(eblocks), dim3(256), 0, stream, view, (const CamK*)d_cam.p, sk, (double*)d_gp.p, (int*)d_err.p);
         else hipLaunchKernelGGL(eye_kernel<false>, dim3(eblocks), dim3(256), 0, stream, view, (const CamK*)d_cam.p, sk, (double*)d_gp.p, (int*)d_err.p);
         const size_t pix_per_block = GATHER_BLOCK / 64;  // one wave per pixel
         hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((npix + pix_per_block - 1) / pix_per_block)), dim3(GATHER_BLOCK), 0, stream, sk,
@@ -4563,6 +4676,14 @@ void debug_hit_device(const rt_scene& s, int kernel, size_t n, const double* ray
         smem += ((size_t)(view.n_nodes2 + NODEW_CHUNK - 1) / NODEW_CHUNK) * 3 * NODEW_FAR;
         if (smem > 160 * 1024) throw RtError(RT_ERR_UNSUPPORTED, "the NodeW table of this scene does not fit in LDS");
         if (smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)hit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    }
+    if (s.flat.xf_nest != 0u) {  // nested Transforms: the chain walk (kernels 5 / 6 were refused above: nested scenes have no compact data)
+        if (smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)hit_kernel_nest, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        hipLaunchKernelGGL(hit_kernel_nest, dim3((unsigned)((n + 63) / 64)), dim3(64), smem, 0, view, kernel, n, (const double*)dr.p, t_min, t_max,
+                           (double*)dout.p, (int*)err.p);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(out, dout.p, n * 96, hipMemcpyDeviceToHost));
+        return;
     }
     hipLaunchKernelGGL(hit_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), smem, 0, view,
                        kernel, n, (const double*)dr.p, t_min, t_max, (double*)dout.p, (int*)err.p);

@@ -37,9 +37,9 @@ struct SppmK {
 };
 static const uint64_t SALT_PHOTON = 0x50484F544F4E5F31ULL, SALT_EYE = 0x5350504D4559455FULL;
 
-template <bool ACCEL>
+template <bool ACCEL, int GENERAL = 1>
 DEV Hit world_hit(const Acc& A, uint32_t* stk, int stride, D3 o, D3 d, double t_min) {
-    return ACCEL ? traverse2<true, false, false>(A, stk, stride, o, d, t_min, INFINITY) : traverse<true>(A, o, d, t_min, INFINITY);  // (no LDS node cache in these kernels)
+    return ACCEL ? traverse2<true, false, false>(A, stk, stride, o, d, t_min, INFINITY) : traverse<GENERAL>(A, o, d, t_min, INFINITY);  // (no LDS node cache in these kernels)
 }
 
 DEV void photon_push(const PhotonBuf& b, D3 p, D3 power, D3 n, int* err) {
@@ -68,9 +68,9 @@ DEV void photon_push(const PhotonBuf& b, D3 p, D3 power, D3 n, int* err) {
 #define RT_PHOTON_CHUNK 256
 #endif
 static const unsigned int PHOTON_CHUNK = RT_PHOTON_CHUNK;
-template <bool ACCEL, bool LDS>
-__global__ void __launch_bounds__(256, 4) photon_kernel(FlatView sv, SppmK sk, LightK lk, PhotonBuf all, PhotonBuf caustic, unsigned int* cursor,
-                                                        int* err) {
+// (the body is shared with photon_kernel_nest: GENERAL == 3 is the chain walk of nested Transforms, kernels.hip)
+template <bool ACCEL, bool LDS, int GENERAL>
+DEV void photon_body(FlatView sv, SppmK sk, LightK lk, PhotonBuf all, PhotonBuf caustic, unsigned int* cursor, int* err) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Acc A;
     uint32_t hot = 0;
@@ -146,9 +146,9 @@ __global__ void __launch_bounds__(256, 4) photon_kernel(FlatView sv, SppmK sk, L
             // ---- one bounce of the photon loop, photon_mapper.rs:243-261 ----
             if (alive) {
                 bool go = false;
-                Hit h = world_hit<ACCEL>(A, stk, stride, o, d, 0.0001);
+                Hit h = world_hit<ACCEL, GENERAL>(A, stk, stride, o, d, 0.0001);
                 if (h.node >= 0) {
-                    Rec rec = materialize<true>(A, h, o, d, err);
+                    Rec rec = materialize<GENERAL>(A, h, o, d, err);
                     // Material::scatter_photon, material.rs:27-45
                     D3 emitted, att, ndir;
                     bool diffuse;
@@ -176,6 +176,15 @@ __global__ void __launch_bounds__(256, 4) photon_kernel(FlatView sv, SppmK sk, L
             }
         }
     }
+}
+template <bool ACCEL, bool LDS>
+__global__ void __launch_bounds__(256, 4) photon_kernel(FlatView sv, SppmK sk, LightK lk, PhotonBuf all, PhotonBuf caustic, unsigned int* cursor,
+                                                        int* err) {
+    photon_body<ACCEL, LDS, 1>(sv, sk, lk, all, caustic, cursor, err);
+}
+__global__ void __launch_bounds__(256, 4) photon_kernel_nest(FlatView sv, SppmK sk, LightK lk, PhotonBuf all, PhotonBuf caustic, unsigned int* cursor,
+                                                             int* err) {
+    photon_body<false, false, 3>(sv, sk, lk, all, caustic, cursor, err);
 }
 
 // ---- uniform grid over a photon set ----
@@ -284,8 +293,9 @@ __global__ void cell_fill_kernel(unsigned int n, const unsigned int* cell_of, co
 }
 
 // update_sppm's eye path, photon_mapper.rs:277-296 ; one pixel per thread.  gp: per pixel {valid, p[3], bsdf[3]}
-template <bool ACCEL>
-__global__ void __launch_bounds__(256) eye_kernel(FlatView sv, const CamK* __restrict__ camp, SppmK sk, double* gp, int* err) {
+// (the body is shared with eye_kernel_nest: GENERAL == 3 is the chain walk of nested Transforms, kernels.hip)
+template <bool ACCEL, int GENERAL>
+DEV void eye_body(FlatView sv, const CamK* __restrict__ camp, SppmK sk, double* gp, int* err) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Acc A = make_acc(sv.base, sv.base, sv);
     uint32_t* stk = (uint32_t*)smem + threadIdx.x;
@@ -306,9 +316,9 @@ __global__ void __launch_bounds__(256) eye_kernel(FlatView sv, const CamK* __res
         double* g = gp + 7 * pix;
         g[0] = 0.;
         for (int bounce = 0; bounce < sk.max_bounces; bounce++) {
-            Hit h = world_hit<ACCEL>(A, stk, stride, o, d, 0.001);
+            Hit h = world_hit<ACCEL, GENERAL>(A, stk, stride, o, d, 0.001);
             if (h.node < 0) break;
-            Rec rec = materialize<true>(A, h, o, d, err);
+            Rec rec = materialize<GENERAL>(A, h, o, d, err);
             D3 emitted, att, ndir;
             bool diffuse;
             bool scattered = shade(A, rec, d, rng, emitted, att, ndir, diffuse, err);
@@ -323,6 +333,13 @@ __global__ void __launch_bounds__(256) eye_kernel(FlatView sv, const CamK* __res
             d = ndir;
         }
     }
+}
+template <bool ACCEL>
+__global__ void __launch_bounds__(256) eye_kernel(FlatView sv, const CamK* __restrict__ camp, SppmK sk, double* gp, int* err) {
+    eye_body<ACCEL, 1>(sv, camp, sk, gp, err);
+}
+__global__ void __launch_bounds__(256) eye_kernel_nest(FlatView sv, const CamK* __restrict__ camp, SppmK sk, double* gp, int* err) {
+    eye_body<false, 3>(sv, camp, sk, gp, err);
 }
 
 struct Fixed3 {

@@ -9,6 +9,8 @@
 // reproduces the reference's result including its tie rule.
 #include <cstring>
 #include <map>
+#include <string>
+#include <utility>
 
 #include <algorithm>
 #include <cmath>
@@ -44,13 +46,22 @@ struct Builder {
         std::vector<AccelItem> items;
         std::map<int, size_t> of;  // object id -> item slot (a re-emitted object keeps one slot, latest order)
         uint32_t xform = 0;
-        const double* Minv = nullptr;
+        const double* Minv = nullptr;  // the chain's innermost level: parent's space <-> this context's object space
         const double* M = nullptr;
+        uint32_t chain = 0;    // nested scenes: the instance record carries the chain instead of the xform
+        size_t parent = 0;     // context of the enclosing chain (0: world space)
+        uint32_t depth = 1;    // levels of the chain
     };
     std::vector<InstCtx> actx{1};
     std::vector<size_t> ctx_stack{0};
-    std::map<int, size_t> ctx_of_xform;  // Transform object id -> its context
+    std::map<uint32_t, size_t> ctx_of_chain;  // chain -> its context (one per chain: a Transform under two parents has two)
     bool accel_ok = true;
+    // chains of Transforms (common/flat.h "Nested Transforms"): one per distinct path from the root, keyed by (parent chain, xform)
+    std::vector<ChainRec> chains;
+    std::map<std::pair<int32_t, uint32_t>, uint32_t> chain_of;
+    int32_t cur_chain = -1;
+    uint32_t xf_nest = 0;  // levels of the deepest chain
+    std::vector<std::pair<uint32_t, uint32_t>> xf_begin, xf_end;  // {node, chain} / {node, parent chain + 1}: the nested payloads
 
     void accel_item(int obj_id, const ObjectRec& o, uint32_t kp, uint32_t node_index, const Box* tight = nullptr) {
         if (medium_depth > 0) return;  // the boundary of a ConstantMedium is not a surface: only the medium's own two queries see it
@@ -172,14 +183,30 @@ struct Builder {
                 break;
             }
             case OBJ_TRANSFORM: {
-                if (xf_depth >= 1) throw RtError(RT_ERR_UNSUPPORTED, "nested Transform (depth > 1) is not supported by the device traversal yet");
                 auto it = xform_of.find(id);
                 if (it == xform_of.end()) {
                     it = xform_of.emplace(id, (uint32_t)(xforms.size() / 32)).first;
                     xforms.insert(xforms.end(), o.Minv, o.Minv + 16);
                     xforms.insert(xforms.end(), o.M, o.M + 16);
                 }
+                // the chain this visit enters: the same Transform under two different parents is two chains (each transforms with its own matrices)
+                const int32_t parent = cur_chain;
+                auto ch = chain_of.find({parent, it->second});
+                if (ch == chain_of.end()) {
+                    ChainRec r{};
+                    if (parent >= 0) r = chains[parent];
+                    if (r.depth >= XF_MAX_DEPTH)
+                        throw RtError(RT_ERR_UNSUPPORTED, "Transforms nested deeper than " + std::to_string(XF_MAX_DEPTH) + " levels are not supported");
+                    r.xf[r.depth++] = it->second;
+                    r.inner = it->second;
+                    if (chains.size() >= (1u << (32 - NK_BITS)) - 1u) throw RtError(RT_ERR_UNSUPPORTED, "scene too large for 28-bit chain ids");
+                    chains.push_back(r);
+                    ch = chain_of.emplace(std::make_pair(parent, it->second), (uint32_t)(chains.size() - 1)).first;
+                    xf_nest = std::max(xf_nest, r.depth);
+                }
                 uint32_t n = node(NK_XFORM_BEGIN, it->second);
+                xf_begin.push_back({n, ch->second});
+                cur_chain = (int32_t)ch->second;
                 // accel: the Transform is one item of the enclosing space; its subtree gets its own object-space BVH
                 // (a Transform emitted twice -- BVHNode::new's 1-object leaf, Q14 -- re-enters its own context, so its
                 // items take the later visit's indices exactly as a re-emitted primitive does)
@@ -187,17 +214,21 @@ struct Builder {
                     xf_depth++;
                     emit(o.children[0]);
                     xf_depth--;
-                    node(NK_XFORM_END, it->second);
+                    cur_chain = parent;
+                    xf_end.push_back({node(NK_XFORM_END, it->second), (uint32_t)(parent + 1)});
                     meta[2 * n + 1] = (uint32_t)(meta.size() / 2);
                     break;
                 }
-                auto ci = ctx_of_xform.find(id);
-                if (ci == ctx_of_xform.end()) {
+                auto ci = ctx_of_chain.find(ch->second);
+                if (ci == ctx_of_chain.end()) {
                     actx.emplace_back();
                     actx.back().xform = it->second;
                     actx.back().Minv = o.Minv;
                     actx.back().M = o.M;
-                    ci = ctx_of_xform.emplace(id, actx.size() - 1).first;
+                    actx.back().chain = ch->second;
+                    actx.back().parent = ctx_stack.back();
+                    actx.back().depth = chains[ch->second].depth;
+                    ci = ctx_of_chain.emplace(ch->second, actx.size() - 1).first;
                 }
                 uint32_t inst_index = (uint32_t)(ci->second - 1);
                 accel_item(id, o, NK_INSTANCE | (inst_index << NK_BITS), n);
@@ -206,7 +237,8 @@ struct Builder {
                 emit(o.children[0]);
                 xf_depth--;
                 ctx_stack.pop_back();
-                node(NK_XFORM_END, it->second);
+                cur_chain = parent;
+                xf_end.push_back({node(NK_XFORM_END, it->second), (uint32_t)(parent + 1)});
                 meta[2 * n + 1] = (uint32_t)(meta.size() / 2);
                 break;
             }
@@ -277,6 +309,12 @@ void flatten(rt_scene& s) {
         b.vnrm.insert(b.vnrm.end(), m->nrm.begin(), m->nrm.end());
     }
     b.emit(s.root);
+    const bool nested = b.xf_nest >= 2;
+    if (nested) {
+        // the chain walk (common/flat.h "Nested Transforms"): BEGIN / END and the accel's instance records carry chain ids
+        for (auto& p : b.xf_begin) b.meta[2 * p.first] = NK_XFORM_BEGIN | (p.second << NK_BITS);
+        for (auto& p : b.xf_end) b.meta[2 * p.first] = NK_XFORM_END | (p.second << NK_BITS);
+    }
 
     // World::new's lights -> {kind, payload} pairs addressing the sphere / rect tables
     std::vector<uint32_t> lights;
@@ -341,11 +379,17 @@ void flatten(rt_scene& s) {
     std::vector<char> compact_cand;  // per instance: only triangles with f32 vertices (kernels 5 / 6 can defer it)
     std::vector<double> inst_oo;  // per instance: bound of |object-space ray origin|
     double origin_limit = 0.;
+    // contexts by chain depth, outermost first (a nested instance's item lives in its parent's context; scenes of depth <= 1: 1, 2, 3 ...)
+    std::vector<size_t> by_depth;
+    for (size_t i = 1; i < b.actx.size(); i++) by_depth.push_back(i);
+    std::stable_sort(by_depth.begin(), by_depth.end(), [&](size_t x, size_t y) { return b.actx[x].depth < b.actx[y].depth; });
     // An instance's item in the enclosing space carries the Transform's own bounding box (the box of the 8 transformed corners
     // of the child's box, transform.rs:104-150): loose for a rotated mesh.  For culling, the union of the transformed boxes of the
     // instance's ITEMS is as valid (affine images of the items lie inside it; the f64 rounding of M * corner is orders of
     // magnitude below the pad added at build time) and tighter: fewer rays enter the object-space BVH for nothing.
-    for (size_t i = 1; b.accel_ok && i < b.actx.size(); i++) {
+    // (innermost chains first: an instance's own item box, in its parent's context, is tightened before the parent's items are unioned)
+    for (size_t k = by_depth.size(); b.accel_ok && k-- > 0;) {
+        const size_t i = by_depth[k];
         const auto& c = b.actx[i];
         if (c.items.empty() || !c.M) continue;
         Box tb;
@@ -399,12 +443,15 @@ void flatten(rt_scene& s) {
             auto is_f32v = [](double x) { return (double)(float)x == x; };
             compact_cand.assign(b.actx.size() - 1, 1);
             inst_oo.assign(b.actx.size() - 1, 0.);
-            for (size_t i = 1; ab.ok && i < b.actx.size(); i++) {
+            for (size_t i : by_depth) {
+                if (!ab.ok) break;
                 auto& c = b.actx[i];
-                // object-space origin bound: |M^-1 o| <= sum_b |Minv[a][b]| * |o|max + |Minv[a][3]|
+                // object-space origin bound: |M^-1 o| <= sum_b |Minv[a][b]| * |o|max + |Minv[a][3]|, composed along the chain (the
+                // parent's bound is its own object-space one; by_depth computes it first)
+                const double o_parent = c.parent == 0 ? origin_limit : inst_oo[c.parent - 1];
                 double oo = 0.;
                 for (int a = 0; a < 3; a++)
-                    oo = std::fmax(oo, (std::fabs(c.Minv[4 * a]) + std::fabs(c.Minv[4 * a + 1]) + std::fabs(c.Minv[4 * a + 2])) * origin_limit +
+                    oo = std::fmax(oo, (std::fabs(c.Minv[4 * a]) + std::fabs(c.Minv[4 * a + 1]) + std::fabs(c.Minv[4 * a + 2])) * o_parent +
                                            std::fabs(c.Minv[4 * a + 3]));
                 for (auto& it : c.items)  // hit points inside the instance also serve as origins of secondary rays (in world space only)
                     for (int a = 0; a < 3; a++) oo = std::fmax(oo, std::fmax(std::fabs(it.box.mn[a]), std::fabs(it.box.mx[a])));
@@ -425,20 +472,25 @@ void flatten(rt_scene& s) {
                 }
             }
             // (the world BVH was built above with the items' kinds as they were: its leaf items are patched below, after the build)
+            // stack depth at which each context's BVH starts: below its parent's deepest level and one REF_RESTORE entry per level
+            std::vector<int> end_depth(b.actx.size(), depth_tlas);
             for (int pass = 0; pass < 2; pass++) {
-                for (size_t i = 1; ab.ok && i < b.actx.size(); i++) {
+                for (size_t i : by_depth) {  // (a parent holds an instance item: never deferrable, so pass 0 builds it before its children)
+                    if (!ab.ok) break;
                     if ((compact_cand[i - 1] != 0) != (pass == 1)) continue;  // pass 0: inline instances, pass 1: deferrable ones
                     auto& c = b.actx[i];
                     const size_t nodes_before = ab.nodes.size();
                     const int depth_before = ab.max_depth;
-                    ab.max_depth = depth_tlas + 1;
-                    uint32_t r = accel_build_bvh(ab, c.items, 3. * std::ldexp(inst_oo[i - 1], -22), depth_tlas + 1);
+                    const int start = end_depth[c.parent] + 1;
+                    ab.max_depth = start;
+                    uint32_t r = accel_build_bvh(ab, c.items, 3. * std::ldexp(inst_oo[i - 1], -22), start);
+                    end_depth[i] = ab.max_depth;
                     if (pass == 1) {
                         max_inst_nodes = std::max<uint32_t>(max_inst_nodes, (uint32_t)(ab.nodes.size() - nodes_before));
                         inst_depth = std::max<uint32_t>(inst_depth, (uint32_t)std::max(1, ab.max_depth - depth_tlas + 1));
                     }
                     ab.max_depth = std::max(ab.max_depth, depth_before);
-                    ab.inst[2 * (i - 1)] = c.xform;
+                    ab.inst[2 * (i - 1)] = nested ? c.chain : c.xform;
                     ab.inst[2 * (i - 1) + 1] = r;
                 }
                 if (pass == 0) {
@@ -514,7 +566,7 @@ void flatten(rt_scene& s) {
     std::vector<NodeQ> n2q;
     std::vector<Tri32> tri32;
     std::vector<QGrid> qgrid;
-    bool coop_data = ab.ok && !ab.inst.empty();
+    bool coop_data = ab.ok && !ab.inst.empty() && !nested;  // kernels 5 / 6 have no chain walk: nested scenes never reach them
     {
         bool any = false;
         for (char c : compact_cand) any = any || c != 0;
@@ -716,6 +768,14 @@ void flatten(rt_scene& s) {
         std::vector<uint32_t> tv = {v.off_meta, v.off_boxes, v.off_spheres, v.off_rects, v.off_tripre, v.off_xforms, 0u, (uint32_t)(b.meta.size() / 2)};
         f.blob.resize((f.blob.size() + 15) & ~size_t(15));
         tv[6] = (uint32_t)f.blob.size();
+        // The chain records follow the tie view's eight words (scenes of depth <= 1 have none: their blob is unchanged).  The kernels
+        // reach them as tie_view + 8 (chain_rec, kernels.hip): the tie view is always written and always read from global memory, so
+        // it doubles as the chain table's locator -- a change to its size must move chain_rec's offset with it.
+        if (nested)
+            for (const ChainRec& r : b.chains) {
+                const uint32_t* w = (const uint32_t*)&r;
+                tv.insert(tv.end(), w, w + CHAIN_WORDS);
+            }
         v.off_tie_view = append(f.blob, tv);
     }
     v.off_lights = append(f.blob, lights);
@@ -729,6 +789,7 @@ void flatten(rt_scene& s) {
     v.kinds_mask = b.kinds;
     v.base = nullptr;
     f.view = v;
+    f.xf_nest = nested ? b.xf_nest : 0u;
 
     rt_scene_info& in = f.info;
     in.n_nodes = (int32_t)v.n_nodes;

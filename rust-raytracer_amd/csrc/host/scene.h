@@ -69,6 +69,8 @@ struct FlatScene {
     // D9: the time range every moving sphere of the scene is defined on = [latest time0, earliest time1] (their boxes are the unions of the
     // boxes at those two times, scene.cpp: a ray time outside it would move a centre out of its committed box); render_tiles checks the shutter
     double msph_t0_max = -1e300, msph_t1_min = 1e300;
+    // levels of the deepest chain of Transforms when the scene nests them (>= 2; 0 otherwise): the kernels' chain walk (GENERAL == 3, common/flat.h)
+    uint32_t xf_nest = 0;
 };
 
 struct DeviceCopy {

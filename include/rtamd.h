@@ -203,8 +203,10 @@ int rt_object_cube(rt_scene* s, const double box_min[3], const double box_max[3]
 int rt_object_sphere_light(rt_scene* s, const double center[3], double radius, const double flux[3], double scale);
 int rt_object_xz_rect_light(rt_scene* s, double x0, double z0, double x1, double z1, double y, const double flux[3], double scale);
 /* objects/medium.rs:16 ConstantMedium::new(d, boundary, phase_function): constant-density participating medium inside
- * `boundary` (any Hitable with a box, not itself a medium).  Its hit() draws a random number (medium.rs:37-38), so scenes with a
- * medium are rendered by the reference-order kernel only (kernel 2 and the SPPM pre-pass refuse them); the logarithm is the
+ * `boundary` (any Hitable with a box, not itself a medium).  Its hit() draws a random number (medium.rs:37-38) from the path's
+ * stream, in the reference's visit order: kernels 1 and 2 render such scenes with integrator 0, and rt_render_sppm* with all three
+ * passes (a volume event is a pass-through interaction: no photon, no gather point); integrator 1, kernels 5 / 6, a medium inside a
+ * medium's boundary and, under SPPM, a light inside a medium's boundary are refused with RT_ERR_UNSUPPORTED.  The logarithm is the
  * deterministic rtamd-ln-1 (csrc/common/detlog.h, < 1 ulp from libm). */
 int rt_object_constant_medium(rt_scene* s, double density, int boundary, int phase_material);
 /* objects/mesh.rs:149 Mesh::load_obj given parsed arrays: positions/normals n_vert*3, indices n_tri*3.

@@ -3890,7 +3890,7 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
     if (integ == 2 && !plan.sppm_est) throw RtError(RT_ERR_ARG, "integrator 2 (SPPM) is reached through rt_render_sppm");
     if (integ != 0 && book2)
         throw RtError(RT_ERR_UNSUPPORTED, "the book-2 extensions (moving spheres, noise textures, an open shutter) render with integrator 0 (kernels 1 and 2)");
-    if (media && integ != 0)
+    if (media && integ == 1)
         throw RtError(RT_ERR_UNSUPPORTED, "scenes with a ConstantMedium render with integrator 0 only (the medium's random draw is part of the "
                                           "reference-order walk; light sampling and SPPM have no volume events)");
     pt_fn fn = (kernel == 1) ? pick_pt_kernel<1>(lds, general, integ) : pick_pt_kernel<2>(lds, general, integ);
@@ -3902,21 +3902,25 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
         if (tie_scene(view)) pick_coop<true>(integ, mixed, wide, fn_coop, fn_coop_early);
         else pick_coop<false>(integ, mixed, wide, fn_coop, fn_coop_early);
     }
-    if (media)
-        fn = (kernel == 2) ? (lds ? pt_kernel<true, true, 2, 0, true> : pt_kernel<false, true, 2, 0, true>)
-                           : (lds ? pt_kernel<true, true, 1, 0, true> : pt_kernel<false, true, 1, 0, true>);
+    if (media)  // (integrator 2: the SPPM final pass, rt_render_sppm; volume events are passed through to the first Diffuse hit)
+        fn = (integ == 2) ? ((kernel == 2) ? (lds ? pt_kernel<true, true, 2, 2, true> : pt_kernel<false, true, 2, 2, true>)
+                                           : (lds ? pt_kernel<true, true, 1, 2, true> : pt_kernel<false, true, 1, 2, true>))
+                          : ((kernel == 2) ? (lds ? pt_kernel<true, true, 2, 0, true> : pt_kernel<false, true, 2, 0, true>)
+                                           : (lds ? pt_kernel<true, true, 1, 0, true> : pt_kernel<false, true, 1, 0, true>));
     if (book2)  // GENERAL == 2
         fn = media ? ((kernel == 2) ? (lds ? pt_kernel<true, 2, 2, 0, true> : pt_kernel<false, 2, 2, 0, true>)
                                     : (lds ? pt_kernel<true, 2, 1, 0, true> : pt_kernel<false, 2, 1, 0, true>))
                    : ((kernel == 2) ? (lds ? pt_kernel<true, 2, 2, 0> : pt_kernel<false, 2, 2, 0>) : (lds ? pt_kernel<true, 2, 1, 0> : pt_kernel<false, 2, 1, 0>));
     if (nest) {  // nested Transforms: the chain walk (GENERAL == 3) of kernels 1 and 2 (kernels 5 / 6 were refused: no compact data)
         if (kernel == 1)
-            fn = media ? (lds ? pt_kernel<true, 3, 1, 0, true> : pt_kernel<false, 3, 1, 0, true>)
+            fn = media ? ((integ == 2) ? (lds ? pt_kernel<true, 3, 1, 2, true> : pt_kernel<false, 3, 1, 2, true>)
+                                       : (lds ? pt_kernel<true, 3, 1, 0, true> : pt_kernel<false, 3, 1, 0, true>))
                : (integ == 1) ? (lds ? pt_kernel<true, 3, 1, 1> : pt_kernel<false, 3, 1, 1>)
                : (integ == 2) ? (lds ? pt_kernel<true, 3, 1, 2> : pt_kernel<false, 3, 1, 2>)
                               : (lds ? pt_kernel<true, 3, 1, 0> : pt_kernel<false, 3, 1, 0>);
         else if (kernel == 2)
-            fn = media ? (lds ? pt_kernel<true, 3, 2, 0, true> : pt_kernel<false, 3, 2, 0, true>)
+            fn = media ? ((integ == 2) ? (lds ? pt_kernel<true, 3, 2, 2, true> : pt_kernel<false, 3, 2, 2, true>)
+                                       : (lds ? pt_kernel<true, 3, 2, 0, true> : pt_kernel<false, 3, 2, 0, true>))
                : (integ == 1) ? (lds ? pt_kernel<true, 3, 2, 1> : pt_kernel<false, 3, 2, 1>)
                : (integ == 2) ? (lds ? pt_kernel<true, 3, 2, 2> : pt_kernel<false, 3, 2, 2>)
                               : (lds ? pt_kernel<true, 3, 2, 0> : pt_kernel<false, 3, 2, 0>);
@@ -4416,10 +4420,12 @@ void render_sppm(const rt_scene& s, const CameraDev& cam, RenderPlan plan, const
     if (!s.committed) throw RtError(RT_ERR_NOT_COMMITTED, "scene not committed");
     const Tuning tun = tuning();  // one snapshot per call
     if (s.lights.empty()) throw RtError(RT_ERR_ARG, "SPPM needs lights (rt_scene_set_lights)");
-    if (s.flat.view.kinds_mask & (1u << NK_MEDIUM_BEGIN))
-        throw RtError(RT_ERR_UNSUPPORTED, "the SPPM pre-pass does not support ConstantMedium (volume events have no photon-map estimate)");
     if (s.flat.view.n_msph != 0u || s.flat.view.has_noise != 0u || plan.time1 > plan.time0)
         throw RtError(RT_ERR_UNSUPPORTED, "the photon passes have no notion of time: the book-2 extensions (moving spheres, noise textures, an open shutter) render with integrator 0");
+    // ConstantMedium (D8): a volume event is a pass-through interaction in all three passes; the photon and eye walks take their path's stream
+    const bool media = (s.flat.view.kinds_mask & (1u << NK_MEDIUM_BEGIN)) != 0;
+    if (media && s.flat.light_in_medium)
+        throw RtError(RT_ERR_UNSUPPORTED, "a light that lies inside the boundary of a ConstantMedium is not supported by the photon pass");
     if (cfg.iterations < 1 || cfg.photons_per_iter < 1 || cfg.k_global < 1 || cfg.k_caustic < 1 || cfg.max_bounces < 1 || !(cfg.alpha > 0.))
         throw RtError(RT_ERR_ARG, "bad rt_sppm_config");
     hipStream_t stream = (hipStream_t)stream_;
@@ -4432,13 +4438,16 @@ void render_sppm(const rt_scene& s, const CameraDev& cam, RenderPlan plan, const
     bool accel = view.accel_ok && cam_abs <= view.origin_limit2 && std::isfinite(cam_abs) && (size_t)view.stack2 * 256 * 4 <= di.lds_max;
     const bool nest = s.flat.xf_nest != 0u;  // nested Transforms: the photon / eye passes take kernel 1's chain walk (their accel walks have none)
     if (nest) accel = false;
+    // per-lane accel stacks: stack2 entries, as render_tiles gives kernel 2 and its MEDIA variants (traverse2_media's walks take the
+    // column one after another; a boundary's reference-order walk uses none)
     const size_t smem = accel ? (size_t)view.stack2 * 256 * sizeof(uint32_t) : 0;
     // photon pass: stage the accel's hot tables into LDS when at least two 256-thread blocks still fit on a CU
     const size_t hot2 = (size_t)(view.stage2_end - view.stage2_begin);
     const size_t smem_photon = hot2 + smem;
     const bool photon_lds = accel && hot2 > 0 && 2 * smem_photon <= di.lds_max && !tun.no_lds;
     if (photon_lds && smem_photon > 48 * 1024)
-        HIP_CHECK(hipFuncSetAttribute((const void*)photon_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_photon));
+        HIP_CHECK(hipFuncSetAttribute(media ? (const void*)photon_kernel_media<true, true> : (const void*)photon_kernel<true, true>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_photon));
 
     // AllLights::new (light.rs:202-217) + the fixed-point shift of the flux accumulators
     const int nl = (int)s.lights.size();
@@ -4522,7 +4531,20 @@ void render_sppm(const rt_scene& s, const CameraDev& cam, RenderPlan plan, const
         HIP_CHECK(hipMemsetAsync(g.count.p, 0, 4, sp.s));
         HIP_CHECK(hipMemsetAsync(c.count.p, 0, 4, sp.s));
         HIP_CHECK(hipMemsetAsync(d_cursor.p, 0, 4, sp.s));
-        if (accel && photon_lds)
+        if (media) {  // the same four choices, MEDIA variants
+            if (accel && photon_lds)
+                hipLaunchKernelGGL((photon_kernel_media<true, true>), dim3(pblocks), dim3(256), smem_photon, sp.s, view, skp, lk, g.b, c.b,
+                                   (unsigned int*)d_cursor.p, (int*)d_err_p.p);
+            else if (accel)
+                hipLaunchKernelGGL((photon_kernel_media<true, false>), dim3(pblocks), dim3(256), smem, sp.s, view, skp, lk, g.b, c.b,
+                                   (unsigned int*)d_cursor.p, (int*)d_err_p.p);
+            else if (nest)
+                hipLaunchKernelGGL(photon_kernel_nest_media, dim3(pblocks), dim3(256), 0, sp.s, view, skp, lk, g.b, c.b, (unsigned int*)d_cursor.p,
+                                   (int*)d_err_p.p);
+            else
+                hipLaunchKernelGGL((photon_kernel_media<false, false>), dim3(pblocks), dim3(256), 0, sp.s, view, skp, lk, g.b, c.b,
+                                   (unsigned int*)d_cursor.p, (int*)d_err_p.p);
+        } else if (accel && photon_lds)
             hipLaunchKernelGGL((photon_kernel<true, true>), dim3(pblocks), dim3(256), smem_photon, sp.s, view, skp, lk, g.b, c.b, (unsigned int*)d_cursor.p,
                                (int*)d_err_p.p);
         else if (accel)
@@ -4573,7 +4595,11 @@ void render_sppm(const rt_scene& s, const CameraDev& cam, RenderPlan plan, const
         build_grid(gc, sc.b, nc, stream);
         sg.sort_into_grid(gg, ng, stream);
         sc.sort_into_grid(gc, nc, stream);
-        if (accel) hipLaunchKernelGGL(eye_kernel<true>, dim3(eblocks), dim3(256), smem, stream, view, (const CamK*)d_cam.p, sk, (double*)d_gp.p, (int*)d_err.p);
+        if (media) {
+            if (accel) hipLaunchKernelGGL(eye_kernel_media<true>, dim3(eblocks), dim3(256), smem, stream, view, (const CamK*)d_cam.p, sk, (double*)d_gp.p, (int*)d_err.p);
+            else if (nest) hipLaunchKernelGGL(eye_kernel_nest_media, dim3(eblocks), dim3(256), 0, stream, view, (const CamK*)d_cam.p, sk, (double*)d_gp.p, (int*)d_err.p);
+            else hipLaunchKernelGGL(eye_kernel_media<false>, dim3(eblocks), dim3(256), 0, stream, view, (const CamK*)d_cam.p, sk, (double*)d_gp.p, (int*)d_err.p);
+        } else if (accel) hipLaunchKernelGGL(eye_kernel<true>, dim3(eblocks), dim3(256), smem, stream, view, (const CamK*)d_cam.p, sk, (double*)d_gp.p, (int*)d_err.p);
         else if (nest) hipLaunchKernelGGL(eye_kernel_nest, dim3(eblocks), dim3(256), 0, stream, view, (const CamK*)d_cam.p, sk, (double*)d_gp.p, (int*)d_err.p);
         else hipLaunchKernelGGL(eye_kernel<false>, dim3(eblocks), dim3(256), 0, stream, view, (const CamK*)d_cam.p, sk, (double*)d_gp.p, (int*)d_err.p);
         const size_t pix_per_block = GATHER_BLOCK / 64;  // one wave per pixel

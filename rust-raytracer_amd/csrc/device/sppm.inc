@@ -37,9 +37,14 @@ struct SppmK {
 };
 static const uint64_t SALT_PHOTON = 0x50484F544F4E5F31ULL, SALT_EYE = 0x5350504D4559455FULL;
 
-template <bool ACCEL, int GENERAL = 1>
-DEV Hit world_hit(const Acc& A, uint32_t* stk, int stride, D3 o, D3 d, double t_min) {
-    return ACCEL ? traverse2<true, false, false>(A, stk, stride, o, d, t_min, INFINITY) : traverse<GENERAL>(A, o, d, t_min, INFINITY);  // (no LDS node cache in these kernels)
+// MEDIA: the scene holds ConstantMedium objects, whose hit() draws from the path's stream (`rng`): the accel's media walk, or the
+// reference-order walk with its media brackets.  Without MEDIA the stream is not touched.
+template <bool ACCEL, int GENERAL = 1, bool MEDIA = false>
+DEV Hit world_hit(const Acc& A, uint32_t n_media, uint32_t* stk, int stride, D3 o, D3 d, double t_min, Rng& rng) {
+    if constexpr (MEDIA)
+        return ACCEL ? traverse2_media<GENERAL, false, false>(A, n_media, stk, stride, o, d, t_min, rng) : traverse<GENERAL, true>(A, o, d, t_min, INFINITY, &rng);
+    else
+        return ACCEL ? traverse2<true, false, false>(A, stk, stride, o, d, t_min, INFINITY) : traverse<GENERAL>(A, o, d, t_min, INFINITY);  // (no LDS node cache in these kernels)
 }
 
 DEV void photon_push(const PhotonBuf& b, D3 p, D3 power, D3 n, int* err) {
@@ -69,7 +74,9 @@ DEV void photon_push(const PhotonBuf& b, D3 p, D3 power, D3 n, int* err) {
 #endif
 static const unsigned int PHOTON_CHUNK = RT_PHOTON_CHUNK;
 // (the body is shared with photon_kernel_nest: GENERAL == 3 is the chain walk of nested Transforms, kernels.hip)
-template <bool ACCEL, bool LDS, int GENERAL>
+// MEDIA: a volume event is a pass-through (Specular) interaction (D8): it stores no photon, marks the path has_specular, and the photon
+// goes on from the scatter point.  The photon's one stream draws in trace_photons' order: emit, walk (a medium's free flight), scatter, roulette.
+template <bool ACCEL, bool LDS, int GENERAL, bool MEDIA = false>
 DEV void photon_body(FlatView sv, SppmK sk, LightK lk, PhotonBuf all, PhotonBuf caustic, unsigned int* cursor, int* err) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Acc A;
@@ -81,6 +88,10 @@ DEV void photon_body(FlatView sv, SppmK sk, LightK lk, PhotonBuf all, PhotonBuf 
         for (uint32_t i = threadIdx.x; i < hot / 16; i += blockDim.x) dst[i] = src[i];
         __syncthreads();
         A = make_acc(smem - sv.stage2_begin, sv.base, sv);
+        if (MEDIA) {  // the media's boundary subtrees are walked in the reference-order program, which is not staged (as in pt_kernel)
+            A.meta = (const uint2*)(sv.base + sv.off_meta);
+            A.boxes = (const double2*)(sv.base + sv.off_boxes);
+        }
     } else {
         A = make_acc(sv.base, sv.base, sv);
     }
@@ -146,7 +157,7 @@ DEV void photon_body(FlatView sv, SppmK sk, LightK lk, PhotonBuf all, PhotonBuf 
             // ---- one bounce of the photon loop, photon_mapper.rs:243-261 ----
             if (alive) {
                 bool go = false;
-                Hit h = world_hit<ACCEL, GENERAL>(A, stk, stride, o, d, 0.0001);
+                Hit h = world_hit<ACCEL, GENERAL, MEDIA>(A, sv.n_media, stk, stride, o, d, 0.0001, rng);
                 if (h.node >= 0) {
                     Rec rec = materialize<GENERAL>(A, h, o, d, err);
                     // Material::scatter_photon, material.rs:27-45
@@ -185,6 +196,16 @@ __global__ void __launch_bounds__(256, 4) photon_kernel(FlatView sv, SppmK sk, L
 __global__ void __launch_bounds__(256, 4) photon_kernel_nest(FlatView sv, SppmK sk, LightK lk, PhotonBuf all, PhotonBuf caustic, unsigned int* cursor,
                                                              int* err) {
     photon_body<false, false, 3>(sv, sk, lk, all, caustic, cursor, err);
+}
+// scenes with a ConstantMedium (kinds_mask has NK_MEDIUM_BEGIN): kernels of their own, so that nothing of the media walks is compiled into the above
+template <bool ACCEL, bool LDS>
+__global__ void __launch_bounds__(256, 4) photon_kernel_media(FlatView sv, SppmK sk, LightK lk, PhotonBuf all, PhotonBuf caustic, unsigned int* cursor,
+                                                              int* err) {
+    photon_body<ACCEL, LDS, 1, true>(sv, sk, lk, all, caustic, cursor, err);
+}
+__global__ void __launch_bounds__(256, 4) photon_kernel_nest_media(FlatView sv, SppmK sk, LightK lk, PhotonBuf all, PhotonBuf caustic, unsigned int* cursor,
+                                                                   int* err) {
+    photon_body<false, false, 3, true>(sv, sk, lk, all, caustic, cursor, err);
 }
 
 // ---- uniform grid over a photon set ----
@@ -294,7 +315,9 @@ __global__ void cell_fill_kernel(unsigned int n, const unsigned int* cell_of, co
 
 // update_sppm's eye path, photon_mapper.rs:277-296 ; one pixel per thread.  gp: per pixel {valid, p[3], bsdf[3]}
 // (the body is shared with eye_kernel_nest: GENERAL == 3 is the chain walk of nested Transforms, kernels.hip)
-template <bool ACCEL, int GENERAL>
+// MEDIA: the eye stream goes on after the camera's draws into the walks (a medium's free flight) and the scatters; volume events are
+// passed through to the first Diffuse hit.
+template <bool ACCEL, int GENERAL, bool MEDIA = false>
 DEV void eye_body(FlatView sv, const CamK* __restrict__ camp, SppmK sk, double* gp, int* err) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Acc A = make_acc(sv.base, sv.base, sv);
@@ -316,7 +339,7 @@ DEV void eye_body(FlatView sv, const CamK* __restrict__ camp, SppmK sk, double* 
         double* g = gp + 7 * pix;
         g[0] = 0.;
         for (int bounce = 0; bounce < sk.max_bounces; bounce++) {
-            Hit h = world_hit<ACCEL, GENERAL>(A, stk, stride, o, d, 0.001);
+            Hit h = world_hit<ACCEL, GENERAL, MEDIA>(A, sv.n_media, stk, stride, o, d, 0.001, rng);
             if (h.node < 0) break;
             Rec rec = materialize<GENERAL>(A, h, o, d, err);
             D3 emitted, att, ndir;
@@ -340,6 +363,13 @@ __global__ void __launch_bounds__(256) eye_kernel(FlatView sv, const CamK* __res
 }
 __global__ void __launch_bounds__(256) eye_kernel_nest(FlatView sv, const CamK* __restrict__ camp, SppmK sk, double* gp, int* err) {
     eye_body<false, 3>(sv, camp, sk, gp, err);
+}
+template <bool ACCEL>
+__global__ void __launch_bounds__(256) eye_kernel_media(FlatView sv, const CamK* __restrict__ camp, SppmK sk, double* gp, int* err) {
+    eye_body<ACCEL, 1, true>(sv, camp, sk, gp, err);
+}
+__global__ void __launch_bounds__(256) eye_kernel_nest_media(FlatView sv, const CamK* __restrict__ camp, SppmK sk, double* gp, int* err) {
+    eye_body<false, 3, true>(sv, camp, sk, gp, err);
 }
 
 struct Fixed3 {

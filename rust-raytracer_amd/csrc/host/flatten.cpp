@@ -41,6 +41,7 @@ struct Builder {
     uint32_t kinds = 0;
     int xf_depth = 0, depth = 0, max_depth = 0;
     std::map<int, bool> in_xform;  // object id -> emitted inside a Transform
+    std::map<int, bool> in_medium;  // object id -> emitted inside the boundary of a ConstantMedium
     // accel (kernel 2) item collection: context 0 = world space, context 1+i = object space of instance i
     struct InstCtx {
         std::vector<AccelItem> items;
@@ -92,6 +93,7 @@ struct Builder {
     void emit(int id) {
         const ObjectRec& o = s.objects[id];
         if (xf_depth > 0) in_xform[id] = true;
+        if (medium_depth > 0) in_medium[id] = true;
         depth++;
         if (depth > max_depth) max_depth = depth;
         switch (o.type) {
@@ -790,6 +792,8 @@ void flatten(rt_scene& s) {
     v.base = nullptr;
     f.view = v;
     f.xf_nest = nested ? b.xf_nest : 0u;
+    f.light_in_medium = false;
+    for (int lid : s.lights) f.light_in_medium = f.light_in_medium || b.in_medium.count(lid) != 0;
 
     rt_scene_info& in = f.info;
     in.n_nodes = (int32_t)v.n_nodes;

@@ -71,6 +71,8 @@ struct FlatScene {
     double msph_t0_max = -1e300, msph_t1_min = 1e300;
     // levels of the deepest chain of Transforms when the scene nests them (>= 2; 0 otherwise): the kernels' chain walk (GENERAL == 3, common/flat.h)
     uint32_t xf_nest = 0;
+    // a light of rt_scene_set_lights is (part of) the boundary of a ConstantMedium: the SPPM photon pass refuses such scenes
+    bool light_in_medium = false;
 };
 
 struct DeviceCopy {

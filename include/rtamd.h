@@ -389,6 +389,47 @@ int rt_render_sppm_multi(const rt_scene* s, const rt_camera* cam, const rt_param
 /* ncclGetVersion of the RCCL the library is linked with (e.g. 22606), 0 if it cannot be asked */
 int rt_rccl_version(void);
 
+/* ---- guide buffers and denoising (no reference counterpart) ---------------------------------------------------------- */
+/* First-hit guide buffers: for every pixel and sample s in [0, aov_spp) the camera ray rt_render draws -- stream (p->seed, pixel, s),
+ * the same jitter and lens draws -- and its first hit World::hit(ray, p->t_min, +inf).  Averaged over the rays that hit, summed in
+ * sample order in f64: out_aov[height][width][8] (HOST) = {normal[3] (the hit record's front-facing normal), t, albedo[3], coverage}.
+ * The albedo is the material's texture value at (u, v, p): Lambertian / Metal albedo, Dielectric's texture, DiffuseLight's emit;
+ * coverage = hits / aov_spp; a pixel without a hit is all zeros.  p->kernel 0 / 1 / 2 picks the walk as rt_render does (0: kernel 2's
+ * when the scene has a usable accel); p->spp, max_depth, integrator and the shutter are not used.  Whole frames only: p->world > 1 or
+ * p->rank != 0 is RT_ERR_ARG.  Scenes with a ConstantMedium (the first hit needs the path's stream) or moving spheres (no ray time) are
+ * RT_ERR_UNSUPPORTED.  stats: seconds, kernel_ms, samples (= rays), kernel_used. */
+int rt_render_aov(const rt_scene* s, const rt_camera* cam, const rt_params* p, int32_t aov_spp, double* out_aov, rt_stats* stats);
+
+/* Edge-aware a-trous wavelet filter: `iterations` passes of the 5x5 B3 kernel H = {3/8, 1/4, 1/16} at step 2^i, f64, one thread per
+ * pixel.  For tap q = p + step (dx, dy) (dy, then dx, from -2 to 2; taps outside the image skipped), h = H[|dx|] H[|dy|], w = h at q == p
+ * and otherwise w = h * wn * wz * wa * wl, left to right, a factor 1 when its guide is absent:
+ *   wn = fmax(0, (nx nx' + ny ny') + nz nz') squared normal_power_log2 times        (guide: aov normal, guides bit 0)
+ *   wz = 1 / (1 + |z_p - z_q| / (sigma_depth * step))                                (guide: aov t, guides bit 1)
+ *   wa = 1 / (1 + ((|dr| + |dg|) + |db|) / sigma_albedo)                              (guide: aov albedo, guides bit 2)
+ *   wl = 1 / (1 + |l_p - l_q| / (sigma_luma * sqrt(v_p) + eps)), l = (0.2126 r + 0.7152 g) + 0.0722 b   (guide: variance)
+ * W += w, C += w c_q, V += (w w) v_q; c'_p = C / W, v'_p = V / (W W).  Only + - * / sqrt fmax: the result is restated bit for bit by
+ * tests/denoise_ref.py.  Every value of a bad config is RT_ERR_ARG. */
+typedef struct rt_denoise_config {
+    int32_t iterations;         /* passes, 1..8; default 5 */
+    int32_t normal_power_log2;  /* wn = max(0, n.n')^(2^k), 0..16; default 7 */
+    double sigma_depth;         /* > 0; default 1 (scene units per pixel of step) */
+    double sigma_albedo;        /* > 0; default 0.1 */
+    double sigma_luma;          /* > 0; default 4 (standard deviations of the pixel's mean luminance) */
+    double eps;                 /* > 0; default 1e-10 */
+    int32_t guides;             /* which aov guides weigh the taps: bit 0 normal, 1 depth, 2 albedo; default 7 (all); unused without aov */
+    int32_t reserved[5];        /* must be 0 */
+} rt_denoise_config;
+void rt_default_denoise_config(rt_denoise_config* c);
+/* rgb[height][width][3]; variance[height][width] (NULL: wl = 1): the variance of each pixel's mean luminance; aov[height][width][8] as
+ * rt_render_aov writes it (NULL: no guides); out_rgb[height][width][3]; out_variance[height][width] (NULL: not returned; needs
+ * variance).  HOST memory; outputs must not be inputs. */
+int rt_denoise(const rt_denoise_config* cfg, int32_t width, int32_t height, const double* rgb, const double* variance, const double* aov,
+               double* out_rgb, double* out_variance);
+/* the same on DEVICE memory of the current device, queued on `hip_stream` (hipStream_t as void*, NULL = default stream); returns after
+ * the work has completed on that stream */
+int rt_denoise_device(const rt_denoise_config* cfg, int32_t width, int32_t height, const double* d_rgb, const double* d_variance,
+                      const double* d_aov, double* d_out_rgb, double* d_out_variance, void* hip_stream);
+
 /* From<Vec3> for Rgb<u8> (vec3.rs:223-231): floor(clamp(sqrt(c),0,1)*255), NaN -> 0.  Host buffers. */
 int rt_tonemap_u8(const double* rgb, size_t n_channels, uint8_t* out);
 /* RgbImage::save("output/test.png") (main.rs:55): 8-bit RGB PNG */

@@ -16,6 +16,7 @@
 
 #include "common/rng.h"
 #include "common/schedule.h"
+#include "device/denoise.h"
 #include "device/device.h"
 #include "host/scene.h"
 #include "rtamd.h"
@@ -1179,6 +1180,72 @@ int rt_render_sppm(const rt_scene* s, const rt_camera* cam, const rt_params* p, 
         return (int)RT_OK;
     });
 }
+// ---- guide buffers and the a-trous filter (device/aov.inc, device/denoise.hip through the weak declarations of device/denoise.h) ----
+int rt_render_aov(const rt_scene* s, const rt_camera* cam, const rt_params* p, int32_t aov_spp, double* out_aov, rt_stats* stats) {
+    return guard([&] {
+        REQUIRE(s && cam && p && out_aov, "null argument");
+        REQUIRE(p->width > 0 && p->height > 0, "width/height must be positive");
+        REQUIRE(aov_spp > 0, "aov_spp must be positive");
+        REQUIRE(p->world == 1 && p->rank == 0, "rt_render_aov renders whole frames: rank / world must be 0 / 1");
+        REQUIRE(p->kernel >= 0 && p->kernel <= 2, "rt_render_aov walks with kernel 0 (auto), 1 or 2");
+        if (!s->committed) throw RtError(RT_ERR_NOT_COMMITTED, "rt_scene_commit has not been called");
+        if (!render_aov || device_count() < 1) throw RtError(RT_ERR_NO_DEVICE, "no HIP device: librtamd has no CPU fallback");
+        auto t0 = std::chrono::steady_clock::now();
+        DeviceScope dev_scope(p->device);
+        rt_stats st{};
+        render_aov(*s, make_camera(*cam), p->width, p->height, p->seed, p->t_min, p->kernel, aov_spp, out_aov, &st);
+        if (stats) {
+            *stats = st;
+            stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        }
+        return (int)RT_OK;
+    });
+}
+void rt_default_denoise_config(rt_denoise_config* c) {
+    if (!c) return;
+    std::memset(c, 0, sizeof(*c));
+    c->iterations = 5;
+    c->normal_power_log2 = 7;
+    c->sigma_depth = 1.0;
+    c->sigma_albedo = 0.1;
+    c->sigma_luma = 4.0;
+    c->eps = 1e-10;
+    c->guides = 7;
+}
+static void check_denoise_args(const rt_denoise_config* cfg, int32_t width, int32_t height, const double* rgb, const double* variance,
+                               const double* aov, const double* out_rgb, const double* out_variance) {
+    REQUIRE(cfg && rgb && out_rgb, "null argument");
+    REQUIRE(width > 0 && height > 0 && (int64_t)width * height <= (int64_t(1) << 31), "width/height must be positive (at most 2^31 pixels)");
+    REQUIRE(cfg->iterations >= 1 && cfg->iterations <= 8, "iterations must be 1..8");
+    REQUIRE(cfg->normal_power_log2 >= 0 && cfg->normal_power_log2 <= 16, "normal_power_log2 must be 0..16");
+    for (double v : {cfg->sigma_depth, cfg->sigma_albedo, cfg->sigma_luma, cfg->eps})
+        REQUIRE(std::isfinite(v) && v > 0., "sigma_depth, sigma_albedo, sigma_luma and eps must be finite and positive");
+    REQUIRE(cfg->guides >= 0 && cfg->guides <= 7, "guides is a mask of bits 0 (normal), 1 (depth), 2 (albedo)");
+    for (int32_t r : cfg->reserved) REQUIRE(r == 0, "reserved fields of rt_denoise_config must be 0");
+    REQUIRE(!out_variance || variance, "out_variance needs a variance input");
+    for (const double* o : {out_rgb, out_variance})
+        REQUIRE(!o || (o != rgb && o != variance && o != aov), "outputs must not be inputs");
+    REQUIRE(!out_variance || out_variance != out_rgb, "out_rgb and out_variance must differ");
+}
+int rt_denoise(const rt_denoise_config* cfg, int32_t width, int32_t height, const double* rgb, const double* variance, const double* aov,
+               double* out_rgb, double* out_variance) {
+    return guard([&] {
+        check_denoise_args(cfg, width, height, rgb, variance, aov, out_rgb, out_variance);
+        if (!denoise_host || device_count() < 1) throw RtError(RT_ERR_NO_DEVICE, "no HIP device: librtamd has no CPU fallback");
+        denoise_host(*cfg, width, height, rgb, variance, aov, out_rgb, out_variance);
+        return (int)RT_OK;
+    });
+}
+int rt_denoise_device(const rt_denoise_config* cfg, int32_t width, int32_t height, const double* d_rgb, const double* d_variance,
+                      const double* d_aov, double* d_out_rgb, double* d_out_variance, void* hip_stream) {
+    return guard([&] {
+        check_denoise_args(cfg, width, height, d_rgb, d_variance, d_aov, d_out_rgb, d_out_variance);
+        if (!denoise_device || device_count() < 1) throw RtError(RT_ERR_NO_DEVICE, "no HIP device: librtamd has no CPU fallback");
+        denoise_device(*cfg, width, height, d_rgb, d_variance, d_aov, d_out_rgb, d_out_variance, hip_stream);
+        return (int)RT_OK;
+    });
+}
+
 int rt_tonemap_u8(const double* rgb, size_t n_channels, uint8_t* out) {
     return guard([&] {
         REQUIRE((rgb && out) || n_channels == 0, "null argument");

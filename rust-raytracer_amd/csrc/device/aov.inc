@@ -1,0 +1,118 @@
+// rt_render_aov (DESIGN.md s4e): the first-hit guide buffers of the a-trous filter (device/denoise.hip).  Included at the end of
+// kernels.hip, whose walks, materialize and tex_color it uses as they are; no render kernel changes.
+//
+// One pixel per thread.  Sample s of pixel (x, y) is pt_kernel's camera ray -- stream (seed, y * width + x, s), the same jitter and
+// lens draws -- and its first hit World::hit(ray, t_min, +inf), by the reference-order walk (ACCEL false, kernel 1) or kernel 2's
+// accel walk (stacks in LDS, stride blockDim.x, as hit_kernel keeps them).  GENERAL 3 is the chain walk of nested Transforms.  The hit
+// record is built with uv for every primitive, as the closest-hit diagnostic builds it; the albedo is tex_color of the material's one
+// texture (noise textures included: the GENERAL >= 2 form).  Sums in sample order, f64; out[pix] = {normal[3], t, albedo[3], coverage}.
+
+#include "denoise.h"
+
+namespace rtamd {
+
+template <bool ACCEL, int GENERAL>
+__global__ void __launch_bounds__(64) aov_kernel(FlatView sv, CamK cam, int width, int height, uint64_t seed, double t_min, int aov_spp,
+                                                 double* out, int* err) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= (size_t)width * (size_t)height) return;
+    Acc A = make_acc(sv.base, sv.base, sv);
+    uint32_t* stk = (uint32_t*)smem + threadIdx.x;
+    const int x = (int)(pix % (size_t)width), y = (int)(pix / (size_t)width);
+    double n0 = 0., n1 = 0., n2 = 0., tt = 0., a0 = 0., a1 = 0., a2 = 0.;
+    int hits = 0;
+    for (int s = 0; s < aov_spp; s++) {
+        // camera.rs:97-99 + Camera::get_ray camera.rs:57-64, as pt_kernel draws them
+        Rng rng;
+        rng.seed_stream(seed, (uint64_t)y * (uint64_t)width + (uint64_t)x, (uint64_t)s);
+        double u = ((double)x + rng.gen_f64()) / (double)(width - 1);
+        double v = ((double)y + rng.gen_f64()) / (double)(height - 1);
+        double st = 1.0 - v;
+        D3 rd = muls(random_in_unit_disk(rng), cam.lens_radius);
+        D3 offset = add(muls(cam.u, rd.x), muls(cam.v, rd.y));
+        D3 o = add(cam.origin, offset);
+        D3 d = sub(sub(add(add(cam.llc, muls(cam.horizontal, u)), muls(cam.vertical, st)), cam.origin), offset);
+        const Hit h = ACCEL ? traverse2<GENERAL, false, false>(A, stk, (int)blockDim.x, o, d, t_min, INFINITY) : traverse<GENERAL>(A, o, d, t_min, INFINITY);
+        if (h.node < 0) continue;
+        const Rec rec = materialize<GENERAL, true>(A, h, o, d, err);
+        const D3 alb = tex_color<(GENERAL >= 2 ? GENERAL : 2)>(A, A.mats[rec.mat].tex, rec);
+        n0 += rec.normal.x; n1 += rec.normal.y; n2 += rec.normal.z;
+        tt += h.t;
+        a0 += alb.x; a1 += alb.y; a2 += alb.z;
+        hits++;
+    }
+    double* q = out + 8 * pix;
+    if (hits == 0) {
+        for (int k = 0; k < 8; k++) q[k] = 0.;
+        return;
+    }
+    const double nh = (double)hits;
+    q[0] = n0 / nh; q[1] = n1 / nh; q[2] = n2 / nh;
+    q[3] = tt / nh;
+    q[4] = a0 / nh; q[5] = a1 / nh; q[6] = a2 / nh;
+    q[7] = nh / (double)aov_spp;
+}
+
+void render_aov(const rt_scene& s, const CameraDev& cam, int width, int height, uint64_t seed, double t_min, int kernel, int aov_spp, double* out_host,
+                rt_stats* st) {
+    if (!s.committed) throw RtError(RT_ERR_NOT_COMMITTED, "scene not committed");
+    if (s.flat.view.kinds_mask & (1u << NK_MSPHERE))
+        throw RtError(RT_ERR_UNSUPPORTED, "rt_render_aov has no ray time: scenes with moving spheres are not supported");
+    if (s.flat.view.kinds_mask & (1u << NK_MEDIUM_BEGIN))
+        throw RtError(RT_ERR_UNSUPPORTED, "rt_render_aov: the first hit in a scene with a ConstantMedium depends on the path's random stream (no guides through media)");
+    int dev = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    const DevInfo& di = dev_info(dev);
+    FlatView view = s.flat.view;
+    double upload_ms = 0.;
+    view.base = device_blob(s, dev, &upload_ms);
+    // kernel 2's walk under render_tiles' conditions: a usable accel, the camera inside the region the f32 boxes were padded for,
+    // t_min >= 0, and the per-lane stacks in LDS
+    const double cam_abs = std::fmax(std::fmax(std::fabs(cam.origin[0]), std::fabs(cam.origin[1])), std::fabs(cam.origin[2])) + std::fabs(cam.lens_radius);
+    const bool camera_ok = cam_abs <= view.origin_limit2 && std::isfinite(cam_abs) && t_min >= 0.;
+    const size_t stack_bytes = (size_t)view.stack2 * 64 * sizeof(uint32_t);
+    const bool accel_usable = view.accel_ok && camera_ok && stack_bytes <= di.lds_max;
+    if (kernel == 0) kernel = accel_usable ? 2 : 1;
+    if (kernel == 2 && !accel_usable)
+        throw RtError(RT_ERR_UNSUPPORTED, "kernel 2 requested but no usable accel for this scene/camera (unbounded item, depth overflow, stacks "
+                                          "larger than LDS, negative t_min, or camera farther than 64x the scene extent); use kernel 0/1");
+    if (kernel != 1 && kernel != 2) throw RtError(RT_ERR_ARG, "rt_render_aov walks with kernel 1 or 2");
+    const bool nest = s.flat.xf_nest != 0u;  // nested Transforms: the chain walk (GENERAL == 3)
+    typedef void (*aov_fn)(FlatView, CamK, int, int, uint64_t, double, int, double*, int*);
+    const aov_fn fn = (kernel == 2) ? (nest ? aov_kernel<true, 3> : aov_kernel<true, 1>) : (nest ? aov_kernel<false, 3> : aov_kernel<false, 1>);
+    const size_t smem = (kernel == 2) ? stack_bytes : 0;
+    if (smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    const size_t npix = (size_t)width * (size_t)height;
+    DevBuf dout, err;
+    dout.alloc(npix * 8 * sizeof(double));
+    err.alloc(4);
+    HIP_CHECK(hipMemset(err.p, 0, 4));
+    Events events;
+    hipEvent_t e0 = events.make(), e1 = events.make();
+    const unsigned blocks = (unsigned)((npix + 63) / 64);
+    HIP_CHECK(hipEventRecord(e0, 0));
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(64), smem, 0, view, to_camk(cam), width, height, seed, t_min, aov_spp, (double*)dout.p, (int*)err.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(e1, 0));
+    HIP_CHECK(hipEventSynchronize(e1));
+    int h_err = 0;
+    HIP_CHECK(hipMemcpy(&h_err, err.p, 4, hipMemcpyDeviceToHost));
+    if (h_err & 1) throw RtError(RT_ERR_UNIT_ZERO, "unitizing zero vector (device, rt_render_aov)");
+    if (h_err & ~1) throw RtError(RT_ERR_INTERNAL, "device invariant failed in rt_render_aov (error bits " + std::to_string(h_err) + ")");
+    HIP_CHECK(hipMemcpy(out_host, dout.p, npix * 8 * sizeof(double), hipMemcpyDeviceToHost));
+    if (st) {
+        float ms = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+        st->kernel_ms = ms;
+        st->upload_ms = upload_ms;
+        st->samples = (uint64_t)npix * (uint64_t)aov_spp;
+        st->launches = 1;
+        st->kernel_used = kernel;
+        st->block_threads = 64;
+        st->grid_blocks = (int32_t)blocks;
+        st->scene_bytes = s.flat.info.bytes;
+    }
+}
+
+}  // namespace rtamd

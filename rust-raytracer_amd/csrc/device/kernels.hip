@@ -4718,3 +4718,6 @@ void debug_hit_device(const rt_scene& s, int kernel, size_t n, const double* ray
 }
 
 }  // namespace rtamd
+
+// rt_render_aov: the first-hit guide buffers of the denoiser
+#include "aov.inc"

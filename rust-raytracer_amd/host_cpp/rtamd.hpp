@@ -462,9 +462,36 @@ class World {
         return true;
     }
 
+    // First-hit guide buffers of the first aov_spp camera rays of every pixel (rt_render_aov): [height][width][8] =
+    // {normal[3], t, albedo[3], coverage}; the filter's guides (denoise below)
+    std::vector<double> render_aov(const Config& cfg, int aov_spp = 4, int kernel = 0, rt_stats* stats = nullptr) const {
+        rt_params p;
+        rt_default_params(&p);
+        p.width = cfg.width; p.height = cfg.height; p.t_min = cfg.t_min; p.seed = cfg.seed; p.kernel = kernel;
+        std::vector<double> aov((size_t)cfg.width * cfg.height * 8);
+        check(rt_render_aov(s_, &cam.c, &p, aov_spp, aov.data(), stats));
+        return aov;
+    }
+
    private:
     rt_scene* s_ = nullptr;
 };
+
+// The edge-aware a-trous filter (rt_denoise) on host buffers: rgb [height][width][3]; variance [height][width] and aov
+// [height][width][8] may be empty (no luminance weight / no guides); cfg NULL = rt_default_denoise_config.
+inline std::vector<double> denoise(int width, int height, const std::vector<double>& rgb, const std::vector<double>& variance = {},
+                                   const std::vector<double>& aov = {}, const rt_denoise_config* cfg = nullptr) {
+    const size_t n = (size_t)width * (size_t)height;
+    if (width <= 0 || height <= 0 || rgb.size() != n * 3 || (!variance.empty() && variance.size() != n) || (!aov.empty() && aov.size() != n * 8))
+        throw Error(RT_ERR_ARG, "denoise: buffer sizes do not match the frame");
+    rt_denoise_config dc;
+    rt_default_denoise_config(&dc);
+    if (cfg) dc = *cfg;
+    std::vector<double> out(n * 3);
+    check(rt_denoise(&dc, width, height, rgb.data(), variance.empty() ? nullptr : variance.data(), aov.empty() ? nullptr : aov.data(), out.data(),
+                     nullptr));
+    return out;
+}
 
 // scene.rs:16-112 cornell_box_scene(), written against the mirrored types exactly as the reference writes it
 inline std::unique_ptr<World> cornell_box_scene(const std::string& cube_obj, double aspect_ratio = 1.0, uint64_t bvh_seed = 1) {

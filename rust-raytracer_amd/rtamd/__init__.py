@@ -64,6 +64,11 @@ class rt_sppm_config(C.Structure):
                 ("max_bounces", C.c_int32), ("reserved", C.c_int32), ("alpha", C.c_double)]
 
 
+class rt_denoise_config(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("normal_power_log2", C.c_int32), ("sigma_depth", C.c_double), ("sigma_albedo", C.c_double),
+                ("sigma_luma", C.c_double), ("eps", C.c_double), ("guides", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
 class rt_tuning(C.Structure):
     _fields_ = [("no_lds", C.c_int32), ("top_nodes", C.c_int32), ("sub_spp", C.c_int32), ("coop_pool", C.c_int32),
                 ("max_leaf", C.c_int32), ("sppm_photon_capacity", C.c_int32), ("sppm_knn_candidates", C.c_int32),
@@ -153,6 +158,11 @@ _SIGS = [
     ("rt_render_sppm_multi", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_sppm_config), C.c_int, C.POINTER(C.c_int), _dp,
                               C.POINTER(rt_stats)]),
     ("rt_rccl_version", C.c_int, []),
+    ("rt_render_aov", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.c_int32, _dp, C.POINTER(rt_stats)]),
+    ("rt_default_denoise_config", None, [C.POINTER(rt_denoise_config)]),
+    ("rt_denoise", C.c_int, [C.POINTER(rt_denoise_config), C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp]),
+    ("rt_denoise_device", C.c_int, [C.POINTER(rt_denoise_config), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
     ("rt_render_tiles_device", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.c_void_p, C.c_void_p,
                                          C.POINTER(rt_stats)]),
     ("rt_render_sppm_tiles_device", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_sppm_config), C.c_void_p,
@@ -561,6 +571,42 @@ class World:
         d["prepass_seconds"] = st.reserved[0] * 1e-6
         return d
 
+    # --- guide buffers and denoising ---
+    def render_aov(self, camera, width, height, aov_spp=4, seed=1, kernel=0, t_min=1e-3, device=-1):
+        """rt_render_aov: first-hit guide buffers [H, W, 8] = {normal[3], t, albedo[3], coverage}, averaged over the aov_spp camera rays
+        render() draws first for each pixel (samples 0 .. aov_spp-1 of stream (seed, pixel, s)); returns (aov, stats dict)."""
+        p = default_params(width=width, height=height, seed=seed, kernel=kernel, t_min=t_min, device=device)
+        out = np.zeros((height, width, 8), dtype=np.float64)
+        st = rt_stats()
+        _chk(self.L.rt_render_aov(self.h, C.byref(camera.c), C.byref(p), int(aov_spp), out.ctypes.data_as(_dp), C.byref(st)))
+        return out, st.as_dict()
+
+    def render_denoised(self, camera, width=800, height=800, spp=256, guides=True, aov_spp=4, max_depth=50, t_min=1e-3, seed=1,
+                        kernel=0, device=-1, integrator=0, **cfg):
+        """A frame, its variance and its guides, filtered by rt_denoise.  spp must be even: samples [0, spp/2) and [spp/2, spp) go through
+        the resumable path (rt_render_accumulate) into ONE accumulator, so `noisy` is bit for bit render()'s frame; the half-means A and B
+        give variance = (l_A - l_B)^2 / 4 of the pixel's mean luminance l.  guides=False skips rt_render_aov (aov is None then: scenes
+        with media or moving spheres).  cfg: rt_denoise_config fields.  Returns (denoised, noisy, variance, aov)."""
+        if spp < 2 or spp % 2:
+            raise ValueError("render_denoised needs an even spp >= 2 (two half-frames), got %r" % (spp,))
+        p = default_params(width=width, height=height, spp=spp, max_depth=max_depth, t_min=t_min, seed=seed, kernel=kernel, device=device,
+                           integrator=integrator)
+        half = spp // 2
+        state, _ = self.render_accumulate(camera, p, 0, half)
+        first = state.copy()
+        state, _ = self.render_accumulate(camera, p, half, spp, state)
+        noisy = accum_finalize(p, state)
+        ph = default_params(width=width, height=height, spp=half, max_depth=max_depth, t_min=t_min, seed=seed, kernel=kernel, device=device,
+                            integrator=integrator)
+        mean_a = accum_finalize(ph, first)
+        mean_b = accum_finalize(ph, state - first)
+        variance = (luminance(mean_a) - luminance(mean_b)) ** 2 / 4.0
+        aov = None
+        if guides:  # (the guides take kernel 1's or kernel 2's walk: kernels 5 / 6 render the frame, the automatic choice walks the guides)
+            aov = self.render_aov(camera, width, height, aov_spp=aov_spp, seed=seed, kernel=kernel if kernel in (1, 2) else 0, t_min=t_min,
+                                  device=device)[0]
+        return denoise(noisy, variance, aov, **cfg), noisy, variance, aov
+
     def debug_hit(self, rays, t_min=1e-3, t_max=float("inf"), kernel=1):
         r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
         out = np.zeros((r.shape[0], 12), dtype=np.float64)
@@ -637,6 +683,57 @@ def accum_finalize(params, state):
 def accum_finalize_device(params, d_accum_ptr, d_tiles_ptr, stream_ptr=None):
     """rt_accum_finalize_device: d_tiles = d_accum / params.spp (the end of a resumable render, World.render_accumulate_device)"""
     _chk(lib().rt_accum_finalize_device(C.byref(params), C.c_void_p(d_accum_ptr), C.c_void_p(d_tiles_ptr), C.c_void_p(stream_ptr or 0)))
+
+
+def denoise_config(**fields):
+    """rt_default_denoise_config with `fields` (rt_denoise_config names) set"""
+    c = rt_denoise_config()
+    lib().rt_default_denoise_config(C.byref(c))
+    for k, v in fields.items():
+        if k == "reserved" or not hasattr(c, k):
+            raise TypeError("unknown denoiser setting %r" % k)
+        setattr(c, k, v)
+    return c
+
+
+def luminance(rgb):
+    """l = (0.2126 r + 0.7152 g) + 0.0722 b, the filter's luminance (same operation order)"""
+    rgb = np.asarray(rgb, dtype=np.float64)
+    return (0.2126 * rgb[..., 0] + 0.7152 * rgb[..., 1]) + 0.0722 * rgb[..., 2]
+
+
+def denoise(rgb, variance=None, aov=None, return_variance=False, **cfg):
+    """rt_denoise: the a-trous filter on host arrays.  rgb [H, W, 3]; variance [H, W] of each pixel's mean luminance (None: no luminance
+    weight); aov [H, W, 8] from World.render_aov (None: no guides).  cfg: rt_denoise_config fields (iterations, normal_power_log2,
+    sigma_depth, sigma_albedo, sigma_luma, eps, guides).  Returns the filtered [H, W, 3], and with return_variance also the filtered variance."""
+    c = denoise_config(**cfg)
+    rgb = np.ascontiguousarray(rgb, dtype=np.float64)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError("rgb must be [H, W, 3]")
+    h, w = rgb.shape[:2]
+    var_p = aov_p = None
+    if variance is not None:
+        variance = np.ascontiguousarray(variance, dtype=np.float64)
+        if variance.shape != (h, w):
+            raise ValueError("variance must be [H, W]")
+        var_p = variance.ctypes.data_as(_dp)
+    if aov is not None:
+        aov = np.ascontiguousarray(aov, dtype=np.float64)
+        if aov.shape != (h, w, 8):
+            raise ValueError("aov must be [H, W, 8]")
+        aov_p = aov.ctypes.data_as(_dp)
+    out = np.zeros_like(rgb)
+    out_var = np.zeros((h, w), dtype=np.float64) if return_variance else None
+    _chk(lib().rt_denoise(C.byref(c), w, h, rgb.ctypes.data_as(_dp), var_p, aov_p, out.ctypes.data_as(_dp),
+                          out_var.ctypes.data_as(_dp) if out_var is not None else None))
+    return (out, out_var) if return_variance else out
+
+
+def denoise_device(width, height, d_rgb_ptr, d_out_ptr, d_variance_ptr=None, d_aov_ptr=None, d_out_variance_ptr=None, stream_ptr=None, **cfg):
+    """rt_denoise_device: raw device pointers (e.g. torch tensor .data_ptr()) of the current device; returns when the passes are done"""
+    c = denoise_config(**cfg)
+    _chk(lib().rt_denoise_device(C.byref(c), int(width), int(height), C.c_void_p(d_rgb_ptr), C.c_void_p(d_variance_ptr or 0), C.c_void_p(d_aov_ptr or 0),
+                                 C.c_void_p(d_out_ptr), C.c_void_p(d_out_variance_ptr or 0), C.c_void_p(stream_ptr or 0)))
 
 
 def tonemap_u8(rgb):

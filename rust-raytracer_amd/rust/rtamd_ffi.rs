@@ -126,6 +126,20 @@ pub struct rt_sppm_config {
     pub alpha: c_double,
 }
 
+/// include/rtamd.h rt_denoise_config (rt_default_denoise_config fills it)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct rt_denoise_config {
+    pub iterations: i32,
+    pub normal_power_log2: i32,
+    pub sigma_depth: c_double,
+    pub sigma_albedo: c_double,
+    pub sigma_luma: c_double,
+    pub eps: c_double,
+    pub guides: i32,
+    pub reserved: [i32; 5],
+}
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct rt_tuning {
@@ -249,6 +263,10 @@ extern "C" {
     pub fn rt_render_multi_camera_frame(s: *const rt_scene, frame: *const rt_camera_frame, p: *const rt_params, n_devices: c_int, device_ids: *const c_int, out_rgb: *mut c_double, stats: *mut rt_stats) -> c_int;
     pub fn rt_render_sppm_multi(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, cfg: *const rt_sppm_config, n_devices: c_int, device_ids: *const c_int, out_rgb: *mut c_double, stats: *mut rt_stats) -> c_int;
     pub fn rt_rccl_version() -> c_int;
+    pub fn rt_render_aov(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, aov_spp: i32, out_aov: *mut c_double, stats: *mut rt_stats) -> c_int;
+    pub fn rt_default_denoise_config(c: *mut rt_denoise_config);
+    pub fn rt_denoise(cfg: *const rt_denoise_config, width: i32, height: i32, rgb: *const c_double, variance: *const c_double, aov: *const c_double, out_rgb: *mut c_double, out_variance: *mut c_double) -> c_int;
+    pub fn rt_denoise_device(cfg: *const rt_denoise_config, width: i32, height: i32, d_rgb: *const c_double, d_variance: *const c_double, d_aov: *const c_double, d_out_rgb: *mut c_double, d_out_variance: *mut c_double, hip_stream: *mut c_void) -> c_int;
     pub fn rt_render_sppm(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, cfg: *const rt_sppm_config, out_rgb: *mut c_double, stats_out: *mut c_double, photons_stored: *mut u64, stats: *mut rt_stats) -> c_int;
     pub fn rt_render_tiles_device(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, d_tiles: *mut c_double, hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
     pub fn rt_render_sppm_tiles_device(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, cfg: *const rt_sppm_config, d_tiles: *mut c_double, hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
@@ -541,6 +559,13 @@ impl Scene {
         check(unsafe { rt_render_sppm_multi(self.raw, cam, p, cfg, n as c_int, std::ptr::null(), out.as_mut_ptr(), st.as_mut_ptr()) })?;
         Ok((out, st))
     }
+    /// rt_render_aov: first-hit guide buffers, [height][width][8] = {normal[3], t, albedo[3], coverage}
+    pub fn render_aov(&self, cam: &rt_camera, p: &rt_params, aov_spp: i32) -> Result<(Vec<f64>, rt_stats), RtError> {
+        let mut out = vec![0.0f64; (p.width as usize) * (p.height as usize) * 8];
+        let mut st = rt_stats::default();
+        check(unsafe { rt_render_aov(self.raw, cam, p, aov_spp, out.as_mut_ptr(), &mut st) })?;
+        Ok((out, st))
+    }
     pub fn render_sppm(&self, cam: &rt_camera, p: &rt_params, cfg: &rt_sppm_config) -> Result<(Vec<f64>, rt_stats), RtError> {
         let mut out = vec![0.0f64; (p.width as usize) * (p.height as usize) * 3];
         let mut st = rt_stats::default();
@@ -745,6 +770,26 @@ impl DescribeHitable for XZRectLight {
 
 // ------------------------------------------------------------------ capture_image ----
 /// camera.rs:12-21: the stored frame of a constructed Camera
+/// rt_denoise: the edge-aware a-trous filter on host buffers (rgb [h][w][3]; variance [h][w] and aov [h][w][8] optional);
+/// cfg None = rt_default_denoise_config
+pub fn denoise(width: i32, height: i32, rgb: &[f64], variance: Option<&[f64]>, aov: Option<&[f64]>, cfg: Option<&rt_denoise_config>) -> Result<Vec<f64>, RtError> {
+    let n = (width.max(0) as usize) * (height.max(0) as usize);
+    if n == 0 || rgb.len() != n * 3 || variance.map_or(false, |v| v.len() != n) || aov.map_or(false, |a| a.len() != n * 8) {
+        return Err(RtError { code: -1, message: "denoise: buffer sizes do not match the frame".to_string() });
+    }
+    let mut c = rt_denoise_config::default();
+    match cfg {
+        Some(x) => c = *x,
+        None => unsafe { rt_default_denoise_config(&mut c) },
+    }
+    let mut out = vec![0.0f64; n * 3];
+    check(unsafe {
+        rt_denoise(&c, width, height, rgb.as_ptr(), variance.map_or(std::ptr::null(), |v| v.as_ptr()), aov.map_or(std::ptr::null(), |a| a.as_ptr()),
+                   out.as_mut_ptr(), std::ptr::null_mut())
+    })?;
+    Ok(out)
+}
+
 pub fn camera_frame(cam: &Camera) -> rt_camera_frame {
     rt_camera_frame {
         origin: v3(&cam.origin),

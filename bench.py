@@ -26,7 +26,7 @@ Extra objects on the JSON line (definitions and formulas: DESIGN.md s5):
   roofline_contract -- SURVEY s8d: algorithmic bytes per sample in the REFERENCE's traversal order / kernel time
                        against the 8 TB/s HBM peak.  The scene is LDS-resident, so this is not a physical fraction.
   roofline_hbm      -- physical HBM traffic (PMC, carried over) / kernel time against the HBM peak.
-  cpu_baseline      -- the oracle (a C++ port of the reference's CPU path; the Rust binary cannot be
+  cpu_baseline      -- --full only: the oracle (a C++ port of the reference's CPU path; the Rust binary cannot be
                        built here) on this box's host cores, bounded sample, rank 0 at N=1 only.
   ranks             -- one entry per rank (all_gather at the end of the timed region): tiles owned, samples, summed pt_kernel time
                        (HIP events inside librtamd), time of gather + stitch (HIP events on the step's stream; the RCCL gather is
@@ -36,6 +36,10 @@ Extra objects on the JSON line (definitions and formulas: DESIGN.md s5):
 `--single-process` renders the same frames through rt_render_multi instead (ONE process, one host thread per GPU inside librtamd,
 RCCL gather linked into the library -- what a Rust / C++ host calls); same JSON line, "launch": "single-process".  The default,
 and what the driver starts, is one process per GPU over torch.distributed.
+
+`--full`: also measure what the headline figure does not need -- today the CPU baseline (`cpu_baseline` above, about half a minute
+of host time after the timed steps).  Off by default: a plain run sets up, warms up, times the steps, writes --dump-outputs and prints
+the line; every other object on it is derived from the timed steps themselves.
 
 `--dump-outputs DIR`: after the timed steps, rank 0 writes the stitched f64 frame of the last timed step -- what a caller of the path
 receives -- as DIR/frame.npy (see dump_outputs).  The inputs depend on the arguments alone (committed scene file, --seed), so two
@@ -316,7 +320,9 @@ def main():
     ap.add_argument("--spp", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--kernel", type=int, default=0, help="0 = library default; 1 / 2 / 5 force a traversal (A/B runs only)")
-    ap.add_argument("--cpu-spp", type=int, default=32, help="spp of the bounded CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline (cpu_baseline, world 1 only)")
+    ap.add_argument("--cpu-spp", type=int, default=32, help="--full: spp of the bounded CPU-baseline sample (0 = skip)")
     ap.add_argument("--force-pg", action="store_true",
                     help="world 1 only: create the RCCL process group anyway and drive the N-rank exchange through it (init, gather of "
                          "the f64 device rows, barrier, all_reduce(MAX)); also RTAMD_BENCH_FORCE_PG=1")
@@ -494,7 +500,7 @@ def main():
             out["dumped_outputs"] = dump_outputs(args.dump_outputs, host_frame)
         if rehearse:
             out["rehearsal"] = "all %d ranks share HIP device 0, gather over gloo through host memory: NOT a scaling measurement" % world_size
-        if world_size == 1 and args.cpu_spp > 0:
+        if args.full and world_size == 1 and args.cpu_spp > 0:
             out["cpu_baseline"] = cpu_baseline(args.width, args.height, args.cpu_spp, args.seed)
         if json_fd is not None:
             sys.stdout.flush()

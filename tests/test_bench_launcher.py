@@ -154,11 +154,10 @@ def test_forced_process_group_runs_the_rccl_exchange_at_world_1(how, tmp_path):
     one touches the GPU for it.  The stitched frame must equal the plain render bit for bit (camera.rs:77,108,115-123)."""
     import numpy as np
     out_npy = str(tmp_path / "frame.npy")
-    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--width", "96", "--height", "72", "--spp", "8", "--cpu-spp", "2" if how == "flag" else "0",
-            "--frame-out", out_npy]
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--width", "96", "--height", "72", "--spp", "8", "--frame-out", out_npy]
     env = {}
     if how == "flag":
-        args.append("--force-pg")
+        args += ["--force-pg", "--full", "--cpu-spp", "2"]   # --full adds the CPU baseline; a plain run (below) leaves it out
     else:  # the environment torch.distributed.run gives a rank
         import socket
         s = socket.socket()
@@ -190,6 +189,8 @@ def test_forced_process_group_runs_the_rccl_exchange_at_world_1(how, tmp_path):
     if how == "flag":
         cb = out["cpu_baseline"]
         assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and "sample" in cb and "cpu_model" in cb and cb["reference_default"]["cores"] <= 8
+    else:
+        assert "cpu_baseline" not in out
     assert len([ln for ln in r.stdout.splitlines() if ln.strip()]) == 1      # ONE line on stdout (RCCL's banner goes to stderr)
     got = np.load(out_npy)
     assert got.shape == (72, 96, 3) and np.array_equal(got, _plain_frame(96, 72, 8))

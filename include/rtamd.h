@@ -430,6 +430,32 @@ int rt_denoise(const rt_denoise_config* cfg, int32_t width, int32_t height, cons
 int rt_denoise_device(const rt_denoise_config* cfg, int32_t width, int32_t height, const double* d_rgb, const double* d_variance,
                       const double* d_aov, double* d_out_rgb, double* d_out_variance, void* hip_stream);
 
+/* ---- tile-adaptive sampling (no reference counterpart) ------------------------------------------------------------ */
+/* A whole frame on one device (p->world 1, p->rank 0, p->device picks it) in which every 8x8 tile T gets its own sample count n_T.  With
+ * h = min_spp / 2 the passes trace the sample ranges [0, h), [h, 2h), [2h, 4h), [4h, 8h), ..., each capped at p->spp (the last one is
+ * [n, p->spp)), over the tiles still active, all of them over the same range (the resumable path: the RNG is keyed by (seed, pixel,
+ * sample)).  After a pass that ends at n = 2m < p->spp every active tile is tested: with S its running sums and S^m their snapshot at m,
+ * the two-buffer error of Dammertz et al. (WSCG 2009) is, in f64 without contraction, for each in-image pixel of the tile in pixel index
+ * order (row-major inside the tile):
+ *   I_c = S_c / n, A_c = S^m_c / m (finalize's divisions), s = (I_r + I_g) + I_b,
+ *   e_p = s > 0 ? ((|I_r - A_r| + |I_g - A_g|) + |I_b - A_b|) / sqrt(s) : 0,
+ * e_T = the e_p added one at a time in that order from 0.0, divided by the tile's in-image pixel count.  The tile stops (n_T = n, for
+ * good) when e_T < threshold -- a NaN error never stops a tile -- so n_T is one of {2h, 4h, ..., p->spp}.  out_rgb (HOST, [H][W][3]) =
+ * S / n_T (0 outside the image); every tile is rt_render's frame at spp = n_T on that tile, bit for bit, and threshold 0 gives
+ * rt_render's frame.  The result depends on no schedule knob (sub_spp, spp_chunk, job size).  out_tile_spp (HOST, [tiles_y][tiles_x],
+ * or NULL) receives n_T.  Kernels 0 / 1 / 2 / 5 and integrators 0 / 1 (those of rt_render_accumulate_device); kernel 6 and integrator 2
+ * are RT_ERR_UNSUPPORTED.  A bad config (min_spp odd, below 2 or above p->spp; threshold negative or NaN) or p->world != 1 is RT_ERR_ARG,
+ * checked before the device.  stats: seconds; kernel_ms and launches summed over the passes; samples = the in-image pixel-samples
+ * actually traced (the sum over tiles of n_T x in-image pixels); the rest from the first pass. */
+typedef struct rt_adaptive_config {
+    int32_t min_spp;   /* even, 2 <= min_spp <= p->spp: samples every tile gets before it may stop; default 16 */
+    int32_t reserved;
+    double threshold;  /* >= 0, not NaN: a tile stops once e_T < threshold; 0 = never stop (the frame is rt_render's); default 0.002 */
+} rt_adaptive_config;
+void rt_default_adaptive_config(rt_adaptive_config* c);
+int rt_render_adaptive(const rt_scene* s, const rt_camera* cam, const rt_params* p, const rt_adaptive_config* cfg, double* out_rgb,
+                       int32_t* out_tile_spp, rt_stats* stats);
+
 /* From<Vec3> for Rgb<u8> (vec3.rs:223-231): floor(clamp(sqrt(c),0,1)*255), NaN -> 0.  Host buffers. */
 int rt_tonemap_u8(const double* rgb, size_t n_channels, uint8_t* out);
 /* RgbImage::save("output/test.png") (main.rs:55): 8-bit RGB PNG */

@@ -16,6 +16,7 @@
 
 #include "common/rng.h"
 #include "common/schedule.h"
+#include "device/adaptive.h"
 #include "device/denoise.h"
 #include "device/device.h"
 #include "host/scene.h"
@@ -595,7 +596,8 @@ int rt_scene_info_get(const rt_scene* s, rt_scene_info* out) {
 }
 
 // ---- render --------------------------------------------------------------
-static RenderPlan make_plan(const rt_params* p) {
+// owned >= 0: a plan for that many tiles in place of the rank's partition (rt_render_adaptive's passes over a tile list)
+static RenderPlan make_plan(const rt_params* p, int64_t owned = -1) {
     REQUIRE(p, "null params");
     REQUIRE(p->width > 0 && p->height > 0, "width/height must be positive");
     REQUIRE(p->spp > 0, "spp must be positive");
@@ -612,6 +614,7 @@ static RenderPlan make_plan(const rt_params* p) {
     pl.tiles_total = (int64_t)pl.tiles_x * pl.tiles_y;
     pl.tiles_owned = (pl.tiles_total - p->rank + p->world - 1) / p->world;
     if (pl.tiles_owned < 0) pl.tiles_owned = 0;
+    if (owned >= 0) pl.tiles_owned = owned;
     pl.kernel = p->kernel;
     pl.integrator = p->integrator;
     pl.time0 = p->time0;
@@ -766,6 +769,103 @@ int rt_accum_finalize(const rt_params* p, const double* accum_state, double* out
         finalize_tiles(pl, (const double*)acc.p, (double*)tiles.p, nullptr);
         assemble_frame(pl, (const double*)tiles.p, pl.tiles_owned, (double*)frame.p, nullptr);
         dev_copy_to_host(out_rgb, frame.p, frame_bytes);
+        return (int)RT_OK;
+    });
+}
+
+// ---- tile-adaptive sampling (the kernels between the passes: device/adaptive.inc) ----
+static const double kAdaptiveThreshold = 0.002;  // rt_default_adaptive_config (how it was chosen)
+void rt_default_adaptive_config(rt_adaptive_config* c) {
+    if (!c) return;
+    std::memset(c, 0, sizeof(*c));
+    c->min_spp = 16;
+    c->threshold = kAdaptiveThreshold;
+}
+int rt_render_adaptive(const rt_scene* s, const rt_camera* cam, const rt_params* p, const rt_adaptive_config* cfg, double* out_rgb,
+                       int32_t* out_tile_spp, rt_stats* stats) {
+    return guard([&] {
+        REQUIRE(s && cam && p && cfg && out_rgb, "null argument");
+        REQUIRE(p->world == 1 && p->rank == 0, "rt_render_adaptive renders whole frames: world must be 1 and rank 0");
+        REQUIRE(p->spp > 0, "spp must be positive");
+        REQUIRE(cfg->min_spp >= 2 && cfg->min_spp % 2 == 0 && cfg->min_spp <= p->spp, "min_spp must be even, >= 2 and <= spp");
+        REQUIRE(!std::isnan(cfg->threshold) && cfg->threshold >= 0., "threshold must be >= 0 (not NaN)");
+        if (p->kernel == 6 || p->integrator == 2)
+            throw RtError(RT_ERR_UNSUPPORTED, "rt_render_adaptive runs with kernels 0 / 1 / 2 / 5 and integrators 0 / 1");
+        const RenderPlan full = make_plan(p);
+        if (!s->committed) throw RtError(RT_ERR_NOT_COMMITTED, "rt_scene_commit has not been called");
+        if (!adaptive_test || device_count() < 1) throw RtError(RT_ERR_NO_DEVICE, "no HIP device: librtamd has no CPU fallback");
+        auto t0 = std::chrono::steady_clock::now();
+        DeviceScope dev_scope(p->device);
+        const CameraDev cd = make_camera(*cam);
+        const int64_t T = full.tiles_total;
+        const size_t acc_bytes = (size_t)T * TILE_PIX * 3 * sizeof(double), frame_bytes = (size_t)full.width * full.height * 3 * sizeof(double);
+        // the frame's running sums S, the half snapshot S_m, a pass's compact accumulator (also the finalized tiles at the end), the active
+        // list, the stop flags and errors of a test, the tiles' final spp, the frame
+        DevBuf acc, half, compact, list, stop, err, tile_spp, frame;
+        acc.p = dev_alloc(acc_bytes);
+        half.p = dev_alloc(acc_bytes);
+        compact.p = dev_alloc(acc_bytes);
+        list.p = dev_alloc((size_t)T * sizeof(int32_t));
+        stop.p = dev_alloc((size_t)T * sizeof(int32_t));
+        err.p = dev_alloc((size_t)T * sizeof(double));
+        tile_spp.p = dev_alloc((size_t)T * sizeof(int32_t));
+        frame.p = dev_alloc(frame_bytes);
+        std::vector<int32_t> active((size_t)T), n_t((size_t)T, full.spp), h_stop;
+        for (int64_t t = 0; t < T; t++) active[(size_t)t] = (int32_t)t;
+        auto tile_px = [&](int64_t t) {
+            const int tx = (int)(t % full.tiles_x), ty = (int)(t / full.tiles_x);
+            return (uint64_t)std::min(TILE_W, full.width - tx * TILE_W) * (uint64_t)std::min(TILE_H, full.height - ty * TILE_H);
+        };
+        rt_stats sum{};
+        uint64_t samples = 0;
+        bool first_pass = true;
+        const int h = cfg->min_spp / 2;
+        // passes [0, h), [h, 2h), [2h, 4h), ... capped at spp; a test after every pass that ends at n = 2m < spp
+        for (int begin = 0, end = h; begin < full.spp && !active.empty(); begin = end, end = (int)std::min<int64_t>((int64_t)end * 2, full.spp)) {
+            const int64_t na = (int64_t)active.size();
+            dev_copy_to_device(list.p, active.data(), (size_t)na * sizeof(int32_t));
+            if (begin > 0) adaptive_copy_tiles((double*)compact.p, nullptr, (const double*)acc.p, (const int32_t*)list.p, na, nullptr);
+            RenderPlan pl = make_plan(p, na);
+            pl.s_first = begin;
+            pl.s_last = end;
+            pl.ext_accum = (double*)compact.p;
+            pl.tile_list = (const int32_t*)list.p;
+            rt_stats st{};
+            render_tiles(*s, cd, pl, nullptr, nullptr, &st);
+            adaptive_copy_tiles((double*)acc.p, (const int32_t*)list.p, (const double*)compact.p, nullptr, na, nullptr);
+            for (int32_t t : active) samples += tile_px(t) * (uint64_t)(end - begin);
+            if (first_pass) {
+                sum = st;
+                first_pass = false;
+            } else {
+                sum.kernel_ms += st.kernel_ms;
+                sum.launches += st.launches;
+            }
+            if (begin == 0) {  // S_h: the first half snapshot, every tile
+                adaptive_copy_tiles((double*)half.p, nullptr, (const double*)acc.p, nullptr, T, nullptr);
+            } else if (end < full.spp) {
+                adaptive_test(full, (const double*)acc.p, (double*)half.p, (const int32_t*)list.p, na, end, end / 2, cfg->threshold, (int32_t*)stop.p,
+                              (double*)err.p, nullptr);
+                h_stop.resize((size_t)na);
+                dev_copy_to_host(h_stop.data(), stop.p, (size_t)na * sizeof(int32_t));
+                std::vector<int32_t> next;
+                for (int64_t i = 0; i < na; i++) {
+                    if (h_stop[(size_t)i]) n_t[(size_t)active[(size_t)i]] = end;
+                    else next.push_back(active[(size_t)i]);
+                }
+                active.swap(next);
+            }
+        }
+        dev_copy_to_device(tile_spp.p, n_t.data(), (size_t)T * sizeof(int32_t));
+        adaptive_finalize(full, (const double*)acc.p, (const int32_t*)tile_spp.p, (double*)compact.p, nullptr);
+        assemble_frame(full, (const double*)compact.p, T, (double*)frame.p, nullptr);
+        dev_copy_to_host(out_rgb, frame.p, frame_bytes);
+        if (out_tile_spp) std::memcpy(out_tile_spp, n_t.data(), (size_t)T * sizeof(int32_t));
+        if (stats) {
+            *stats = sum;
+            stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            stats->samples = samples;
+        }
         return (int)RT_OK;
     });
 }

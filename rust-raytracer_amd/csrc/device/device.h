@@ -27,6 +27,9 @@ struct RenderPlan {
     // into the CALLER's accumulator (device, [tiles_owned][64][3] f64 sums; s_first == 0 initialises it); no division by spp, d_tiles unused
     int s_first = 0, s_last = -1;
     double* ext_accum = nullptr;
+    // rt_render_adaptive: null, or DEVICE int32[tiles_owned] -- the image tiles this call renders, in place of the rank's
+    // partition; job tile j (and slot j of ext_accum, which must be set) is image tile tile_list[j]
+    const int32_t* tile_list = nullptr;
 };
 
 // Renders plan.tiles_owned tiles into d_tiles (device, tile-major f64 RGB) on `stream`; blocks until done.

@@ -268,6 +268,7 @@ struct RenderK {
     int coop_stack;          // kernel 5: stack entries per lane
     double time0, time1;     // D9: the camera's shutter; time1 > time0: every sample draws its time after the lens sample
     int time_slots;          // D9: 1 = the scene has moving spheres: 8 bytes of LDS per lane (behind the launch constants) hold the paths' times
+    const int* tile_list;    // null, or the image tiles of this launch (rt_render_adaptive's active tiles): job tile j renders tile_list[j]
 };
 
 // ------------------------------------------------------ intersection ------
@@ -1786,13 +1787,19 @@ __device__ __attribute__((noinline)) int fold_units(const uint32_t* rmeta, const
 enum { CFG_N_JOBS, CFG_TILES_OWNED, CFG_JOB_UNITS, CFG_SUBS_PER_TILE, CFG_WORLD, CFG_RANK, CFG_TILES_X, CFG_S_BEGIN, CFG_S_END, CFG_SUB_SPP,
        CFG_WIDTH, CFG_HEIGHT, CFG_RING_UNITS /* unit buffers per wave: RING_UNITS, kernel 6: WF_RING_UNITS */,
        CFG_JOB_LISTS /* lists next_unit() deals the tiles from: JOB_LISTS (one per XCD) or 1 */, CFG_LVL = 16 /* RenderK::lvl, 25 words */,
-       CFG_WORDS = 48 };
+       CFG_TILE_LIST = 42 /* RenderK::tile_list, 2 words (low, high) */, CFG_WORDS = 48 };
 static_assert(SCHED_LEVELS == 4, "RenderK::lvl holds SCHED_LEVELS + 1 rows");
 struct UnitInfo {
     int pool;      // paths of the unit that was started (0: none was)
     int s0, tx, ty, cur_slot;
     int finished;  // no job left, every unit folded: the wave may exit once its lanes are dead
 };
+// The image tile of job tile `job_tile` (an index into the rank's tiles, which also addresses the accumulator and the tickets): the
+// rank's partition, or the launch's tile list when it has one (rt_render_adaptive renders only the tiles still active)
+__device__ __forceinline__ int job_image_tile(const AS_L int* cfg, int job_tile) {
+    const uint64_t list = (uint64_t)(uint32_t)cfg[CFG_TILE_LIST] | ((uint64_t)(uint32_t)cfg[CFG_TILE_LIST + 1] << 32);
+    return list != 0ull ? ((const AS_G int*)list)[job_tile] : job_tile * cfg[CFG_WORLD] + cfg[CFG_RANK];
+}
 // next_unit()'s result comes back in vector registers; it is the same in every lane, and reading it through readfirstlane tells the
 // compiler so (the unit's six words then live in scalar registers across pt_kernel's main loop: -3 ms on the 507 ms headline frame.  NOT in pt_kernel_coop: C4 888 -> 835 Msamples/s with it)
 __device__ __forceinline__ UnitInfo uniform_unit(const UnitInfo& v) {
@@ -1886,7 +1893,7 @@ __device__ __attribute__((noinline)) UnitInfo next_unit_pool(uint32_t* wst_, uin
             const int sub_i = L[1] + (round - L[0]);  // (single-unit jobs: a round is a unit)
             const uint64_t fm = __ballot(lane < ring_units && (rmeta[4 * lane + 2] & 0x100u) == 0u);
             const int slot = __ffsll((long long)fm) - 1;
-            const int tile = job_tile * cfg[CFG_WORLD] + cfg[CFG_RANK];
+            const int tile = job_image_tile(cfg, job_tile);
             u.tx = tile % cfg[CFG_TILES_X];
             u.ty = tile / cfg[CFG_TILES_X];
             u.s0 = L[2] + (sub_i - L[1]) * L[3];
@@ -1998,7 +2005,7 @@ __device__ __attribute__((noinline)) UnitInfo next_unit(uint32_t* wst_, uint32_t
             job_lvl |= (int)(list_cursor << 8);
         }
         if (job_k < job_n) {  // start the job's next unit
-            const int tile = job_tile * cfg[CFG_WORLD] + cfg[CFG_RANK];
+            const int tile = job_image_tile(cfg, job_tile);
             u.tx = tile % cfg[CFG_TILES_X];
             u.ty = tile / cfg[CFG_TILES_X];
             const int sub_i = job_blk0 + job_k;
@@ -2122,6 +2129,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
         cfg[CFG_JOB_LISTS] = 1;
 #pragma unroll
         for (int i = 0; i < 25; i++) cfg[CFG_LVL + i] = rk.lvl[i / 5][i % 5];
+        cfg[CFG_TILE_LIST] = (int)(uint32_t)(uintptr_t)rk.tile_list; cfg[CFG_TILE_LIST + 1] = (int)(uint32_t)((uint64_t)(uintptr_t)rk.tile_list >> 32);
     }
     if (GENERAL >= 2 && rk.time_slots) A.time_lds = (uint32_t)(uintptr_t)(AS_L char*)(cfg + CFG_WORDS);  // (8-aligned: every section before it is)
     __syncthreads();
@@ -3022,6 +3030,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel_coop(FlatView sv, CamK cam
         cfg[CFG_JOB_LISTS] = (int)JOB_LISTS;
 #pragma unroll
         for (int i = 0; i < 25; i++) cfg[CFG_LVL + i] = rk.lvl[i / 5][i % 5];
+        cfg[CFG_TILE_LIST] = (int)(uint32_t)(uintptr_t)rk.tile_list; cfg[CFG_TILE_LIST + 1] = (int)(uint32_t)((uint64_t)(uintptr_t)rk.tile_list >> 32);
         cargs->base = sv.base;
         cargs->pool = coop + (size_t)blockIdx.x * COOP_POOL * COOP_REC;
         cargs->err = err;
@@ -3875,6 +3884,7 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
                                           "larger than LDS, negative t_min, or camera farther than 64x the scene extent); use kernel 0/1");
     const size_t ring_meta = ((size_t)(PT_BLOCK / 64) * (RING_UNITS * 4 + 8) + CFG_WORDS) * sizeof(uint32_t);  // ring / job bookkeeping, behind the stacks
     const size_t stack_bytes = ((kernel == 2) ? stack2_bytes : (kernel == 5) ? stack5_bytes : 0) + ring_meta + ((kernel == 5) ? coop_lds : 0);
+    if (plan.tile_list && !plan.ext_accum) throw RtError(RT_ERR_INTERNAL, "a tile list needs the caller's (compact) accumulator");
     if (plan.ext_accum && (kernel == 6 || plan.integrator == 2))
         throw RtError(RT_ERR_UNSUPPORTED, "resumable rendering (rt_render_accumulate_device) runs with kernels 1 / 2 / 5 and integrators 0 / 1");
     if (kernel == 6) {
@@ -4005,6 +4015,7 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
         rk.time0 = plan.time0;
         rk.time1 = plan.time1;
         rk.time_slots = moving ? 1 : 0;
+        rk.tile_list = plan.tile_list;
         rk.n_top = n_top;
         rk.n_topq = n_topq;
         rk.coop_stack = (int)stack5;
@@ -4721,3 +4732,4 @@ void debug_hit_device(const rt_scene& s, int kernel, size_t n, const double* ray
 
 // rt_render_aov: the first-hit guide buffers of the denoiser
 #include "aov.inc"
+#include "adaptive.inc"

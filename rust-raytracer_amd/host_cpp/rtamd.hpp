@@ -473,6 +473,25 @@ class World {
         return aov;
     }
 
+    // Tile-adaptive sampling (rt_render_adaptive): every 8x8 tile gets acfg.min_spp samples, then doubles its count until
+    // its two-buffer error drops below acfg.threshold or it reaches cfg.sample_per_pixel (acfg NULL = rt_default_adaptive_config).
+    // Returns the linear radiance [height][width][3]; tile_spp (if given) receives each tile's final sample count, [tiles_y][tiles_x].
+    std::vector<double> render_adaptive(const Config& cfg, const rt_adaptive_config* acfg = nullptr, std::vector<int32_t>* tile_spp = nullptr,
+                                        int kernel = 0, rt_stats* stats = nullptr) const {
+        rt_params p;
+        rt_default_params(&p);
+        p.width = cfg.width; p.height = cfg.height; p.spp = cfg.sample_per_pixel; p.max_depth = cfg.max_depth;
+        p.t_min = cfg.t_min; p.seed = cfg.seed; p.integrator = cfg.integrator; p.kernel = kernel;
+        rt_adaptive_config c;
+        if (acfg) c = *acfg;
+        else rt_default_adaptive_config(&c);
+        std::vector<double> rad((size_t)cfg.width * cfg.height * 3);
+        std::vector<int32_t> spp((size_t)((cfg.width + 7) / 8) * ((cfg.height + 7) / 8));
+        check(rt_render_adaptive(s_, &cam.c, &p, &c, rad.data(), spp.data(), stats));
+        if (tile_spp) *tile_spp = std::move(spp);
+        return rad;
+    }
+
    private:
     rt_scene* s_ = nullptr;
 };

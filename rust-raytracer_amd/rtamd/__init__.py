@@ -69,6 +69,10 @@ class rt_denoise_config(C.Structure):
                 ("sigma_luma", C.c_double), ("eps", C.c_double), ("guides", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
+class rt_adaptive_config(C.Structure):
+    _fields_ = [("min_spp", C.c_int32), ("reserved", C.c_int32), ("threshold", C.c_double)]
+
+
 class rt_tuning(C.Structure):
     _fields_ = [("no_lds", C.c_int32), ("top_nodes", C.c_int32), ("sub_spp", C.c_int32), ("coop_pool", C.c_int32),
                 ("max_leaf", C.c_int32), ("sppm_photon_capacity", C.c_int32), ("sppm_knn_candidates", C.c_int32),
@@ -163,6 +167,9 @@ _SIGS = [
     ("rt_denoise", C.c_int, [C.POINTER(rt_denoise_config), C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp]),
     ("rt_denoise_device", C.c_int, [C.POINTER(rt_denoise_config), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
+    ("rt_default_adaptive_config", None, [C.POINTER(rt_adaptive_config)]),
+    ("rt_render_adaptive", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_adaptive_config), _dp,
+                                     C.POINTER(C.c_int32), C.POINTER(rt_stats)]),
     ("rt_render_tiles_device", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.c_void_p, C.c_void_p,
                                          C.POINTER(rt_stats)]),
     ("rt_render_sppm_tiles_device", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_sppm_config), C.c_void_p,
@@ -462,6 +469,25 @@ class World:
         st = rt_stats()
         _chk(self.L.rt_render(self.h, C.byref(camera.c), C.byref(p), out.ctypes.data_as(_dp), C.byref(st)))
         return out, st.as_dict()
+
+    def render_adaptive(self, camera, width, height, spp, min_spp=16, threshold=None, seed=1, kernel=0, integrator=0, max_depth=50,
+                        t_min=1e-3, device=-1, spp_chunk=0):
+        """rt_render_adaptive: tile-adaptive sampling.  Every 8x8 tile gets min_spp samples, then doubles its count until
+        its two-buffer error drops below `threshold` (None: the library's default) or it reaches spp.  Returns (radiance [H,W,3],
+        tile_spp int32 [tiles_y, tiles_x] = each tile's final sample count, stats dict)."""
+        p = default_params(width=width, height=height, spp=spp, max_depth=max_depth, t_min=t_min, seed=seed, kernel=kernel,
+                           integrator=integrator, device=device, spp_chunk=spp_chunk)
+        cfg = rt_adaptive_config()
+        self.L.rt_default_adaptive_config(C.byref(cfg))
+        cfg.min_spp = int(min_spp)
+        if threshold is not None:
+            cfg.threshold = float(threshold)
+        out = np.zeros((height, width, 3), dtype=np.float64)
+        tile_spp = np.zeros(((height + 7) // 8, (width + 7) // 8), dtype=np.int32)
+        st = rt_stats()
+        _chk(self.L.rt_render_adaptive(self.h, C.byref(camera.c), C.byref(p), C.byref(cfg), out.ctypes.data_as(_dp),
+                                       tile_spp.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(st)))
+        return out, tile_spp, st.as_dict()
 
     def render_multi(self, camera, devices=None, gpus=0, width=800, height=800, spp=256, max_depth=50, t_min=1e-3, seed=1, spp_chunk=0,
                      kernel=0, integrator=0, shutter=(0.0, 0.0)):

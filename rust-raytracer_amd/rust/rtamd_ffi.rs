@@ -140,6 +140,15 @@ pub struct rt_denoise_config {
     pub reserved: [i32; 5],
 }
 
+/// include/rtamd.h rt_adaptive_config (rt_default_adaptive_config fills it)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct rt_adaptive_config {
+    pub min_spp: i32,
+    pub reserved: i32,
+    pub threshold: c_double,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct rt_tuning {
@@ -268,6 +277,8 @@ extern "C" {
     pub fn rt_denoise(cfg: *const rt_denoise_config, width: i32, height: i32, rgb: *const c_double, variance: *const c_double, aov: *const c_double, out_rgb: *mut c_double, out_variance: *mut c_double) -> c_int;
     pub fn rt_denoise_device(cfg: *const rt_denoise_config, width: i32, height: i32, d_rgb: *const c_double, d_variance: *const c_double, d_aov: *const c_double, d_out_rgb: *mut c_double, d_out_variance: *mut c_double, hip_stream: *mut c_void) -> c_int;
     pub fn rt_render_sppm(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, cfg: *const rt_sppm_config, out_rgb: *mut c_double, stats_out: *mut c_double, photons_stored: *mut u64, stats: *mut rt_stats) -> c_int;
+    pub fn rt_default_adaptive_config(c: *mut rt_adaptive_config);
+    pub fn rt_render_adaptive(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, cfg: *const rt_adaptive_config, out_rgb: *mut c_double, out_tile_spp: *mut i32, stats: *mut rt_stats) -> c_int;
     pub fn rt_render_tiles_device(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, d_tiles: *mut c_double, hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
     pub fn rt_render_sppm_tiles_device(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, cfg: *const rt_sppm_config, d_tiles: *mut c_double, hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
     pub fn rt_render_accumulate_device(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, sample_begin: i32, sample_end: i32, d_accum: *mut c_double, hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
@@ -546,6 +557,22 @@ impl Scene {
         let mut st = rt_stats::default();
         check(unsafe { rt_render_accumulate(self.raw, cam, p, begin, end, state.as_mut_ptr(), &mut st) })?;
         Ok(st)
+    }
+    /// Tile-adaptive sampling: every 8x8 tile gets `cfg.min_spp` samples, then doubles its count until its two-buffer
+    /// error drops below `cfg.threshold` or it reaches `p.spp` (cfg None = rt_default_adaptive_config).  Returns the frame (sum / n_T per
+    /// tile), each tile's final sample count n_T ([tiles_y][tiles_x], row-major) and the statistics.
+    pub fn render_adaptive(&self, cam: &rt_camera, p: &rt_params, cfg: Option<&rt_adaptive_config>) -> Result<(Vec<f64>, Vec<i32>, rt_stats), RtError> {
+        let mut c = rt_adaptive_config::default();
+        match cfg {
+            Some(v) => c = *v,
+            None => unsafe { rt_default_adaptive_config(&mut c) },
+        }
+        let tiles = (((p.width.max(0) as usize) + 7) / 8) * (((p.height.max(0) as usize) + 7) / 8);
+        let mut out = vec![0.0f64; (p.width.max(0) as usize) * (p.height.max(0) as usize) * 3];
+        let mut tile_spp = vec![0i32; tiles];
+        let mut st = rt_stats::default();
+        check(unsafe { rt_render_adaptive(self.raw, cam, p, &c, out.as_mut_ptr(), tile_spp.as_mut_ptr(), &mut st) })?;
+        Ok((out, tile_spp, st))
     }
     pub fn finish_accumulated(p: &rt_params, state: &[f64]) -> Result<Vec<f64>, RtError> {
         let mut out = vec![0.0f64; (p.width as usize) * (p.height as usize) * 3];

@@ -206,8 +206,9 @@ int rt_object_xz_rect_light(rt_scene* s, double x0, double z0, double x1, double
  * `boundary` (any Hitable with a box, not itself a medium).  Its hit() draws a random number (medium.rs:37-38) from the path's
  * stream, in the reference's visit order: kernels 1 and 2 render such scenes with integrator 0, and rt_render_sppm* with all three
  * passes (a volume event is a pass-through interaction: no photon, no gather point); integrator 1, kernels 5 / 6, a medium inside a
- * medium's boundary and, under SPPM, a light inside a medium's boundary are refused with RT_ERR_UNSUPPORTED.  The logarithm is the
- * deterministic rtamd-ln-1 (csrc/common/detlog.h, < 1 ulp from libm). */
+ * medium's boundary and, under SPPM, a light inside a medium's boundary are refused with RT_ERR_UNSUPPORTED.  Under a background
+ * (rt_scene_set_background) such scenes render with kernels 1 and 2 and integrator 0; SPPM refuses every scene with a background.  The
+ * logarithm is the deterministic rtamd-ln-1 (csrc/common/detlog.h, < 1 ulp from libm). */
 int rt_object_constant_medium(rt_scene* s, double density, int boundary, int phase_material);
 /* objects/mesh.rs:149 Mesh::load_obj given parsed arrays: positions/normals n_vert*3, indices n_tri*3.
  * normals == NULL -> RT_ERR_NO_NORMALS unless synthesize_normals != 0 (area-weighted smooth normals). */
@@ -265,16 +266,48 @@ int rt_object_children(const rt_scene* s, int object, int capacity, int* out);  
 int rt_world_new(rt_scene* s, int n, const int* objects, uint64_t bvh_seed);
 /* World::new's `lights: Vec<Arc<dyn Light>>` (world.rs:18; scene.rs:110 passes the XZRectLight): the objects that the
  * mixture-pdf integrator samples.  Each must be a sphere or an XZ rectangle in world space (the reference's two Light
- * impls, light.rs:67-86,127-146); RT_ERR_UNSUPPORTED for lights under a Transform. */
+ * impls, light.rs:67-86,127-146); RT_ERR_UNSUPPORTED for lights under a Transform.  A background (rt_scene_set_background) is no
+ * light: integrator 1 reaches it by the BSDF and light-sampled directions of the mixture only, and rt_render_sppm* refuses a scene
+ * with one (the photon pass has no environment emitter). */
 int rt_scene_set_lights(rt_scene* s, int n, const int* objects);
 /* root = an existing object (e.g. the HitableList of a scene file) */
 int rt_scene_set_root(rt_scene* s, int object);
+/* ---- background (no reference counterpart: a miss ends sample_ray with what it has, photon_mapper.rs:335,364) ----
+ * What a ray that leaves the scene sees.  A ray that the segment loop traces and that hits nothing adds beta (x) B(d) to L (per
+ * channel: L_c + beta_c * B_c), then the path ends.  A hit at depth == 0 still ends the path without a background (Q12 unchanged).
+ * With u = unit(d) (the kernels' unit(): sqrt(sqlen) followed by a division), in f64 without contraction:
+ *   kind 0: none -- black, the default; the scene keeps the flattened blob and the fingerprint it had without this call.
+ *   kind 1: B = scale * color0, per channel.
+ *   kind 2: t = 0.5 * (u.y + 1.0), c = (1.0 - t) * color0 + t * color1, B = scale * c.  color0 is the colour straight down
+ *           (u.y = -1), color1 straight up; book 1's sky is color0 = (1, 1, 1), color1 = (0.5, 0.7, 1.0).
+ *   kind 3: B = scale * tex_color(texture, rec) with rec.p = u and (rec.u, rec.v) = Sphere::get_uv(u) (sphere.rs:16-20, the
+ *           deterministic acos / atan2 of D10): an ImageTexture is an equirectangular map with its top row up; checker and noise
+ *           textures work too.
+ * Set before rt_scene_commit, like every builder.  RT_ERR_ARG: a kind outside 0..3, a texture that is not one of this scene's for
+ * kind 3, a non-finite or negative colour component or scale, a call after commit.  The background is part of the flattened scene, so
+ * rt_scene_fingerprint tells scenes with different backgrounds apart.  It reaches every render entry point that runs kernels 1 / 2
+ * (rt_render, rt_render_camera_frame, rt_render_tiles_device, rt_render_accumulate(_device), rt_render_adaptive, rt_render_multi*)
+ * with integrators 0 and 1; kernels 5 / 6 requested explicitly and rt_render_sppm* are RT_ERR_UNSUPPORTED for a scene with a
+ * background (kind != 0), and the automatic choice is kernel 2 (kernel 1 without an accel).  rt_render_aov and rt_denoise are
+ * unchanged: their guides are first-hit data. */
+typedef struct rt_background {
+    int32_t kind;      /* 0 none (black, the default); 1 constant colour; 2 vertical gradient; 3 texture by direction */
+    int32_t texture;   /* kind 3: any texture id of this scene */
+    double color0[3];  /* kind 1: the colour; kind 2: the colour straight down (unit(d).y = -1) */
+    double color1[3];  /* kind 2: the colour straight up (unit(d).y = +1) */
+    double scale;      /* multiplies the colour; finite, >= 0 */
+} rt_background;
+int rt_scene_set_background(rt_scene* s, const rt_background* bg);
+int rt_scene_get_background(const rt_scene* s, rt_background* out);
 /* scene.rs:16-112 cornell_box_scene(): the reference's only built-in scene, numbers verbatim.
  * cube_obj_path = "data/mesh/cube.obj" of the reference. */
 int rt_scene_cornell_box(rt_scene* s, const char* cube_obj_path, double aspect_ratio, uint64_t bvh_seed, rt_camera* cam_out);
 /* data/<name>.json|.yaml loader (schema SURVEY.md sA.1; README.md:86-89 Track 5). File BVH topology is kept
  * verbatim, the redundant "bounding_box" is recomputed as BVHNode::construct does. Creates AND commits. */
 int rt_scene_load_file(const char* path, rt_scene** out, rt_camera* cam_out);
+/* The same scene as rt_scene_load_file, left UNcommitted: builders such as rt_scene_set_background or rt_scene_set_lights still apply,
+ * and rt_scene_commit then flattens it to the blob rt_scene_load_file would have made (with the additions). */
+int rt_scene_parse_file(const char* path, rt_scene** out, rt_camera* cam_out);
 /* flatten the graph into the linear device form (DFS pre-order program, SoA tables) */
 int rt_scene_commit(rt_scene* s);
 

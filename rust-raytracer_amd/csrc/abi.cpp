@@ -510,6 +510,27 @@ int rt_scene_set_lights(rt_scene* s, int n, const int* objects) {
         return (int)RT_OK;
     });
 }
+int rt_scene_set_background(rt_scene* s, const rt_background* bg) {
+    return guard([&] {
+        not_committed_only(s);
+        REQUIRE(bg, "null background");
+        REQUIRE(bg->kind >= 0 && bg->kind <= 3, "background kind must be 0 (none), 1 (constant), 2 (vertical gradient) or 3 (texture)");
+        bool ok = std::isfinite(bg->scale) && bg->scale >= 0.;
+        for (int c = 0; c < 3; c++) ok = ok && std::isfinite(bg->color0[c]) && bg->color0[c] >= 0. && std::isfinite(bg->color1[c]) && bg->color1[c] >= 0.;
+        REQUIRE(ok, "background colours and scale must be finite and >= 0");
+        if (bg->kind == 3)
+            REQUIRE(bg->texture >= 0 && bg->texture < (int)s->textures.size(), "background kind 3 needs a texture id of this scene");
+        s->background = *bg;
+        return (int)RT_OK;
+    });
+}
+int rt_scene_get_background(const rt_scene* s, rt_background* out) {
+    return guard([&] {
+        REQUIRE(s && out, "null argument");
+        *out = s->background;
+        return (int)RT_OK;
+    });
+}
 int rt_scene_set_root(rt_scene* s, int object) {
     return guard([&] {
         not_committed_only(s);
@@ -564,6 +585,13 @@ int rt_scene_load_file(const char* path, rt_scene** out, rt_camera* cam_out) {
     return guard([&] {
         REQUIRE(path && out, "null argument");
         *out = load_scene_file(path, cam_out);
+        return (int)RT_OK;
+    });
+}
+int rt_scene_parse_file(const char* path, rt_scene** out, rt_camera* cam_out) {
+    return guard([&] {
+        REQUIRE(path && out, "null argument");
+        *out = load_scene_file(path, cam_out, false);
         return (int)RT_OK;
     });
 }

@@ -82,6 +82,13 @@ struct MatDev {   // material.rs:88-212 (+ :213-231, the commented-out Isotropic
     double r0_front;    // ((1 - 1/ir) / (1 + 1/ir))^2                reflectance, material.rs:150-153
     double r0_back;     // ((1 - ir) / (1 + ir))^2
 };
+struct BgDev {    // rt_background of a scene whose kind is 1..3 (no reference counterpart: DESIGN.md s4g)
+    int32_t kind;          // 1 constant, 2 vertical gradient, 3 texture by direction
+    int32_t tex;           // kind 3
+    double c0[3], c1[3];   // kind 1: c0; kind 2: down (c0) / up (c1)
+    double scale;
+};
+static_assert(sizeof(BgDev) == 64, "BgDev: 64 bytes in the blob");
 struct TexDev {   // material.rs:48-84
     int32_t type;  // 0 Constant, 1 Checker, 2 Image, 3 Noise (D9: Perlin marble, book 2)
     int32_t t0, t1;        // Checker: constant-texture ids (.0 when sines < 0, .1 otherwise)
@@ -168,6 +175,8 @@ struct FlatView {  // by-value kernel argument
     uint32_t off_qgrid;          // QGrid per instance
     uint32_t world_top2;         // world-space BVH nodes all have an index below this (the Node2 array is depth-sorted)
     uint32_t world_depth2;       // depth of the world-space BVH (kernel 5 walks it and the object-space BVHs separately)
+    // cold part: the scene's background (rt_scene_set_background), one BgDev; 0 = none (kind 0: the blob is unchanged)
+    uint32_t off_bg;
 };
 
 // ---------------------------------------------------------------------------

@@ -1376,6 +1376,31 @@ DEV void sphere_uv(D3 outward, double& u, double& v) {  // get_uv, sphere.rs:16-
     u = phi * FRAC_1_PI * 0.5;
     v = theta * FRAC_1_PI;
 }
+// Background (no reference counterpart): B(d) of a ray that hit nothing, in the order rtamd.h pins.  Only the
+// background variants (INTEG & INTEG_BG) call it, once per path at most; out of line: inlined it ran no faster and spilled more
+// registers in most variants.  The record and the textures stay in global memory.
+template <int GENERAL>
+__device__ __attribute__((noinline)) D3 background_radiance(const BgDev* __restrict__ bg, const TexDev* texs, const uint8_t* texels, D3 d, int* err) {
+    const D3 u = unit(d, err);
+    const int kind = bg->kind;
+    D3 c;
+    if (kind == 1) {
+        c = mk(bg->c0[0], bg->c0[1], bg->c0[2]);
+    } else if (kind == 2) {  // book 1's ray_color: t = 0.5 (unit(d).y + 1), (1 - t) * down + t * up
+        const double t = 0.5 * (u.y + 1.0);
+        c = add(muls(mk(bg->c0[0], bg->c0[1], bg->c0[2]), 1.0 - t), muls(mk(bg->c1[0], bg->c1[1], bg->c1[2]), t));
+    } else {  // the texture read on the unit sphere of directions: p = u, uv = Sphere::get_uv(u)
+        Acc a;
+        a.texs = texs;
+        a.texels = texels;
+        Rec rec;
+        rec.p = u;
+        sphere_uv(u, rec.u, rec.v);
+        c = tex_color<GENERAL>(a, bg->tex, rec);
+    }
+    const double sc = bg->scale;
+    return mk(sc * c.x, sc * c.y, sc * c.z);
+}
 // Build the HitRecord of the winning leaf only (the reference builds one per candidate).  uv is computed only where an ImageTexture
 // reads it, unless ALL_UV (the closest-hit diagnostic, which returns the whole record).
 template <int GENERAL, bool ALL_UV = false>
@@ -2045,6 +2070,9 @@ __device__ __attribute__((noinline)) UnitInfo next_unit(uint32_t* wst_, uint32_t
 #ifndef RT_SLICE_TH
 #define RT_SLICE_TH 0
 #endif
+// INTEG & INTEG_BG: the background variants of integrator INTEG & 3 -- a value of the INTEG axis rather than a template
+// parameter of its own, so that every kernel without a background keeps its name (and its code)
+static constexpr int INTEG_BG = 4;
 template <bool LDS, int GENERAL, int ACCEL, int INTEG, bool MEDIA = false, bool POOL = false>
 __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, RenderK rk, double* __restrict__ ring, double* accum,
                                                       unsigned int* tickets, unsigned int* __restrict__ counter, int* __restrict__ err) {
@@ -2275,12 +2303,12 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
                     L = add(L, elemul(beta, emitted));  // radiance += throughput * Le
                     if (scattered) {  // Diffuse continues like Specular/Reflect/Refract (photon_mapper.rs:346-347)
                         bool go = true;
-                        if (INTEG == 2 && diffuse) {
+                        if ((INTEG & 3) == 2 && diffuse) {
                             const double* e = rk.sppm_est + 6 * (size_t)pix_id;
                             L = add(L, elemul(beta, mk(e[0], e[1], e[2])));  // caustic estimate
                             L = add(L, elemul(beta, mk(e[3], e[4], e[5])));  // global estimate
                             go = false;
-                        } else if (INTEG == 1 && diffuse) {
+                        } else if ((INTEG & 3) == 1 && diffuse) {
                             PH_EV(14);
                             go = mixture_step(A, rec, rng, att, beta, ndir, err);
                         } else {
@@ -2292,6 +2320,8 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
                             done = false;
                         }
                     }
+                } else if ((INTEG & INTEG_BG) && h.node < 0) {  // a miss sees the background: L += beta (x) B(d), then the path ends
+                    L = add(L, elemul(beta, background_radiance<GENERAL>((const BgDev*)(sv.base + sv.off_bg), A.texs, A.texels, d, err)));
                 }
                 if (done) {
                     double* dst = wring + 3 * (size_t)out_slot;
@@ -3790,6 +3820,16 @@ static pt_fn pick_pt_kernel_pool(bool lds, bool general, int integ) {
     return lds ? (general ? pt_kernel<true, true, 2, 0, false, true> : pt_kernel<true, false, 2, 0, false, true>)
                : (general ? pt_kernel<false, true, 2, 0, false, true> : pt_kernel<false, false, 2, 0, false, true>);
 }
+// the background variants (INTEG | INTEG_BG) of kernels 1 and 2: integrators 0 and 1 on the same GENERAL / MEDIA choices as
+// without a background (g: 0 spheres only, 1 general, 2 book 2, 3 nested chains; integrator 1 runs on g >= 1, MEDIA with integrator 0 only)
+template <int ACCEL, bool LDS>
+static pt_fn pick_pt_kernel_bg(int g, bool media, int integ) {
+    constexpr int B = INTEG_BG;
+    if (g == 0) return pt_kernel<LDS, 0, ACCEL, B>;
+    if (g == 1) return media ? pt_kernel<LDS, 1, ACCEL, B, true> : (integ == 1) ? pt_kernel<LDS, 1, ACCEL, B | 1> : pt_kernel<LDS, 1, ACCEL, B>;
+    if (g == 2) return media ? pt_kernel<LDS, 2, ACCEL, B, true> : pt_kernel<LDS, 2, ACCEL, B>;
+    return media ? pt_kernel<LDS, 3, ACCEL, B, true> : (integ == 1) ? pt_kernel<LDS, 3, ACCEL, B | 1> : pt_kernel<LDS, 3, ACCEL, B>;
+}
 
 static void render_tiles_wf(const rt_scene& s, const FlatView& view, const CameraDev& cam, const RenderPlan& plan, const Tuning& tun, double* d_tiles,
                             hipStream_t stream, rt_stats* st, int dev, const DevInfo& di, uint32_t stack6, uint32_t n_entry6, size_t lds_pt, uint32_t stack6w,
@@ -3867,12 +3907,19 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
     const size_t wf_lds_walk_min = wf_tables_w + (size_t)stack6w * WF_WALK_BLOCK * sizeof(uint32_t);
     const bool wf_usable = accel2_usable && general && !media && !book2 && view.coop_data_ok != 0 && view.n_inst2 >= 1 && view.n_inst2 <= (uint32_t)WF_MAX_INST &&
                            coop_world <= 32768 && wf_lds_pt <= lds_max && wf_lds_walk_min <= lds_max && plan.max_depth < (1 << 24);
+    // a background (rt_scene_set_background): kernels 1 and 2 only (kernels 5 / 6 have no background variants), never the SPPM pass
+    const bool bg = view.off_bg != 0u;
     int kernel = plan.kernel;
+    if (bg && (kernel == 5 || kernel == 6))
+        throw RtError(RT_ERR_UNSUPPORTED, "kernels 5 / 6 have no background variant: a scene with a background renders with kernel 1 or 2 (kernel 0 picks one)");
+    if (bg && plan.integrator == 2) throw RtError(RT_ERR_UNSUPPORTED, "the SPPM integrator has no background (the photon pass has no environment emitter)");
     // auto: the cooperative kernel as soon as an instance is more than a handful of triangles (Cornell box + torus instance, 64 spp,
     // kernel 5 / kernel 2 in Msamples/s: 120 triangles 1351 / 1182 (kernel 2 LDS-resident), 1 600: 1263 / 822, 25 600: 1035 / 517,
     // 102 400: 861 / 427, 409 600: 746 / 370; the 12-triangle cube of the reference's Cornell box: 2507 / 2533)
     // (kernel 6, the wavefront form of the same service, reaches 766 Msamples/s on C4 where kernel 5 reaches 891 and kernel 2 469: it is
     // since round 4 kernel 5 takes up to 64 instances too, so kernel 6 runs by request only)
+    if (kernel == 0 && bg)
+        kernel = accel2_usable ? 2 : 1;
     if (kernel == 0)
         kernel = accel2_usable ? ((coop_usable && view.max_inst_nodes2 >= 64u) ? 5 : (wf_usable && !coop_usable && view.max_inst_nodes2 >= 64u) ? 6 : 2) : 1;
     if (kernel == 5 && !coop_usable)
@@ -3937,6 +3984,11 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
         else
             throw RtError(RT_ERR_INTERNAL, "nested Transforms reached kernel " + std::to_string(kernel));
     }
+    if (bg) {
+        const int g = nest ? 3 : book2 ? 2 : (general || integ == 1) ? 1 : 0;
+        fn = (kernel == 2) ? (lds ? pick_pt_kernel_bg<2, true>(g, media, integ) : pick_pt_kernel_bg<2, false>(g, media, integ))
+                           : (lds ? pick_pt_kernel_bg<1, true>(g, media, integ) : pick_pt_kernel_bg<1, false>(g, media, integ));
+    }
     // scene too large for LDS: spend what is left after the stacks on the shallowest BVH levels (the Node2 array is depth-sorted)
     int n_top = 0, n_topq = 0;
     if (kernel == 2 && !lds && lds_max > stack_bytes) {
@@ -3962,7 +4014,7 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
     const int grid = di.cus * blocks_per_cu;
     // a rank that owns fewer tiles than the launch has waves: single-unit jobs (below) folded out of order (next_unit_pool)
     const bool pool = POOL_MODE && SINGLE_UNITS_BELOW_WAVES && plan.tiles_owned < (int64_t)grid * (PT_BLOCK / 64) &&
-                      ((kernel == 2 && !media && !book2 && !nest) || (kernel == 5 && fn_coop == fn_coop_early));
+                      ((kernel == 2 && !media && !book2 && !nest && !bg) || (kernel == 5 && fn_coop == fn_coop_early));
     if (pool && kernel == 2) {
         fn = pick_pt_kernel_pool(lds, general, integ);  // (same resources as the variant the occupancy was asked for)
         if (smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
@@ -4430,6 +4482,8 @@ void render_sppm(const rt_scene& s, const CameraDev& cam, RenderPlan plan, const
                  void* stream_, rt_stats* st, uint64_t* totals2) {
     if (!s.committed) throw RtError(RT_ERR_NOT_COMMITTED, "scene not committed");
     const Tuning tun = tuning();  // one snapshot per call
+    if (s.flat.view.off_bg != 0u)
+        throw RtError(RT_ERR_UNSUPPORTED, "SPPM does not render a scene with a background: the photon pass has no environment emitter (DESIGN.md s4g)");
     if (s.lights.empty()) throw RtError(RT_ERR_ARG, "SPPM needs lights (rt_scene_set_lights)");
     if (s.flat.view.n_msph != 0u || s.flat.view.has_noise != 0u || plan.time1 > plan.time0)
         throw RtError(RT_ERR_UNSUPPORTED, "the photon passes have no notion of time: the book-2 extensions (moving spheres, noise textures, an open shutter) render with integrator 0");

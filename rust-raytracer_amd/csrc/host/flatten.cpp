@@ -785,6 +785,18 @@ void flatten(rt_scene& s) {
     v.off_vpos = append(f.blob, b.vpos);  // kept for introspection; the kernels read tripre instead
     v.off_vnrm = append(f.blob, b.vnrm);
     v.off_texels = append(f.blob, texels);
+    v.off_bg = 0u;
+    if (s.background.kind != 0) {  // a scene without a background keeps its blob (and its fingerprint) byte for byte
+        BgDev bg{};
+        bg.kind = s.background.kind;
+        bg.tex = s.background.kind == 3 ? s.background.texture : 0;
+        for (int c = 0; c < 3; c++) {
+            bg.c0[c] = s.background.color0[c];
+            bg.c1[c] = s.background.color1[c];
+        }
+        bg.scale = s.background.scale;
+        v.off_bg = append(f.blob, std::vector<BgDev>{bg});
+    }
     f.blob.resize((f.blob.size() + 15) & ~size_t(15));
     v.total_bytes = (uint32_t)f.blob.size();
     v.n_nodes = (uint32_t)(b.meta.size() / 2);

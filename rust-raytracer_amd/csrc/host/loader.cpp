@@ -462,7 +462,7 @@ int build_object(rt_scene& s, const Value& d, int depth) {
 
 }  // namespace
 
-rt_scene* load_scene_file(const char* path, rt_camera* cam) {
+rt_scene* load_scene_file(const char* path, rt_camera* cam, bool commit) {
     std::ifstream f(path, std::ios::binary);
     if (!f) throw RtError(RT_ERR_IO, std::string("cannot open scene file ") + path);
     std::stringstream ss;
@@ -504,7 +504,7 @@ rt_scene* load_scene_file(const char* path, rt_camera* cam) {
         cam->aperture = num(c, "aperture", "camera");
         cam->focus_dist = num(c, "focus_dist", "camera");
     }
-    flatten(*s);
+    if (commit) flatten(*s);
     return s.release();
 }
 

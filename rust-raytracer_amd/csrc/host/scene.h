@@ -89,6 +89,7 @@ struct rt_scene {
     std::vector<std::unique_ptr<rtamd::MeshData>> meshes;
     int root = -1;
     std::vector<int> lights;  // World::new's lights (object ids)
+    rt_background background{};  // rt_scene_set_background; kind 0 = none (flattened only when kind != 0: DESIGN.md s4g)
     bool committed = false;
     rtamd::FlatScene flat;
     // device copies of the blob, one per HIP device, created lazily by the render entry points
@@ -133,7 +134,7 @@ bool bounding_box(const rt_scene& s, int o, Box& out);
 // flatten.cpp
 void flatten(rt_scene& s);
 // loader.cpp
-rt_scene* load_scene_file(const char* path, rt_camera* cam);
+rt_scene* load_scene_file(const char* path, rt_camera* cam, bool commit = true);
 // obj.cpp
 struct ObjMesh {
     std::vector<double> pos, nrm;

@@ -3,10 +3,12 @@
 // and the same "Total / RT" timing print.  Also renders the reference's scene files.
 //   rtamd_render [--scene cornell|FILE.json|FILE.yaml] [--cube data/mesh/cube.obj] [-w W] [-h H] [--spp N]
 //                [--depth D] [--seed S] [--aspect A] [--integrator 0|1] [--sppm ITERATIONS PHOTONS_PER_ITER]
-//                [--gpus N | --devices 0,1,...] [-o out.png] [--describe] [--vec3-selftest]
+//                [--gpus N | --devices 0,1,...] [--background r,g,b | --sky] [-o out.png] [--describe] [--vec3-selftest]
 // --gpus N spreads the frame over N GPUs of this node inside ONE capture_image call (rt_render_multi: tiles dealt round-robin, RCCL
 // gather; 0 = all visible); --devices names the HIP ordinal of every rank (an ordinal may repeat).
 // `rtamd_render --cube data/mesh/cube.obj --sppm 50 500000` is the reference binary: SPPM pre-pass + 256 spp, output/test.png
+// --background r,g,b gives rays that leave the scene a constant colour, --sky book 1's sky gradient (rt_scene_set_background; the
+// reference has neither: its misses are black)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -49,6 +51,7 @@ int main(int argc, char** argv) {
     bool describe = false;
     std::string checkpoint;  // --checkpoint FILE [--run-samples K]: trace the next K samples per pixel into the state in FILE; the image is written once all are in
     int run_samples = 64;
+    rt_background bg{};  // kind 0: none
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -70,6 +73,12 @@ int main(int argc, char** argv) {
                 else if (*q) { std::fprintf(stderr, "--devices wants a comma-separated list of ordinals\n"); return 2; }
             }
         }
+        else if (a == "--sky") bg = World::background_sky();
+        else if (a == "--background") {
+            double c[3];
+            if (std::sscanf(next(), "%lf,%lf,%lf", &c[0], &c[1], &c[2]) != 3) { std::fprintf(stderr, "--background wants r,g,b\n"); return 2; }
+            bg = World::background_color(c[0], c[1], c[2]);
+        }
         else if (a == "-o") out = next();
         else if (a == "--checkpoint") { checkpoint = next(); }
         else if (a == "--run-samples") run_samples = std::atoi(next());
@@ -81,9 +90,9 @@ int main(int argc, char** argv) {
         auto start_time = std::chrono::steady_clock::now();
         std::unique_ptr<World> world;
         if (scene == "cornell") {
-            world = cornell_box_scene(cube, aspect > 0 ? aspect : (double)cfg.width / cfg.height);
+            world = cornell_box_scene(cube, aspect > 0 ? aspect : (double)cfg.width / cfg.height, 1, bg.kind ? &bg : nullptr);
         } else {
-            world = std::make_unique<World>(scene);
+            world = std::make_unique<World>(scene, bg.kind ? &bg : nullptr);
             if (aspect > 0) world->cam.c.aspect = aspect;
         }
         rt_scene_info info;

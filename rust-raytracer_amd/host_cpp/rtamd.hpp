@@ -336,7 +336,9 @@ struct Config {
 class World {
    public:
     Camera cam;
-    World(const HitableList& hitable_list, Camera camera, const HitableList& lights = {}, uint64_t bvh_seed = 1) : cam(camera) {
+    // bg: rt_scene_set_background before the commit (nullptr: none, the reference's black)
+    World(const HitableList& hitable_list, Camera camera, const HitableList& lights = {}, uint64_t bvh_seed = 1, const rt_background* bg = nullptr)
+        : cam(camera) {
         check(rt_scene_create(&s_));
         try {
             Emitter e(s_, bvh_seed);
@@ -345,6 +347,7 @@ class World {
             for (auto& l : lights) lids.push_back(e.once(l.get()));  // a light shared with the hitable list is emitted once
             check(rt_world_new(s_, (int)ids.size(), ids.data(), bvh_seed));
             if (!lids.empty()) check(rt_scene_set_lights(s_, (int)lids.size(), lids.data()));
+            if (bg) check(rt_scene_set_background(s_, bg));
             check(rt_scene_commit(s_));
         } catch (...) {
             rt_scene_destroy(s_);
@@ -352,8 +355,40 @@ class World {
         }
     }
     // a scene file of the reference's data/ directory (README.md Track 5)
-    explicit World(const std::string& scene_file) {
-        check(rt_scene_load_file(scene_file.c_str(), &s_, &cam.c));
+    explicit World(const std::string& scene_file, const rt_background* bg = nullptr) {
+        if (!bg) {
+            check(rt_scene_load_file(scene_file.c_str(), &s_, &cam.c));
+            return;
+        }
+        check(rt_scene_parse_file(scene_file.c_str(), &s_, &cam.c));  // uncommitted: the background is a builder
+        const int rc = rt_scene_set_background(s_, bg);
+        const int rc2 = rc < 0 ? rc : rt_scene_commit(s_);
+        if (rc2 < 0) {
+            const std::string msg = rt_last_error();
+            rt_scene_destroy(s_);
+            throw Error(rc2, msg);
+        }
+    }
+    // rt_background helpers: a constant colour (kind 1) and book 1's sky (kind 2: white straight down, (0.5, 0.7, 1.0) straight up)
+    static rt_background background_color(double r, double g, double b, double scale = 1.0) {
+        rt_background bg{};
+        bg.kind = 1;
+        bg.color0[0] = r; bg.color0[1] = g; bg.color0[2] = b;
+        bg.scale = scale;
+        return bg;
+    }
+    static rt_background background_sky(double scale = 1.0) {
+        rt_background bg{};
+        bg.kind = 2;
+        bg.color0[0] = 1.0; bg.color0[1] = 1.0; bg.color0[2] = 1.0;
+        bg.color1[0] = 0.5; bg.color1[1] = 0.7; bg.color1[2] = 1.0;
+        bg.scale = scale;
+        return bg;
+    }
+    rt_background background() const {
+        rt_background bg{};
+        check(rt_scene_get_background(s_, &bg));
+        return bg;
     }
     ~World() { rt_scene_destroy(s_); }
     World(const World&) = delete;
@@ -513,7 +548,8 @@ inline std::vector<double> denoise(int width, int height, const std::vector<doub
 }
 
 // scene.rs:16-112 cornell_box_scene(), written against the mirrored types exactly as the reference writes it
-inline std::unique_ptr<World> cornell_box_scene(const std::string& cube_obj, double aspect_ratio = 1.0, uint64_t bvh_seed = 1) {
+inline std::unique_ptr<World> cornell_box_scene(const std::string& cube_obj, double aspect_ratio = 1.0, uint64_t bvh_seed = 1,
+                                                const rt_background* bg = nullptr) {
     auto tex = [](double r, double g, double b) { return std::make_shared<ConstantTexture>(Vec3(r, g, b)); };
     MaterialPtr red = std::make_shared<Lambertian>(tex(0.75, 0.25, 0.25));
     MaterialPtr white = std::make_shared<Lambertian>(tex(0.75, 0.75, 0.75));
@@ -532,7 +568,7 @@ inline std::unique_ptr<World> cornell_box_scene(const std::string& cube_obj, dou
         std::make_shared<Cube>(Vec3(300., 0., 100.), Vec3(380., 100., 180.), white),
     };
     Camera cam({Vec3(278., 278., -800.), Vec3(278., 278., 278.)}, Vec3(0., 1., 0.), 50., aspect_ratio, 0.0, 10.0);
-    return std::make_unique<World>(hitable_list, cam, HitableList{light}, bvh_seed);  // scene.rs:100-111: lights = vec![light]
+    return std::make_unique<World>(hitable_list, cam, HitableList{light}, bvh_seed, bg);  // scene.rs:100-111: lights = vec![light]
 }
 
 }  // namespace rtamd_host

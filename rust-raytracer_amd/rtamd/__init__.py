@@ -73,6 +73,14 @@ class rt_adaptive_config(C.Structure):
     _fields_ = [("min_spp", C.c_int32), ("reserved", C.c_int32), ("threshold", C.c_double)]
 
 
+class rt_background(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("texture", C.c_int32), ("color0", C.c_double * 3), ("color1", C.c_double * 3), ("scale", C.c_double)]
+
+
+BACKGROUND_KINDS = ("none", "constant", "gradient", "texture")
+SKY = ((1.0, 1.0, 1.0), (0.5, 0.7, 1.0))  # book 1's ray_color: white straight down, (0.5, 0.7, 1.0) straight up
+
+
 class rt_tuning(C.Structure):
     _fields_ = [("no_lds", C.c_int32), ("top_nodes", C.c_int32), ("sub_spp", C.c_int32), ("coop_pool", C.c_int32),
                 ("max_leaf", C.c_int32), ("sppm_photon_capacity", C.c_int32), ("sppm_knn_candidates", C.c_int32),
@@ -144,8 +152,11 @@ _SIGS = [
     ("rt_world_new", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_uint64]),
     ("rt_scene_set_root", C.c_int, [C.c_void_p, C.c_int]),
     ("rt_scene_set_lights", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    ("rt_scene_set_background", C.c_int, [C.c_void_p, C.POINTER(rt_background)]),
+    ("rt_scene_get_background", C.c_int, [C.c_void_p, C.POINTER(rt_background)]),
     ("rt_scene_cornell_box", C.c_int, [C.c_void_p, C.c_char_p, C.c_double, C.c_uint64, C.POINTER(rt_camera)]),
     ("rt_scene_load_file", C.c_int, [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(rt_camera)]),
+    ("rt_scene_parse_file", C.c_int, [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(rt_camera)]),
     ("rt_scene_commit", C.c_int, [C.c_void_p]),
     ("rt_scene_info_get", C.c_int, [C.c_void_p, C.POINTER(rt_scene_info)]),
     ("rt_scene_fingerprint", C.c_uint64, [C.c_void_p]),
@@ -446,6 +457,39 @@ class World:
         arr = (C.c_int * len(lights))(*lights)
         _chk(self.L.rt_scene_set_lights(self.h, len(lights), arr))
 
+    def set_background(self, color=None, gradient=None, texture=None, scale=1.0):
+        """rt_scene_set_background (before commit): at most one of color=(r, g, b) (kind 1), gradient=((down), (up)) (kind 2) or
+        texture=<texture id> (kind 3, sampled by direction; an ImageTexture is an equirectangular map).  None of them: no background."""
+        if sum(x is not None for x in (color, gradient, texture)) > 1:
+            raise ValueError("set_background takes one of color, gradient, texture")
+        bg = rt_background()
+        bg.scale = float(scale)
+        if color is not None:
+            bg.kind = 1
+            bg.color0 = _arr3(color)
+        elif gradient is not None:
+            bg.kind = 2
+            bg.color0 = _arr3(gradient[0])
+            bg.color1 = _arr3(gradient[1])
+        elif texture is not None:
+            bg.kind = 3
+            bg.texture = int(texture)
+        _chk(self.L.rt_scene_set_background(self.h, C.byref(bg)))
+        return self
+
+    def set_sky(self, scale=1.0):
+        """book 1's sky: the vertical gradient from white (straight down) to (0.5, 0.7, 1.0) (straight up)"""
+        return self.set_background(gradient=SKY, scale=scale)
+
+    def background(self):
+        """rt_scene_get_background: dict(kind, texture, color0, color1, scale)"""
+        bg = rt_background()
+        _chk(self.L.rt_scene_get_background(self.h, C.byref(bg)))
+        return dict(kind=bg.kind, texture=bg.texture, color0=tuple(bg.color0), color1=tuple(bg.color1), scale=bg.scale)
+
+    def fingerprint(self):
+        return int(self.L.rt_scene_fingerprint(self.h))
+
     def set_root(self, obj):
         _chk(self.L.rt_scene_set_root(self.h, obj))
         return self.commit()
@@ -641,21 +685,24 @@ class World:
         return out
 
 
-def load_scene_file(path):
-    """rt_scene_load_file: returns (World, Camera) for data/<name>.json|.yaml."""
+def load_scene_file(path, commit=True):
+    """rt_scene_load_file: returns (World, Camera) for data/<name>.json|.yaml.  commit=False: rt_scene_parse_file, the same scene left
+    uncommitted (set a background or lights, then World.commit())."""
     L = lib()
     h = C.c_void_p()
     cam = rt_camera()
-    _chk(L.rt_scene_load_file(os.fsencode(path), C.byref(h), C.byref(cam)))
+    fn = L.rt_scene_load_file if commit else L.rt_scene_parse_file
+    _chk(fn(os.fsencode(path), C.byref(h), C.byref(cam)))
     return World(h), Camera.from_struct(cam)
 
 
-def select_scene(cube_obj_path, aspect_ratio=1.0, bvh_seed=1):
-    """scene.rs:114-116 select_scene(_index) == cornell_box_scene(): returns (World, Camera)."""
+def select_scene(cube_obj_path, aspect_ratio=1.0, bvh_seed=1, commit=True):
+    """scene.rs:114-116 select_scene(_index) == cornell_box_scene(): returns (World, Camera); commit=False leaves it uncommitted."""
     w = World()
     cam = rt_camera()
     _chk(w.L.rt_scene_cornell_box(w.h, os.fsencode(cube_obj_path), float(aspect_ratio), int(bvh_seed), C.byref(cam)))
-    w.commit()
+    if commit:
+        w.commit()
     return w, Camera.from_struct(cam)
 
 

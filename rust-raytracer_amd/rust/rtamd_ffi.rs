@@ -140,6 +140,17 @@ pub struct rt_denoise_config {
     pub reserved: [i32; 5],
 }
 
+/// include/rtamd.h rt_background (rt_scene_set_background; kind 0 = none, the default)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct rt_background {
+    pub kind: i32,
+    pub texture: i32,
+    pub color0: [c_double; 3],
+    pub color1: [c_double; 3],
+    pub scale: c_double,
+}
+
 /// include/rtamd.h rt_adaptive_config (rt_default_adaptive_config fills it)
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -257,8 +268,11 @@ extern "C" {
     pub fn rt_world_new(s: *mut rt_scene, n: c_int, objects: *const c_int, bvh_seed: u64) -> c_int;
     pub fn rt_scene_set_lights(s: *mut rt_scene, n: c_int, objects: *const c_int) -> c_int;
     pub fn rt_scene_set_root(s: *mut rt_scene, object: c_int) -> c_int;
+    pub fn rt_scene_set_background(s: *mut rt_scene, bg: *const rt_background) -> c_int;
+    pub fn rt_scene_get_background(s: *const rt_scene, out: *mut rt_background) -> c_int;
     pub fn rt_scene_cornell_box(s: *mut rt_scene, cube_obj_path: *const c_char, aspect_ratio: c_double, bvh_seed: u64, cam_out: *mut rt_camera) -> c_int;
     pub fn rt_scene_load_file(path: *const c_char, out: *mut *mut rt_scene, cam_out: *mut rt_camera) -> c_int;
+    pub fn rt_scene_parse_file(path: *const c_char, out: *mut *mut rt_scene, cam_out: *mut rt_camera) -> c_int;
     pub fn rt_scene_commit(s: *mut rt_scene) -> c_int;
     pub fn rt_scene_info_get(s: *const rt_scene, out: *mut rt_scene_info) -> c_int;
     pub fn rt_scene_fingerprint(s: *const rt_scene) -> u64;
@@ -472,6 +486,22 @@ impl SceneBuilder {
     pub fn set_lights(&mut self, lights: &[Id]) -> Result<(), RtError> {
         check(unsafe { rt_scene_set_lights(self.raw, lights.len() as c_int, lights.as_ptr()) }).map(|_| ())
     }
+    /// rt_scene_set_background: what a ray that leaves the scene sees (before commit)
+    pub fn set_background(&mut self, bg: &rt_background) -> Result<(), RtError> {
+        check(unsafe { rt_scene_set_background(self.raw, bg) }).map(|_| ())
+    }
+    /// book 1's sky: the vertical gradient from white (straight down) to (0.5, 0.7, 1.0) (straight up)
+    pub fn set_sky(&mut self) -> Result<(), RtError> {
+        self.set_background(&rt_background { kind: 2, texture: 0, color0: [1.0, 1.0, 1.0], color1: [0.5, 0.7, 1.0], scale: 1.0 })
+    }
+    /// rt_scene_parse_file: a scene file's graph, left uncommitted (a background or lights may still be set)
+    pub fn parse_file(path: &str) -> Result<(SceneBuilder, rt_camera), RtError> {
+        let c = CString::new(path).unwrap();
+        let mut raw: *mut rt_scene = std::ptr::null_mut();
+        let mut cam = rt_camera::default();
+        check(unsafe { rt_scene_parse_file(c.as_ptr(), &mut raw, &mut cam) })?;
+        Ok((Self { raw, seen: HashMap::new(), meshes: HashMap::new() }, cam))
+    }
     pub fn commit(self) -> Result<Scene, RtError> {
         check(unsafe { rt_scene_commit(self.raw) })?;
         let raw = self.raw;
@@ -503,6 +533,11 @@ impl Scene {
         let mut cam = rt_camera::default();
         check(unsafe { rt_scene_load_file(c.as_ptr(), &mut raw, &mut cam) })?;
         Ok((Scene { raw }, cam))
+    }
+    pub fn background(&self) -> Result<rt_background, RtError> {
+        let mut b = rt_background::default();
+        check(unsafe { rt_scene_get_background(self.raw, &mut b) })?;
+        Ok(b)
     }
     pub fn info(&self) -> Result<rt_scene_info, RtError> {
         let mut i = rt_scene_info::default();

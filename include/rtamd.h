@@ -266,9 +266,11 @@ int rt_object_children(const rt_scene* s, int object, int capacity, int* out);  
 int rt_world_new(rt_scene* s, int n, const int* objects, uint64_t bvh_seed);
 /* World::new's `lights: Vec<Arc<dyn Light>>` (world.rs:18; scene.rs:110 passes the XZRectLight): the objects that the
  * mixture-pdf integrator samples.  Each must be a sphere or an XZ rectangle in world space (the reference's two Light
- * impls, light.rs:67-86,127-146); RT_ERR_UNSUPPORTED for lights under a Transform.  A background (rt_scene_set_background) is no
- * light: integrator 1 reaches it by the BSDF and light-sampled directions of the mixture only, and rt_render_sppm* refuses a scene
- * with one (the photon pass has no environment emitter). */
+ * impls, light.rs:67-86,127-146); RT_ERR_UNSUPPORTED for lights under a Transform.  A background (rt_scene_set_background) is a
+ * light of integrator 1 only where the scene switched env sampling on (rt_scene_set_env_sampling below): then it is one more strategy
+ * of the light half of the mixture, and a scene lit by nothing else needs no object lights.  Without that switch integrator 1 reaches
+ * the background by the BSDF and light-sampled directions of the mixture only.  rt_render_sppm* refuses a scene with a background
+ * either way (the photon pass has no environment emitter). */
 int rt_scene_set_lights(rt_scene* s, int n, const int* objects);
 /* root = an existing object (e.g. the HitableList of a scene file) */
 int rt_scene_set_root(rt_scene* s, int object);
@@ -299,6 +301,41 @@ typedef struct rt_background {
 } rt_background;
 int rt_scene_set_background(rt_scene* s, const rt_background* bg);
 int rt_scene_get_background(const rt_scene* s, rt_background* out);
+/* ---- env sampling: the background as a light of integrator 1 (no reference counterpart) ----
+ * Off by default; a scene that leaves it off keeps its blob, its fingerprint, its kernels and every image.  Enabled, every device the
+ * scene is uploaded to builds a piecewise-constant distribution over the (u, v) square of Sphere::get_uv from the background B(d) above,
+ * W x H cells, cell (i, j) = u in [i/W, (i+1)/W), v in [j/H, (j+1)/H) (v = 0 is straight down; an ImageTexture flips v, so image row r
+ * from the top is table row H - 1 - r).  All of it in f64 without contraction; PI = 3.14159265358979323846, sin = rtamd-sin-1 (det_sin),
+ * cos x = det_sin(x + PI / 2.0):
+ *   weight  theta = PI * ((j + 0.5) / H), phi = (2.0 * PI) * ((i + 0.5) / W), st = det_sin(theta),
+ *           d_ij = (-(cos phi * st), -cos theta, sin phi * st), (r, g, b) = B(d_ij) (the very function that shades a miss, which
+ *           normalises d_ij once more), w_ij = ((0.2126 r + 0.7152 g) + 0.0722 b) * st.
+ *   q_ij    0 where w_ij is not > 0, otherwise max(1, floor((w_ij / w_max) * 4294967295.0)) as uint32, w_max the largest w_ij.  Row
+ *           sums, their prefix sums and `total` are uint64, so no order of summation shows.  total == 0 (a black background) switches
+ *           the strategy off: the scene renders as if env sampling were not enabled, the refusal of a scene without lights included.
+ *   draw    four gen_f64 draws xi1..xi4 in this order: row j = the first row whose inclusive prefix sum of row totals exceeds
+ *           min(total - 1, (uint64)(xi1 * (double)total)); column i likewise within row j from xi2 and the row's total;
+ *           u = (i + xi3) / W, v = (j + xi4) / H, theta = PI * v, phi = (2.0 * PI) * u, and d by the formula of d_ij.
+ *   pdf     of ANY direction d: n = unit(d), (u, v) = get_uv(n) (rtamd-acos-1 / rtamd-atan2-1), i = min(W - 1, (int)floor(W * u)),
+ *           j = min(H - 1, (int)floor(H * v)), s2 = 1.0 - n.y * n.y; 0 where s2 is not > 0, otherwise
+ *           p = ((((double)q_ij / (double)total) * (double)W) * (double)H) / (((2.0 * PI) * PI) * sqrt(s2)).
+ *   mixture with L >= 0 object lights the light half of integrator 1 picks one of L + 1 strategies by (uint32)(gen_f64() * (L + 1))
+ *           (clamped to L), index L being the environment, and pdf = 0.5 * ((sum of the light pdfs + p) / (L + 1)) + 0.5 * cosine / PI,
+ *           the sum taken lights first.  Weight, termination and what a miss adds are unchanged.  The cosine half reaches every
+ *           direction the BSDF scatters into, so the estimator is unbiased whatever the table's resolution.
+ * width = height = 0: automatic -- a kind-3 background whose texture is an ImageTexture gets one cell per texel, both axes halved
+ * (integer division) until the table is at most 4096 x 2048; every other background 256 x 128.  The table lives in device memory
+ * beside the scene's upload, is freed with it and is not part of the blob; the blob gains a 16-byte record {1, W, H}, so
+ * rt_scene_fingerprint tells a scene with env sampling from one without and two table sizes apart.
+ * RT_ERR_ARG: enabled outside 0 / 1, a negative size, only one of width / height zero, a size above 8192 x 8192, a call after commit;
+ * at rt_scene_commit, enabled with a background of kind 0.  Only integrator 1 on kernels 1 / 2 changes; everything integrator 1 refuses
+ * without env sampling (media, the book-2 kinds, kernels 5 / 6 under a background) stays refused, and so does rt_render_sppm*. */
+typedef struct rt_env_sampling {
+    int32_t enabled;        /* 0 (default) / 1 */
+    int32_t width, height;  /* table resolution; 0, 0 = automatic */
+} rt_env_sampling;
+int rt_scene_set_env_sampling(rt_scene* s, const rt_env_sampling* cfg);
+int rt_scene_get_env_sampling(const rt_scene* s, rt_env_sampling* out);  /* what was set (0, 0 stays 0, 0) */
 /* scene.rs:16-112 cornell_box_scene(): the reference's only built-in scene, numbers verbatim.
  * cube_obj_path = "data/mesh/cube.obj" of the reference. */
 int rt_scene_cornell_box(rt_scene* s, const char* cube_obj_path, double aspect_ratio, uint64_t bvh_seed, rt_camera* cam_out);
@@ -517,6 +554,13 @@ int rt_debug_hit_device(const rt_scene* s, int kernel, size_t n, const double* r
  * are cut the same way; jobs are dealt round by round, so the small jobs of the last levels are what runs when the queue runs dry.
  * Returns the number of rounds (jobs per tile) or a negative rt_status. */
 int rt_debug_schedule(int64_t tiles_owned, int n_waves, int s_begin, int s_end, int sub_spp, int job_units, int* out25);
+/* env sampling diagnostics on HIP device `device` (a committed scene with env sampling enabled; RT_ERR_NO_DEVICE without a GPU).
+ * table: the resolved size and, where q_host is not NULL, the h*w quantised weights q (row j = v cell j) as that device built them.
+ * sample: n draws from xi4_host (n*4: xi1..xi4) -> out_host n*4 = {d[3], pdf(d)}.  pdf: n directions (n*3) -> n pdfs.  A table whose
+ * total is 0 returns zeros from both. */
+int rt_debug_env_table_device(const rt_scene* s, int device, int* w, int* h, uint32_t* q_host);
+int rt_debug_env_sample_device(const rt_scene* s, int device, size_t n, const double* xi4_host, double* out_host);
+int rt_debug_env_pdf_device(const rt_scene* s, int device, size_t n, const double* dirs_host, double* pdf_host);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <new>
@@ -63,6 +64,14 @@ static void not_committed_only(const rt_scene* s) {
     REQUIRE(s, "null scene");
     if (s->committed) throw RtError(RT_ERR_ARG, "scene is immutable after rt_scene_commit");
 }
+
+// The device half of the env sampling diagnostics (device/kernels.hip).  Referenced weakly: a build of the host half alone, linked
+// against a stand-in for the device layer that predates them, still links, and the diagnostics then report that there is no device.
+namespace rtamd {
+void debug_env_table_device(const rt_scene& s, int* w, int* h, uint32_t* q_host) __attribute__((weak));
+void debug_env_eval_device(const rt_scene& s, int mode, size_t n, const double* in, double* out) __attribute__((weak));
+}  // namespace rtamd
+static bool env_debug_linked() { return &rtamd::debug_env_table_device != nullptr && &rtamd::debug_env_eval_device != nullptr; }
 
 extern "C" {
 
@@ -528,6 +537,25 @@ int rt_scene_get_background(const rt_scene* s, rt_background* out) {
     return guard([&] {
         REQUIRE(s && out, "null argument");
         *out = s->background;
+        return (int)RT_OK;
+    });
+}
+int rt_scene_set_env_sampling(rt_scene* s, const rt_env_sampling* cfg) {
+    return guard([&] {
+        not_committed_only(s);
+        REQUIRE(cfg, "null env sampling config");
+        REQUIRE(cfg->enabled == 0 || cfg->enabled == 1, "env sampling: enabled must be 0 or 1");
+        REQUIRE(cfg->width >= 0 && cfg->height >= 0, "env sampling: the table size must not be negative");
+        REQUIRE((cfg->width == 0) == (cfg->height == 0), "env sampling: width and height are both 0 (automatic) or both set");
+        REQUIRE(cfg->width <= ENV_MAX_DIM && cfg->height <= ENV_MAX_DIM, "env sampling: the table is at most 8192 x 8192");
+        s->env_sampling = *cfg;
+        return (int)RT_OK;
+    });
+}
+int rt_scene_get_env_sampling(const rt_scene* s, rt_env_sampling* out) {
+    return guard([&] {
+        REQUIRE(s && out, "null argument");
+        *out = s->env_sampling;
         return (int)RT_OK;
     });
 }
@@ -1437,6 +1465,40 @@ int rt_debug_hit_device(const rt_scene* s, int kernel, size_t n, const double* r
         if (device_count() < 1) throw RtError(RT_ERR_NO_DEVICE, "no HIP device");
         debug_hit_device(*s, kernel, n, rays_host, t_min, t_max, out_host);
         return (int)RT_OK;
+    });
+}
+// the three env sampling diagnostics run on `device` and leave the caller's current device as it was
+static int env_debug(const rt_scene* s, int device, const std::function<void()>& f) {
+    return guard([&] {
+        REQUIRE(s, "null scene");
+        const int n_dev = device_count();
+        if (n_dev < 1 || !env_debug_linked()) throw RtError(RT_ERR_NO_DEVICE, "no HIP device");
+        REQUIRE(device >= 0 && device < n_dev, "no such device");
+        const int cur = dev_get_device();
+        dev_set_device(device);
+        try {
+            f();
+        } catch (...) {
+            dev_set_device(cur);
+            throw;
+        }
+        dev_set_device(cur);
+        return (int)RT_OK;
+    });
+}
+int rt_debug_env_table_device(const rt_scene* s, int device, int* w, int* h, uint32_t* q_host) {
+    return env_debug(s, device, [&] { debug_env_table_device(*s, w, h, q_host); });
+}
+int rt_debug_env_sample_device(const rt_scene* s, int device, size_t n, const double* xi4_host, double* out_host) {
+    return env_debug(s, device, [&] {
+        REQUIRE(n > 0 && xi4_host && out_host, "bad argument");
+        debug_env_eval_device(*s, 0, n, xi4_host, out_host);
+    });
+}
+int rt_debug_env_pdf_device(const rt_scene* s, int device, size_t n, const double* dirs_host, double* pdf_host) {
+    return env_debug(s, device, [&] {
+        REQUIRE(n > 0 && dirs_host && pdf_host, "bad argument");
+        debug_env_eval_device(*s, 1, n, dirs_host, pdf_host);
     });
 }
 int rt_debug_schedule(int64_t tiles_owned, int n_waves, int s_begin, int s_end, int sub_spp, int job_units, int* out25) {

@@ -89,6 +89,22 @@ struct BgDev {    // rt_background of a scene whose kind is 1..3 (no reference c
     double scale;
 };
 static_assert(sizeof(BgDev) == 64, "BgDev: 64 bytes in the blob");
+struct EnvDev {   // rt_env_sampling of a scene that enabled it: the resolution of the table each device builds
+    int32_t enabled;       // 1
+    int32_t w, h;          // resolved (never 0)
+    int32_t pad;
+};
+static_assert(sizeof(EnvDev) == 16, "EnvDev: 16 bytes in the blob");
+// The environment table as a device holds it, right behind its copy of the blob (at base + total_bytes; never part of the blob):
+// this header, then rowcum[h] (inclusive prefix sums of the row totals), then cum[h][w] (inclusive prefix sums of q along each row).
+struct EnvTabHdr {
+    uint64_t total;        // sum of every q; 0: a black background, the env strategy is off
+    uint64_t wmax_bits;    // the largest cell weight as the bits of its f64 (scratch of the build)
+    uint32_t w, h;
+    uint64_t pad;
+};
+static_assert(sizeof(EnvTabHdr) == 32, "EnvTabHdr: 32 bytes");
+static const int ENV_MAX_DIM = 8192;
 struct TexDev {   // material.rs:48-84
     int32_t type;  // 0 Constant, 1 Checker, 2 Image, 3 Noise (D9: Perlin marble, book 2)
     int32_t t0, t1;        // Checker: constant-texture ids (.0 when sines < 0, .1 otherwise)
@@ -177,6 +193,8 @@ struct FlatView {  // by-value kernel argument
     uint32_t world_depth2;       // depth of the world-space BVH (kernel 5 walks it and the object-space BVHs separately)
     // cold part: the scene's background (rt_scene_set_background), one BgDev; 0 = none (kind 0: the blob is unchanged)
     uint32_t off_bg;
+    // cold part: one EnvDev when the scene enabled env sampling (rt_scene_set_env_sampling); 0 = none (the blob is unchanged)
+    uint32_t off_env;
 };
 
 // ---------------------------------------------------------------------------

@@ -45,6 +45,10 @@ void debug_rng_device(uint64_t seed, uint64_t pixel, uint64_t sample, int n, uin
 void debug_rng_floats_device(uint64_t seed, uint64_t pixel, uint64_t sample, int n, double lo, double hi, double* out_gen, double* out_range);
 void debug_math_device(int op, size_t n, const double* a, const double* b, double* out);
 void debug_hit_device(const rt_scene& s, int kernel, size_t n, const double* rays, double t_min, double t_max, double* out);
+// env sampling diagnostics on the current device: the table as built; mode 0: n draws (in n*4 xi -> out n*4 {d, pdf}),
+// mode 1: n pdfs (in n*3 directions -> out n)
+void debug_env_table_device(const rt_scene& s, int* w, int* h, uint32_t* q_host);
+void debug_env_eval_device(const rt_scene& s, int mode, size_t n, const double* in, double* out);
 int device_count();
 // thin HIP wrappers so abi.cpp stays free of HIP headers
 void* dev_alloc(size_t n);

@@ -1401,6 +1401,69 @@ __device__ __attribute__((noinline)) D3 background_radiance(const BgDev* __restr
     const double sc = bg->scale;
     return mk(sc * c.x, sc * c.y, sc * c.z);
 }
+// Env sampling (no reference counterpart): the background as one more light of integrator 1.  The table sits in global
+// memory right behind the device's copy of the blob (EnvTabHdr, rowcum[h], cum[h][w]: flat.h); every operation below is in the order
+// rtamd.h pins.  Only the INTEG_ENV variants, the table build and the diagnostics call these.
+struct EnvTab {
+    const EnvTabHdr* hdr;
+    const uint64_t* rowcum;  // inclusive prefix sums of the row totals
+    const uint64_t* cum;     // per row: inclusive prefix sums of q
+};
+DEV EnvTab env_tab(const char* tab) {
+    EnvTab e;
+    e.hdr = (const EnvTabHdr*)tab;
+    e.rowcum = (const uint64_t*)(tab + sizeof(EnvTabHdr));
+    e.cum = e.rowcum + e.hdr->h;
+    return e;
+}
+DEV D3 env_dir(double u, double v, double& st) {  // the inverse of Sphere::get_uv
+    const double PI = 3.14159265358979323846264338327950288;
+    const double theta = PI * v, phi = (2.0 * PI) * u;
+    st = det_sin(theta);
+    const double ct = det_sin(theta + PI / 2.0), cp = det_sin(phi + PI / 2.0), sp = det_sin(phi);
+    return mk(-(cp * st), -ct, sp * st);
+}
+// the first index in [0, n) whose inclusive prefix sum exceeds t (t < p[n - 1]): every step is a dependent global load (L2 hits mostly)
+DEV uint32_t env_search(const uint64_t* __restrict__ p, uint32_t n, uint64_t t) {
+    uint32_t lo = 0u, hi = n - 1u;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (p[mid] > t) hi = mid;
+        else lo = mid + 1u;
+    }
+    return lo;
+}
+__device__ __attribute__((noinline)) D3 env_sample(const char* tab, double x1, double x2, double x3, double x4) {
+    const EnvTab e = env_tab(tab);
+    const uint32_t W = e.hdr->w, H = e.hdr->h;
+    const uint64_t total = e.hdr->total;
+    uint64_t t = (uint64_t)(x1 * (double)total);
+    if (t > total - 1ull) t = total - 1ull;
+    const uint32_t j = env_search(e.rowcum, H, t);
+    const uint64_t* row = e.cum + (size_t)j * W;
+    const uint64_t row_total = row[W - 1u];
+    uint64_t tc = (uint64_t)(x2 * (double)row_total);
+    if (tc > row_total - 1ull) tc = row_total - 1ull;
+    const uint32_t i = env_search(row, W, tc);
+    double st;
+    return env_dir(((double)i + x3) / (double)W, ((double)j + x4) / (double)H, st);
+}
+__device__ __attribute__((noinline)) double env_pdf(const char* tab, D3 d, int* err) {
+    const double PI = 3.14159265358979323846264338327950288;
+    const EnvTab e = env_tab(tab);
+    const uint32_t W = e.hdr->w, H = e.hdr->h;
+    const D3 n = unit(d, err);
+    double u, v;
+    sphere_uv(n, u, v);
+    int i = (int)floor((double)W * u), j = (int)floor((double)H * v);
+    i = i < 0 ? 0 : (i > (int)W - 1 ? (int)W - 1 : i);  // (u, v lie in [0, 1]; the clamps also keep a NaN direction inside the table)
+    j = j < 0 ? 0 : (j > (int)H - 1 ? (int)H - 1 : j);
+    const double s2 = 1.0 - n.y * n.y;
+    if (!(s2 > 0.)) return 0.;
+    const uint64_t* row = e.cum + (size_t)j * W;
+    const uint64_t q = row[i] - (i > 0 ? row[i - 1] : 0ull);
+    return ((((double)q / (double)e.hdr->total) * (double)W) * (double)H) / (((2.0 * PI) * PI) * sqrt(s2));
+}
 // Build the HitRecord of the winning leaf only (the reference builds one per candidate).  uv is computed only where an ImageTexture
 // reads it, unless ALL_UV (the closest-hit diagnostic, which returns the whole record).
 template <int GENERAL, bool ALL_UV = false>
@@ -1628,6 +1691,31 @@ DEV bool mixture_step(const Acc& A, const Rec& rec, Rng& rng, D3 att, D3& beta, 
     double lp = 0.;
     for (uint32_t i = 0; i < A.n_lights; i++) lp = lp + light_pdf_value(A, A.lights[i], rec.p, dir);
     double pdf_val = 0.5 * (lp / (double)A.n_lights) + 0.5 * scattering_pdf;
+    double wgt = scattering_pdf / pdf_val;
+    if (!(wgt > 0.)) return false;
+    beta = muls(elemul(beta, att), wgt);
+    return true;
+}
+// mixture_step with the environment as strategy number n_lights of the light half (INTEG_ENV; rtamd.h "env sampling"): n_lights may be 0
+DEV bool mixture_step_env(const Acc& A, const char* env, const Rec& rec, Rng& rng, D3 att, D3& beta, D3& dir, int* err) {
+    const double PI = 3.14159265358979323846264338327950288;
+    const uint32_t n = A.n_lights + 1u;
+    if (rng.gen_f64() < 0.5) {
+        uint32_t li = (uint32_t)(rng.gen_f64() * (double)n);
+        if (li >= n) li = n - 1u;
+        if (li == A.n_lights) {
+            const double x1 = rng.gen_f64(), x2 = rng.gen_f64(), x3 = rng.gen_f64(), x4 = rng.gen_f64();
+            dir = env_sample(env, x1, x2, x3, x4);
+        } else {
+            dir = light_random(A, A.lights[li], rec.p, rng, err);
+        }
+    }
+    double cosine = dot(rec.normal, unit(dir, err));
+    double scattering_pdf = (cosine < 0.) ? 0. : cosine / PI;
+    double lp = 0.;
+    for (uint32_t i = 0; i < A.n_lights; i++) lp = lp + light_pdf_value(A, A.lights[i], rec.p, dir);
+    lp = lp + env_pdf(env, dir, err);
+    double pdf_val = 0.5 * (lp / (double)n) + 0.5 * scattering_pdf;
     double wgt = scattering_pdf / pdf_val;
     if (!(wgt > 0.)) return false;
     beta = muls(elemul(beta, att), wgt);
@@ -2073,6 +2161,8 @@ __device__ __attribute__((noinline)) UnitInfo next_unit(uint32_t* wst_, uint32_t
 // INTEG & INTEG_BG: the background variants of integrator INTEG & 3 -- a value of the INTEG axis rather than a template
 // parameter of its own, so that every kernel without a background keeps its name (and its code)
 static constexpr int INTEG_BG = 4;
+// INTEG & INTEG_ENV (on top of 1 | INTEG_BG): integrator 1 with the background as a light (env sampling)
+static constexpr int INTEG_ENV = 8;
 template <bool LDS, int GENERAL, int ACCEL, int INTEG, bool MEDIA = false, bool POOL = false>
 __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, RenderK rk, double* __restrict__ ring, double* accum,
                                                       unsigned int* tickets, unsigned int* __restrict__ counter, int* __restrict__ err) {
@@ -2310,7 +2400,8 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
                             go = false;
                         } else if ((INTEG & 3) == 1 && diffuse) {
                             PH_EV(14);
-                            go = mixture_step(A, rec, rng, att, beta, ndir, err);
+                            if (INTEG & INTEG_ENV) go = mixture_step_env(A, sv.base + sv.total_bytes, rec, rng, att, beta, ndir, err);
+                            else go = mixture_step(A, rec, rng, att, beta, ndir, err);
                         } else {
                             beta = elemul(beta, att);
                         }
@@ -3616,6 +3707,123 @@ __global__ void hit_kernel_nest(FlatView sv, int accel, size_t n, const double* 
     hit_row(q, h, rec);
 }
 
+// ------------------------------------------------- env sampling: table build ----
+// Three launches per scene and device, on the table behind the blob.  1: w_ij of every cell through the very
+// background_radiance that shades a miss, stored as f64 in the cell's cum slot, and the largest of them (non-negative f64 order like
+// their bit patterns, so an integer max does).  2: one workgroup per row quantises w to q and turns the row into inclusive prefix sums;
+// the row total goes to rowcum[j].  3: one workgroup turns rowcum into prefix sums and stores the total.  All sums are integers.
+static const int ENV_BLOCK = 256;
+DEV uint64_t env_block_scan(uint64_t x, uint64_t* sh) {  // inclusive scan over the ENV_BLOCK threads of a workgroup (sh: ENV_BLOCK words of LDS)
+    const int t = (int)threadIdx.x;
+    sh[t] = x;
+    __syncthreads();
+    for (int off = 1; off < ENV_BLOCK; off <<= 1) {
+        const uint64_t add = (t >= off) ? sh[t - off] : 0ull;
+        __syncthreads();
+        sh[t] += add;
+        __syncthreads();
+    }
+    const uint64_t r = sh[t];
+    __syncthreads();
+    return r;
+}
+template <int GENERAL>
+__global__ void __launch_bounds__(ENV_BLOCK) env_weight_kernel(FlatView sv, int* err) {
+    __shared__ uint64_t sh[ENV_BLOCK];
+    char* tab = const_cast<char*>(sv.base) + sv.total_bytes;
+    EnvTabHdr* hdr = (EnvTabHdr*)tab;
+    const uint32_t W = hdr->w, H = hdr->h;
+    double* wcell = (double*)(tab + sizeof(EnvTabHdr)) + H;
+    const size_t n = (size_t)W * H;
+    const BgDev* bg = (const BgDev*)(sv.base + sv.off_bg);
+    const TexDev* texs = (const TexDev*)(sv.base + sv.off_texs);
+    const uint8_t* texels = (const uint8_t*)(sv.base + sv.off_texels);
+    double wmax = 0.;
+    for (size_t k = (size_t)blockIdx.x * ENV_BLOCK + threadIdx.x; k < n; k += (size_t)gridDim.x * ENV_BLOCK) {
+        const uint32_t i = (uint32_t)(k % W), j = (uint32_t)(k / W);
+        double st;
+        const D3 d = env_dir(((double)i + 0.5) / (double)W, ((double)j + 0.5) / (double)H, st);
+        const D3 c = background_radiance<GENERAL>(bg, texs, texels, d, err);
+        double w = ((0.2126 * c.x + 0.7152 * c.y) + 0.0722 * c.z) * st;
+        if (!(w > 0.)) w = 0.;
+        wcell[k] = w;
+        wmax = fmax(wmax, w);
+    }
+    sh[threadIdx.x] = (uint64_t)__double_as_longlong(wmax);
+    __syncthreads();
+    for (int off = ENV_BLOCK / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off && sh[threadIdx.x + off] > sh[threadIdx.x]) sh[threadIdx.x] = sh[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && sh[0] != 0ull) atomicMax((unsigned long long*)&hdr->wmax_bits, (unsigned long long)sh[0]);
+}
+__global__ void __launch_bounds__(ENV_BLOCK) env_row_kernel(FlatView sv) {
+    __shared__ uint64_t sh[ENV_BLOCK];
+    char* tab = const_cast<char*>(sv.base) + sv.total_bytes;
+    const EnvTabHdr* hdr = (const EnvTabHdr*)tab;
+    const uint32_t W = hdr->w, H = hdr->h;
+    const uint32_t j = blockIdx.x;
+    if (j >= H) return;
+    uint64_t* rowcum = (uint64_t*)(tab + sizeof(EnvTabHdr));
+    uint64_t* row = rowcum + H + (size_t)j * W;
+    const double wmax = __longlong_as_double((long long)hdr->wmax_bits);
+    uint64_t carry = 0ull;
+    for (uint32_t i0 = 0; i0 < W; i0 += ENV_BLOCK) {  // (every thread runs every round: the scan synchronises the workgroup)
+        const uint32_t i = i0 + threadIdx.x;
+        uint64_t q = 0ull;
+        if (i < W) {
+            const double w = __longlong_as_double((long long)row[i]);
+            if (w > 0.) {
+                q = (uint64_t)floor((w / wmax) * 4294967295.0);
+                if (q < 1ull) q = 1ull;
+            }
+        }
+        const uint64_t incl = env_block_scan(q, sh) + carry;
+        if (i < W) row[i] = incl;
+        sh[threadIdx.x] = incl;
+        __syncthreads();
+        carry = sh[ENV_BLOCK - 1];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) rowcum[j] = carry;
+}
+__global__ void __launch_bounds__(ENV_BLOCK) env_total_kernel(FlatView sv) {
+    __shared__ uint64_t sh[ENV_BLOCK];
+    char* tab = const_cast<char*>(sv.base) + sv.total_bytes;
+    EnvTabHdr* hdr = (EnvTabHdr*)tab;
+    const uint32_t H = hdr->h;
+    uint64_t* rowcum = (uint64_t*)(tab + sizeof(EnvTabHdr));
+    uint64_t carry = 0ull;
+    for (uint32_t j0 = 0; j0 < H; j0 += ENV_BLOCK) {
+        const uint32_t j = j0 + threadIdx.x;
+        const uint64_t incl = env_block_scan(j < H ? rowcum[j] : 0ull, sh) + carry;
+        if (j < H) rowcum[j] = incl;
+        sh[threadIdx.x] = incl;
+        __syncthreads();
+        carry = sh[ENV_BLOCK - 1];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) hdr->total = carry;
+}
+// rt_debug_env_sample_device (mode 0: in = n x {xi1..xi4}, out = n x {d, pdf(d)}) and rt_debug_env_pdf_device (mode 1: in = n directions)
+__global__ void env_eval_kernel(FlatView sv, int mode, size_t n, const double* __restrict__ in, double* __restrict__ out, int* err) {
+    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const char* tab = sv.base + sv.total_bytes;
+    const bool live = ((const EnvTabHdr*)tab)->total != 0ull;
+    if (mode == 0) {
+        D3 d = mk(0., 0., 0.);
+        double p = 0.;
+        if (live) {
+            d = env_sample(tab, in[4 * k], in[4 * k + 1], in[4 * k + 2], in[4 * k + 3]);
+            p = env_pdf(tab, d, err);
+        }
+        out[4 * k] = d.x; out[4 * k + 1] = d.y; out[4 * k + 2] = d.z; out[4 * k + 3] = p;
+    } else {
+        out[k] = live ? env_pdf(tab, mk(in[3 * k], in[3 * k + 1], in[3 * k + 2]), err) : 0.;
+    }
+}
+
 // ------------------------------------------------------------ host side ---
 int device_count() {
     int n = 0;
@@ -3633,10 +3841,23 @@ void dev_copy_to_host(void* dst, const void* src, size_t n) { HIP_CHECK(hipMemcp
 void dev_copy_to_device(void* dst, const void* src, size_t n) { HIP_CHECK(hipMemcpy(dst, src, n, hipMemcpyHostToDevice)); }
 void dev_set_device(int d) { HIP_CHECK(hipSetDevice(d)); }
 
-static const char* device_blob(const rt_scene& s, int dev, double* upload_ms = nullptr) {
+// the bytes of the env table behind a device's blob (flat.h: EnvTabHdr, rowcum[h], cum[h][w]); 0 for a scene without env sampling
+static size_t env_table_bytes(const rt_scene& s, uint32_t* w = nullptr, uint32_t* h = nullptr) {
+    const uint32_t off = s.flat.view.off_env;
+    if (off == 0u) return 0;
+    EnvDev e;
+    std::memcpy(&e, s.flat.blob.data() + off, sizeof(e));
+    if (w) *w = (uint32_t)e.w;
+    if (h) *h = (uint32_t)e.h;
+    return sizeof(EnvTabHdr) + sizeof(uint64_t) * ((size_t)e.h + (size_t)e.w * (size_t)e.h);
+}
+static const char* device_blob(const rt_scene& s, int dev, double* upload_ms = nullptr, uint64_t* env_total = nullptr) {
     std::lock_guard<std::mutex> g(s.dev_mu);
     for (auto& c : s.dev)
-        if (c.device == dev) return (const char*)c.d_blob;
+        if (c.device == dev) {
+            if (env_total) *env_total = c.env_total;
+            return (const char*)c.d_blob;
+        }
     const auto t0 = std::chrono::steady_clock::now();
     struct Timed {  // the one upload of this scene to this device (rt_stats.upload_ms of the call that made it)
         double* out;
@@ -3647,9 +3868,41 @@ static const char* device_blob(const rt_scene& s, int dev, double* upload_ms = n
     } timed{upload_ms, t0};
     DeviceCopy c;
     c.device = dev;
-    HIP_CHECK(hipMalloc(&c.d_blob, s.flat.blob.size()));
+    uint32_t env_w = 0, env_h = 0;
+    const size_t env_bytes = env_table_bytes(s, &env_w, &env_h);
+    HIP_CHECK(hipMalloc(&c.d_blob, s.flat.blob.size() + env_bytes));
+    struct Guard {  // (a failed build leaves no half-made copy behind)
+        void* p;
+        ~Guard() {
+            if (p) (void)hipFree(p);
+        }
+    } guard{c.d_blob};
     HIP_CHECK(hipMemcpy(c.d_blob, s.flat.blob.data(), s.flat.blob.size(), hipMemcpyHostToDevice));
+    if (env_bytes != 0) {  // env sampling: this device builds its own table, once
+        FlatView view = s.flat.view;
+        view.base = (const char*)c.d_blob;
+        EnvTabHdr hdr{};
+        hdr.w = env_w;
+        hdr.h = env_h;
+        char* tab = (char*)c.d_blob + s.flat.blob.size();
+        HIP_CHECK(hipMemcpy(tab, &hdr, sizeof(hdr), hipMemcpyHostToDevice));
+        int* err = (int*)(tab + offsetof(EnvTabHdr, pad));  // the build's error word (unit() of a zero vector; zeroed with the header)
+        const size_t cells = (size_t)env_w * env_h;
+        const unsigned grid = (unsigned)std::min<size_t>((cells + ENV_BLOCK - 1) / ENV_BLOCK, 8192);
+        if (view.has_noise) hipLaunchKernelGGL(env_weight_kernel<2>, dim3(grid), dim3(ENV_BLOCK), 0, 0, view, err);
+        else hipLaunchKernelGGL(env_weight_kernel<1>, dim3(grid), dim3(ENV_BLOCK), 0, 0, view, err);
+        HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(env_row_kernel, dim3(env_h), dim3(ENV_BLOCK), 0, 0, view);
+        HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(env_total_kernel, dim3(1), dim3(ENV_BLOCK), 0, 0, view);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(&hdr, tab, sizeof(hdr), hipMemcpyDeviceToHost));  // (synchronises)
+        if (hdr.pad != 0ull) throw RtError(RT_ERR_INTERNAL, "the env table build reported an error (bits " + std::to_string(hdr.pad) + ")");
+        c.env_total = hdr.total;
+    }
+    guard.p = nullptr;
     s.dev.push_back(c);
+    if (env_total) *env_total = c.env_total;
     return (const char*)c.d_blob;
 }
 void free_device_copies(rt_scene& s) {
@@ -3830,6 +4083,12 @@ static pt_fn pick_pt_kernel_bg(int g, bool media, int integ) {
     if (g == 2) return media ? pt_kernel<LDS, 2, ACCEL, B, true> : pt_kernel<LDS, 2, ACCEL, B>;
     return media ? pt_kernel<LDS, 3, ACCEL, B, true> : (integ == 1) ? pt_kernel<LDS, 3, ACCEL, B | 1> : pt_kernel<LDS, 3, ACCEL, B>;
 }
+// the env sampling variants (INTEG_ENV on top of 1 | INTEG_BG): integrator 1 where pick_pt_kernel_bg returns a B | 1 variant
+template <int ACCEL, bool LDS>
+static pt_fn pick_pt_kernel_env(bool nest) {
+    constexpr int E = INTEG_ENV | INTEG_BG | 1;
+    return nest ? pt_kernel<LDS, 3, ACCEL, E> : pt_kernel<LDS, 1, ACCEL, E>;
+}
 
 static void render_tiles_wf(const rt_scene& s, const FlatView& view, const CameraDev& cam, const RenderPlan& plan, const Tuning& tun, double* d_tiles,
                             hipStream_t stream, rt_stats* st, int dev, const DevInfo& di, uint32_t stack6, uint32_t n_entry6, size_t lds_pt, uint32_t stack6w,
@@ -3866,8 +4125,11 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
 
     FlatView view = s.flat.view;
     double upload_ms = 0.;
-    view.base = device_blob(s, dev, &upload_ms);
+    uint64_t env_total = 0;
+    view.base = device_blob(s, dev, &upload_ms, &env_total);
     if (st) st->upload_ms = upload_ms;
+    // env sampling: the background is a light of integrator 1 -- unless its table sums to zero (a black background)
+    const bool env = view.off_env != 0u && env_total != 0ull;
     const bool moving = (view.kinds_mask & (1u << NK_MSPHERE)) != 0;  // D9: the paths' times live in LDS, 8 bytes per lane
     // D9: moving spheres, noise textures and an open shutter (every sample draws a time) live in their own kernel variants (GENERAL == 2,
     // kernels 1 / 2, integrator 0): nothing of them is compiled into the others
@@ -3943,7 +4205,7 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
     const size_t hot_bytes = (kernel == 2 || kernel == 5) ? hot2 - (size_t)view.n_nodes2 * sizeof(Node2) + nodew : hot1;
     const bool lds = hot_bytes > 0 && hot_bytes + stack_bytes <= lds_max && !tun.no_lds && kernel != 5;  // kernel 5: scene in L2/HBM always
     const int integ = plan.integrator;
-    if (integ == 1 && view.n_lights == 0) throw RtError(RT_ERR_ARG, "integrator 1 (light importance sampling) needs rt_scene_set_lights");
+    if (integ == 1 && view.n_lights == 0 && !env) throw RtError(RT_ERR_ARG, "integrator 1 (light importance sampling) needs rt_scene_set_lights");
     if (integ == 2 && !plan.sppm_est) throw RtError(RT_ERR_ARG, "integrator 2 (SPPM) is reached through rt_render_sppm");
     if (integ != 0 && book2)
         throw RtError(RT_ERR_UNSUPPORTED, "the book-2 extensions (moving spheres, noise textures, an open shutter) render with integrator 0 (kernels 1 and 2)");
@@ -3989,6 +4251,9 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
         fn = (kernel == 2) ? (lds ? pick_pt_kernel_bg<2, true>(g, media, integ) : pick_pt_kernel_bg<2, false>(g, media, integ))
                            : (lds ? pick_pt_kernel_bg<1, true>(g, media, integ) : pick_pt_kernel_bg<1, false>(g, media, integ));
     }
+    if (bg && env && integ == 1)  // (media and the book-2 kinds were refused above: GENERAL is 1 or 3 here)
+        fn = (kernel == 2) ? (lds ? pick_pt_kernel_env<2, true>(nest) : pick_pt_kernel_env<2, false>(nest))
+                           : (lds ? pick_pt_kernel_env<1, true>(nest) : pick_pt_kernel_env<1, false>(nest));
     // scene too large for LDS: spend what is left after the stacks on the shallowest BVH levels (the Node2 array is depth-sorted)
     int n_top = 0, n_topq = 0;
     if (kernel == 2 && !lds && lds_max > stack_bytes) {
@@ -4740,6 +5005,38 @@ void debug_math_device(int op, size_t n, const double* a, const double* bb, doub
                        (double*)dc.p);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpy(out, dc.p, n * 8, hipMemcpyDeviceToHost));
+}
+static const char* env_debug_blob(const rt_scene& s, uint32_t* w, uint32_t* h) {
+    if (!s.committed) throw RtError(RT_ERR_NOT_COMMITTED, "scene not committed");
+    if (env_table_bytes(s, w, h) == 0) throw RtError(RT_ERR_ARG, "the scene has no env sampling (rt_scene_set_env_sampling)");
+    int dev = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    return device_blob(s, dev);
+}
+void debug_env_table_device(const rt_scene& s, int* w, int* h, uint32_t* q_host) {
+    uint32_t W = 0, H = 0;
+    const char* blob = env_debug_blob(s, &W, &H);
+    if (w) *w = (int)W;
+    if (h) *h = (int)H;
+    if (!q_host) return;
+    std::vector<uint64_t> cum((size_t)W * H);
+    HIP_CHECK(hipMemcpy(cum.data(), blob + s.flat.blob.size() + sizeof(EnvTabHdr) + sizeof(uint64_t) * (size_t)H, cum.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < H; j++)
+        for (size_t i = 0; i < W; i++) q_host[j * W + i] = (uint32_t)(cum[j * W + i] - (i ? cum[j * W + i - 1] : 0ull));
+}
+void debug_env_eval_device(const rt_scene& s, int mode, size_t n, const double* in, double* out) {
+    FlatView view = s.flat.view;
+    view.base = env_debug_blob(s, nullptr, nullptr);
+    const size_t n_in = n * (mode == 0 ? 4 : 3) * sizeof(double), n_out = n * (mode == 0 ? 4 : 1) * sizeof(double);
+    DevBuf din, dout, err;
+    din.alloc(n_in);
+    dout.alloc(n_out);
+    err.alloc(4);
+    HIP_CHECK(hipMemset(err.p, 0, 4));
+    HIP_CHECK(hipMemcpy(din.p, in, n_in, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(env_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, view, mode, n, (const double*)din.p, (double*)dout.p, (int*)err.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpy(out, dout.p, n_out, hipMemcpyDeviceToHost));
 }
 void debug_hit_device(const rt_scene& s, int kernel, size_t n, const double* rays, double t_min, double t_max, double* out) {
     if (s.flat.view.kinds_mask & (1u << NK_MSPHERE)) throw RtError(RT_ERR_UNSUPPORTED, "rt_debug_hit_device has no ray time: scenes with moving spheres are not supported");

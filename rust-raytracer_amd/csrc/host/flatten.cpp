@@ -797,6 +797,27 @@ void flatten(rt_scene& s) {
         bg.scale = s.background.scale;
         v.off_bg = append(f.blob, std::vector<BgDev>{bg});
     }
+    v.off_env = 0u;
+    if (s.env_sampling.enabled != 0) {  // (a scene that leaves it off keeps its blob, like one without a background)
+        if (s.background.kind == 0) throw RtError(RT_ERR_ARG, "env sampling needs a background (rt_scene_set_background) to sample");
+        EnvDev e{};
+        e.enabled = 1;
+        e.w = s.env_sampling.width;
+        e.h = s.env_sampling.height;
+        if (e.w == 0) {  // automatic: an image map gets one cell per texel, halved per axis down to 4096 x 2048; anything else 256 x 128
+            e.w = 256;
+            e.h = 128;
+            if (s.background.kind == 3 && s.textures[s.background.texture].type == TEX_IMAGE) {
+                e.w = s.textures[s.background.texture].w;
+                e.h = s.textures[s.background.texture].h;
+                while (e.w > 4096 || e.h > 2048) {
+                    e.w = std::max(1, e.w / 2);
+                    e.h = std::max(1, e.h / 2);
+                }
+            }
+        }
+        v.off_env = append(f.blob, std::vector<EnvDev>{e});
+    }
     f.blob.resize((f.blob.size() + 15) & ~size_t(15));
     v.total_bytes = (uint32_t)f.blob.size();
     v.n_nodes = (uint32_t)(b.meta.size() / 2);

@@ -78,6 +78,8 @@ struct FlatScene {
 struct DeviceCopy {
     int device = -1;
     void* d_blob = nullptr;
+    // env sampling: the table this device built behind its blob sums to env_total (0: none, or a black background)
+    uint64_t env_total = 0;
 };
 
 }  // namespace rtamd
@@ -90,6 +92,7 @@ struct rt_scene {
     int root = -1;
     std::vector<int> lights;  // World::new's lights (object ids)
     rt_background background{};  // rt_scene_set_background; kind 0 = none (flattened only when kind != 0: DESIGN.md s4g)
+    rt_env_sampling env_sampling{};  // rt_scene_set_env_sampling; flattened only when enabled
     bool committed = false;
     rtamd::FlatScene flat;
     // device copies of the blob, one per HIP device, created lazily by the render entry points

@@ -3,12 +3,13 @@
 // and the same "Total / RT" timing print.  Also renders the reference's scene files.
 //   rtamd_render [--scene cornell|FILE.json|FILE.yaml] [--cube data/mesh/cube.obj] [-w W] [-h H] [--spp N]
 //                [--depth D] [--seed S] [--aspect A] [--integrator 0|1] [--sppm ITERATIONS PHOTONS_PER_ITER]
-//                [--gpus N | --devices 0,1,...] [--background r,g,b | --sky] [-o out.png] [--describe] [--vec3-selftest]
+//                [--gpus N | --devices 0,1,...] [--background r,g,b | --sky] [--env-sampling] [-o out.png] [--describe] [--vec3-selftest]
 // --gpus N spreads the frame over N GPUs of this node inside ONE capture_image call (rt_render_multi: tiles dealt round-robin, RCCL
 // gather; 0 = all visible); --devices names the HIP ordinal of every rank (an ordinal may repeat).
 // `rtamd_render --cube data/mesh/cube.obj --sppm 50 500000` is the reference binary: SPPM pre-pass + 256 spp, output/test.png
 // --background r,g,b gives rays that leave the scene a constant colour, --sky book 1's sky gradient (rt_scene_set_background; the
-// reference has neither: its misses are black)
+// reference has neither: its misses are black); --env-sampling makes that background one more light of --integrator 1
+// (rt_scene_set_env_sampling, automatic table size)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -52,6 +53,7 @@ int main(int argc, char** argv) {
     std::string checkpoint;  // --checkpoint FILE [--run-samples K]: trace the next K samples per pixel into the state in FILE; the image is written once all are in
     int run_samples = 64;
     rt_background bg{};  // kind 0: none
+    bool env_sampling = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -74,6 +76,7 @@ int main(int argc, char** argv) {
             }
         }
         else if (a == "--sky") bg = World::background_sky();
+        else if (a == "--env-sampling") env_sampling = true;
         else if (a == "--background") {
             double c[3];
             if (std::sscanf(next(), "%lf,%lf,%lf", &c[0], &c[1], &c[2]) != 3) { std::fprintf(stderr, "--background wants r,g,b\n"); return 2; }
@@ -89,10 +92,12 @@ int main(int argc, char** argv) {
     try {
         auto start_time = std::chrono::steady_clock::now();
         std::unique_ptr<World> world;
+        const rt_env_sampling env = World::env_sampling_on();
+        const rt_env_sampling* envp = env_sampling ? &env : nullptr;
         if (scene == "cornell") {
-            world = cornell_box_scene(cube, aspect > 0 ? aspect : (double)cfg.width / cfg.height, 1, bg.kind ? &bg : nullptr);
+            world = cornell_box_scene(cube, aspect > 0 ? aspect : (double)cfg.width / cfg.height, 1, bg.kind ? &bg : nullptr, envp);
         } else {
-            world = std::make_unique<World>(scene, bg.kind ? &bg : nullptr);
+            world = std::make_unique<World>(scene, bg.kind ? &bg : nullptr, envp);
             if (aspect > 0) world->cam.c.aspect = aspect;
         }
         rt_scene_info info;

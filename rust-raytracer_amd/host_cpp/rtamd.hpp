@@ -337,7 +337,9 @@ class World {
    public:
     Camera cam;
     // bg: rt_scene_set_background before the commit (nullptr: none, the reference's black)
-    World(const HitableList& hitable_list, Camera camera, const HitableList& lights = {}, uint64_t bvh_seed = 1, const rt_background* bg = nullptr)
+    // env: rt_scene_set_env_sampling before the commit (nullptr: off)
+    World(const HitableList& hitable_list, Camera camera, const HitableList& lights = {}, uint64_t bvh_seed = 1, const rt_background* bg = nullptr,
+          const rt_env_sampling* env = nullptr)
         : cam(camera) {
         check(rt_scene_create(&s_));
         try {
@@ -348,6 +350,7 @@ class World {
             check(rt_world_new(s_, (int)ids.size(), ids.data(), bvh_seed));
             if (!lids.empty()) check(rt_scene_set_lights(s_, (int)lids.size(), lids.data()));
             if (bg) check(rt_scene_set_background(s_, bg));
+            if (env) check(rt_scene_set_env_sampling(s_, env));
             check(rt_scene_commit(s_));
         } catch (...) {
             rt_scene_destroy(s_);
@@ -355,14 +358,15 @@ class World {
         }
     }
     // a scene file of the reference's data/ directory (README.md Track 5)
-    explicit World(const std::string& scene_file, const rt_background* bg = nullptr) {
-        if (!bg) {
+    explicit World(const std::string& scene_file, const rt_background* bg = nullptr, const rt_env_sampling* env = nullptr) {
+        if (!bg && !env) {
             check(rt_scene_load_file(scene_file.c_str(), &s_, &cam.c));
             return;
         }
         check(rt_scene_parse_file(scene_file.c_str(), &s_, &cam.c));  // uncommitted: the background is a builder
-        const int rc = rt_scene_set_background(s_, bg);
-        const int rc2 = rc < 0 ? rc : rt_scene_commit(s_);
+        const int rc = bg ? rt_scene_set_background(s_, bg) : 0;
+        const int rc1 = (rc < 0 || !env) ? rc : rt_scene_set_env_sampling(s_, env);
+        const int rc2 = rc1 < 0 ? rc1 : rt_scene_commit(s_);
         if (rc2 < 0) {
             const std::string msg = rt_last_error();
             rt_scene_destroy(s_);
@@ -389,6 +393,19 @@ class World {
         rt_background bg{};
         check(rt_scene_get_background(s_, &bg));
         return bg;
+    }
+    // rt_env_sampling helper: the background as one more light of integrator 1 (0 x 0: automatic table size)
+    static rt_env_sampling env_sampling_on(int width = 0, int height = 0) {
+        rt_env_sampling e{};
+        e.enabled = 1;
+        e.width = width;
+        e.height = height;
+        return e;
+    }
+    rt_env_sampling env_sampling() const {
+        rt_env_sampling e{};
+        check(rt_scene_get_env_sampling(s_, &e));
+        return e;
     }
     ~World() { rt_scene_destroy(s_); }
     World(const World&) = delete;
@@ -549,7 +566,7 @@ inline std::vector<double> denoise(int width, int height, const std::vector<doub
 
 // scene.rs:16-112 cornell_box_scene(), written against the mirrored types exactly as the reference writes it
 inline std::unique_ptr<World> cornell_box_scene(const std::string& cube_obj, double aspect_ratio = 1.0, uint64_t bvh_seed = 1,
-                                                const rt_background* bg = nullptr) {
+                                                const rt_background* bg = nullptr, const rt_env_sampling* env = nullptr) {
     auto tex = [](double r, double g, double b) { return std::make_shared<ConstantTexture>(Vec3(r, g, b)); };
     MaterialPtr red = std::make_shared<Lambertian>(tex(0.75, 0.25, 0.25));
     MaterialPtr white = std::make_shared<Lambertian>(tex(0.75, 0.75, 0.75));
@@ -568,7 +585,7 @@ inline std::unique_ptr<World> cornell_box_scene(const std::string& cube_obj, dou
         std::make_shared<Cube>(Vec3(300., 0., 100.), Vec3(380., 100., 180.), white),
     };
     Camera cam({Vec3(278., 278., -800.), Vec3(278., 278., 278.)}, Vec3(0., 1., 0.), 50., aspect_ratio, 0.0, 10.0);
-    return std::make_unique<World>(hitable_list, cam, HitableList{light}, bvh_seed, bg);  // scene.rs:100-111: lights = vec![light]
+    return std::make_unique<World>(hitable_list, cam, HitableList{light}, bvh_seed, bg, env);  // scene.rs:100-111: lights = vec![light]
 }
 
 }  // namespace rtamd_host

@@ -77,6 +77,10 @@ class rt_background(C.Structure):
     _fields_ = [("kind", C.c_int32), ("texture", C.c_int32), ("color0", C.c_double * 3), ("color1", C.c_double * 3), ("scale", C.c_double)]
 
 
+class rt_env_sampling(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("width", C.c_int32), ("height", C.c_int32)]
+
+
 BACKGROUND_KINDS = ("none", "constant", "gradient", "texture")
 SKY = ((1.0, 1.0, 1.0), (0.5, 0.7, 1.0))  # book 1's ray_color: white straight down, (0.5, 0.7, 1.0) straight up
 
@@ -154,6 +158,8 @@ _SIGS = [
     ("rt_scene_set_lights", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     ("rt_scene_set_background", C.c_int, [C.c_void_p, C.POINTER(rt_background)]),
     ("rt_scene_get_background", C.c_int, [C.c_void_p, C.POINTER(rt_background)]),
+    ("rt_scene_set_env_sampling", C.c_int, [C.c_void_p, C.POINTER(rt_env_sampling)]),
+    ("rt_scene_get_env_sampling", C.c_int, [C.c_void_p, C.POINTER(rt_env_sampling)]),
     ("rt_scene_cornell_box", C.c_int, [C.c_void_p, C.c_char_p, C.c_double, C.c_uint64, C.POINTER(rt_camera)]),
     ("rt_scene_load_file", C.c_int, [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(rt_camera)]),
     ("rt_scene_parse_file", C.c_int, [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(rt_camera)]),
@@ -202,6 +208,9 @@ _SIGS = [
     ("rt_debug_math_device", C.c_int, [C.c_int, C.c_size_t, _dp, _dp, _dp]),
     ("rt_debug_hit_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, C.c_double, C.c_double, _dp]),
     ("rt_debug_schedule", C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    ("rt_debug_env_table_device", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
+    ("rt_debug_env_sample_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, _dp]),
+    ("rt_debug_env_pdf_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, _dp]),
 ]
 ABI_SYMBOLS = [s[0] for s in _SIGS]
 
@@ -487,6 +496,20 @@ class World:
         _chk(self.L.rt_scene_get_background(self.h, C.byref(bg)))
         return dict(kind=bg.kind, texture=bg.texture, color0=tuple(bg.color0), color1=tuple(bg.color1), scale=bg.scale)
 
+    def set_env_sampling(self, enabled=True, width=0, height=0):
+        """rt_scene_set_env_sampling (before commit): the background becomes one more light of integrator 1, drawn from a width x height
+        table over (u, v) that every device builds from the background itself; 0, 0 = automatic (an image map: one cell per texel, halved
+        down to 4096 x 2048; anything else 256 x 128)."""
+        cfg = rt_env_sampling(1 if enabled else 0, int(width), int(height))
+        _chk(self.L.rt_scene_set_env_sampling(self.h, C.byref(cfg)))
+        return self
+
+    def env_sampling(self):
+        """rt_scene_get_env_sampling: dict(enabled, width, height) as set"""
+        cfg = rt_env_sampling()
+        _chk(self.L.rt_scene_get_env_sampling(self.h, C.byref(cfg)))
+        return dict(enabled=bool(cfg.enabled), width=cfg.width, height=cfg.height)
+
     def fingerprint(self):
         return int(self.L.rt_scene_fingerprint(self.h))
 
@@ -682,6 +705,28 @@ class World:
         out = np.zeros((r.shape[0], 12), dtype=np.float64)
         _chk(self.L.rt_debug_hit_device(self.h, int(kernel), r.shape[0], r.ctypes.data_as(_dp), float(t_min), float(t_max),
                                         out.ctypes.data_as(_dp)))
+        return out
+
+    def debug_env_table(self, device=0):
+        """rt_debug_env_table_device: the quantised weights q, uint32 [H, W] (row j = v cell j), as `device` built them"""
+        w, h = C.c_int(), C.c_int()
+        _chk(self.L.rt_debug_env_table_device(self.h, int(device), C.byref(w), C.byref(h), None))
+        q = np.zeros((h.value, w.value), dtype=np.uint32)
+        _chk(self.L.rt_debug_env_table_device(self.h, int(device), C.byref(w), C.byref(h), q.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return q
+
+    def debug_env_sample(self, xi, device=0):
+        """rt_debug_env_sample_device: xi [n, 4] -> [n, 4] = direction, pdf"""
+        x = np.ascontiguousarray(xi, dtype=np.float64).reshape(-1, 4)
+        out = np.zeros((x.shape[0], 4), dtype=np.float64)
+        _chk(self.L.rt_debug_env_sample_device(self.h, int(device), x.shape[0], x.ctypes.data_as(_dp), out.ctypes.data_as(_dp)))
+        return out
+
+    def debug_env_pdf(self, dirs, device=0):
+        """rt_debug_env_pdf_device: directions [n, 3] (any length) -> pdf [n] per solid angle"""
+        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        out = np.zeros(d.shape[0], dtype=np.float64)
+        _chk(self.L.rt_debug_env_pdf_device(self.h, int(device), d.shape[0], d.ctypes.data_as(_dp), out.ctypes.data_as(_dp)))
         return out
 
 

@@ -151,6 +151,15 @@ pub struct rt_background {
     pub scale: c_double,
 }
 
+/// include/rtamd.h rt_env_sampling (rt_scene_set_env_sampling; enabled 0 = off, the default; 0 x 0 = automatic table size)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct rt_env_sampling {
+    pub enabled: i32,
+    pub width: i32,
+    pub height: i32,
+}
+
 /// include/rtamd.h rt_adaptive_config (rt_default_adaptive_config fills it)
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -270,6 +279,8 @@ extern "C" {
     pub fn rt_scene_set_root(s: *mut rt_scene, object: c_int) -> c_int;
     pub fn rt_scene_set_background(s: *mut rt_scene, bg: *const rt_background) -> c_int;
     pub fn rt_scene_get_background(s: *const rt_scene, out: *mut rt_background) -> c_int;
+    pub fn rt_scene_set_env_sampling(s: *mut rt_scene, cfg: *const rt_env_sampling) -> c_int;
+    pub fn rt_scene_get_env_sampling(s: *const rt_scene, out: *mut rt_env_sampling) -> c_int;
     pub fn rt_scene_cornell_box(s: *mut rt_scene, cube_obj_path: *const c_char, aspect_ratio: c_double, bvh_seed: u64, cam_out: *mut rt_camera) -> c_int;
     pub fn rt_scene_load_file(path: *const c_char, out: *mut *mut rt_scene, cam_out: *mut rt_camera) -> c_int;
     pub fn rt_scene_parse_file(path: *const c_char, out: *mut *mut rt_scene, cam_out: *mut rt_camera) -> c_int;
@@ -312,6 +323,9 @@ extern "C" {
     pub fn rt_debug_math_device(op: c_int, n: usize, a_host: *const c_double, b_host: *const c_double, out_host: *mut c_double) -> c_int;
     pub fn rt_debug_hit_device(s: *const rt_scene, kernel: c_int, n: usize, rays_host: *const c_double, t_min: c_double, t_max: c_double, out_host: *mut c_double) -> c_int;
     pub fn rt_debug_schedule(tiles_owned: i64, n_waves: c_int, s_begin: c_int, s_end: c_int, sub_spp: c_int, job_units: c_int, out25: *mut c_int) -> c_int;
+    pub fn rt_debug_env_table_device(s: *const rt_scene, device: c_int, w: *mut c_int, h: *mut c_int, q_host: *mut u32) -> c_int;
+    pub fn rt_debug_env_sample_device(s: *const rt_scene, device: c_int, n: usize, xi4_host: *const c_double, out_host: *mut c_double) -> c_int;
+    pub fn rt_debug_env_pdf_device(s: *const rt_scene, device: c_int, n: usize, dirs_host: *const c_double, pdf_host: *mut c_double) -> c_int;
 }
 
 // ------------------------------------------------------------------ errors ----
@@ -494,6 +508,11 @@ impl SceneBuilder {
     pub fn set_sky(&mut self) -> Result<(), RtError> {
         self.set_background(&rt_background { kind: 2, texture: 0, color0: [1.0, 1.0, 1.0], color1: [0.5, 0.7, 1.0], scale: 1.0 })
     }
+    /// rt_scene_set_env_sampling: the background as one more light of integrator 1 (before commit; 0 x 0 = automatic table size)
+    pub fn set_env_sampling(&mut self, enabled: bool, width: i32, height: i32) -> Result<(), RtError> {
+        let cfg = rt_env_sampling { enabled: enabled as i32, width, height };
+        check(unsafe { rt_scene_set_env_sampling(self.raw, &cfg) }).map(|_| ())
+    }
     /// rt_scene_parse_file: a scene file's graph, left uncommitted (a background or lights may still be set)
     pub fn parse_file(path: &str) -> Result<(SceneBuilder, rt_camera), RtError> {
         let c = CString::new(path).unwrap();
@@ -538,6 +557,11 @@ impl Scene {
         let mut b = rt_background::default();
         check(unsafe { rt_scene_get_background(self.raw, &mut b) })?;
         Ok(b)
+    }
+    pub fn env_sampling(&self) -> Result<rt_env_sampling, RtError> {
+        let mut e = rt_env_sampling::default();
+        check(unsafe { rt_scene_get_env_sampling(self.raw, &mut e) })?;
+        Ok(e)
     }
     pub fn info(&self) -> Result<rt_scene_info, RtError> {
         let mut i = rt_scene_info::default();

@@ -2,17 +2,13 @@
 // Every function converts C++ exceptions into rt_status codes; nothing unwinds
 // across the boundary.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
-#include <map>
 #include <mutex>
 #include <new>
 #include <string>
-#include <thread>
-#include <utility>
 #include <vector>
 
 #include "common/rng.h"
@@ -20,6 +16,7 @@
 #include "device/adaptive.h"
 #include "device/denoise.h"
 #include "device/device.h"
+#include "host/frame.h"
 #include "host/scene.h"
 #include "rtamd.h"
 
@@ -57,8 +54,6 @@ static int guard(F&& f) {
         return RT_ERR_ARG;
     }
 }
-#define REQUIRE(c, msg) \
-    if (!(c)) throw RtError(RT_ERR_ARG, msg)
 
 static void not_committed_only(const rt_scene* s) {
     REQUIRE(s, "null scene");
@@ -97,103 +92,6 @@ void rt_default_params(rt_params* p) {
     p->time1 = 0.;
 }
 int rt_device_count(void) { return device_count(); }
-// Frame-sized device buffers of rt_render_multi (the gathered rows, the stitched frame, the ranks' own rows) are kept between calls:
-// allocating and freeing them cost every frame about a millisecond (hipFree waits for the device).  Per (device, size): at most
-// FRAME_POOL_KEEP idle buffers, and FRAME_POOL_BYTES of idle buffers in all -- a host that renders many resolutions or rank counts does
-// not pile up a frame per shape: beyond the cap the least recently returned buffers are freed; rt_release_workspaces frees them all.
-namespace {
-const size_t FRAME_POOL_KEEP = 4;
-const size_t FRAME_POOL_BYTES = size_t(1) << 30;
-struct IdleFrame {
-    int dev;
-    size_t bytes;
-    void* p;
-};
-std::mutex g_frame_pool_mu;
-std::vector<IdleFrame> g_frame_pool;  // in the order they were returned: the front is the least recently used
-void* frame_pool_take(int dev, size_t bytes) {
-    {
-        std::lock_guard<std::mutex> g(g_frame_pool_mu);
-        for (size_t i = g_frame_pool.size(); i-- > 0;)
-            if (g_frame_pool[i].dev == dev && g_frame_pool[i].bytes == bytes) {
-                void* p = g_frame_pool[i].p;
-                g_frame_pool.erase(g_frame_pool.begin() + (ptrdiff_t)i);
-                return p;
-            }
-    }
-    return dev_alloc(bytes);  // (the caller has made `dev` current)
-}
-void frame_pool_give(int dev, size_t bytes, void* p) {  // the caller has made `dev` current
-    std::vector<IdleFrame> drop;
-    {
-        std::lock_guard<std::mutex> g(g_frame_pool_mu);
-        size_t same = 0, total = bytes;
-        for (const IdleFrame& f : g_frame_pool) {
-            same += (f.dev == dev && f.bytes == bytes) ? 1 : 0;
-            total += f.bytes;
-        }
-        if (same >= FRAME_POOL_KEEP || bytes > FRAME_POOL_BYTES) {
-            drop.push_back(IdleFrame{dev, bytes, p});
-        } else {
-            g_frame_pool.push_back(IdleFrame{dev, bytes, p});
-            while (total > FRAME_POOL_BYTES && g_frame_pool.size() > 1) {  // evict the least recently returned
-                total -= g_frame_pool.front().bytes;
-                drop.push_back(g_frame_pool.front());
-                g_frame_pool.erase(g_frame_pool.begin());
-            }
-        }
-    }
-    for (const IdleFrame& f : drop) {
-        try {
-            if (f.dev != dev) dev_set_device(f.dev);
-            dev_free(f.p);
-        } catch (...) {
-        }
-    }
-    if (!drop.empty()) {
-        try {
-            dev_set_device(dev);
-        } catch (...) {
-        }
-    }
-}
-size_t frame_pool_release() {
-    std::vector<IdleFrame> all;
-    {
-        std::lock_guard<std::mutex> g(g_frame_pool_mu);
-        all.swap(g_frame_pool);
-    }
-    size_t freed = 0;
-    for (const IdleFrame& f : all) {
-        try {
-            dev_set_device(f.dev);
-            dev_free(f.p);
-            freed += f.bytes;
-        } catch (...) {
-        }
-    }
-    return freed;
-}
-// rt_params.device >= 0 makes that device current for the call only: the caller's current device comes back
-struct DeviceScope {
-    int prev = -1;
-    explicit DeviceScope(int want) {
-        if (want < 0) return;
-        prev = dev_get_device();
-        if (prev != want) dev_set_device(want);
-        else prev = -1;
-    }
-    ~DeviceScope() {
-        if (prev < 0) return;
-        try {
-            dev_set_device(prev);
-        } catch (...) {
-        }
-    }
-    DeviceScope(const DeviceScope&) = delete;
-    DeviceScope& operator=(const DeviceScope&) = delete;
-};
-}  // namespace
 
 int64_t rt_release_workspaces(void) {
     int64_t n = 0;
@@ -651,87 +549,29 @@ int rt_scene_info_get(const rt_scene* s, rt_scene_info* out) {
     });
 }
 
-// ---- render --------------------------------------------------------------
-// owned >= 0: a plan for that many tiles in place of the rank's partition (rt_render_adaptive's passes over a tile list)
-static RenderPlan make_plan(const rt_params* p, int64_t owned = -1) {
-    REQUIRE(p, "null params");
-    REQUIRE(p->width > 0 && p->height > 0, "width/height must be positive");
-    REQUIRE(p->spp > 0, "spp must be positive");
-    REQUIRE(p->max_depth >= 0, "max_depth must be >= 0");
-    REQUIRE(p->world >= 1 && p->rank >= 0 && p->rank < p->world, "bad rank/world");
-    REQUIRE((p->kernel >= 0 && p->kernel <= 2) || p->kernel == 5 || p->kernel == 6, "unknown kernel id (0 auto, 1, 2, 5, 6)");
-    REQUIRE(p->integrator >= 0 && p->integrator <= 2, "unknown integrator id");
-    REQUIRE(std::isfinite(p->time0) && std::isfinite(p->time1) && p->time1 >= p->time0, "shutter: time1 must be >= time0 and both finite");
-    RenderPlan pl;
-    pl.width = p->width; pl.height = p->height; pl.spp = p->spp; pl.max_depth = p->max_depth;
-    pl.t_min = p->t_min; pl.seed = p->seed; pl.rank = p->rank; pl.world = p->world;
-    pl.tiles_x = (p->width + TILE_W - 1) / TILE_W;
-    pl.tiles_y = (p->height + TILE_H - 1) / TILE_H;
-    pl.tiles_total = (int64_t)pl.tiles_x * pl.tiles_y;
-    pl.tiles_owned = (pl.tiles_total - p->rank + p->world - 1) / p->world;
-    if (pl.tiles_owned < 0) pl.tiles_owned = 0;
-    if (owned >= 0) pl.tiles_owned = owned;
-    pl.kernel = p->kernel;
-    pl.integrator = p->integrator;
-    pl.time0 = p->time0;
-    pl.time1 = p->time1;
-    // One launch renders all sample indices unless the caller splits them (rt_params.spp_chunk): samples are folded into the
-    // accumulator inside the kernel, unit by unit, so no per-launch sample buffer bounds the launch size.
-    int chunk = p->spp_chunk > 0 ? p->spp_chunk : p->spp;
-    if (chunk > p->spp) chunk = p->spp;
-    // one work unit = 64 pixels x sub_spp samples (a wave works through it with in-wave regeneration and fetches the next
-    // one as soon as its pool is empty).  Many units balance the 4096 resident waves at the end of a launch: aim at
-    // >= ~12 units per wave, 4 <= sub_spp <= 8 (measured on the headline workload: 4: 2144, 8: 2166, 16: 2104 Msamples/s).
-    int64_t want_units = 12 * 4096;
-    int64_t subs = std::max<int64_t>(1, want_units / std::max<int64_t>(1, pl.tiles_owned));
-    int sub = (int)((chunk + subs - 1) / subs);
-    pl.sub_spp = std::max(std::min(chunk, 4), std::min(sub, 8));
-    const int tun_sub_spp = tuning().sub_spp;
-    if (tun_sub_spp > 0) pl.sub_spp = std::max(1, std::min(std::min(chunk, 8), tun_sub_spp));  // rt_tuning (A/B runs)
-    {   // at most 2^31 jobs per launch; 2^30 uniform units leave room for the tapered end of the schedule (host/schedule.cpp: up to
-        // 1.2x as many units as a uniform cut, single-unit jobs)
-        const int64_t max_chunk = (int64_t(1) << 30) / std::max<int64_t>(1, pl.tiles_owned) * pl.sub_spp;
-        if (max_chunk < 1) throw RtError(RT_ERR_UNSUPPORTED, "image too large for one rank");
-        if (chunk > max_chunk) chunk = (int)max_chunk;
-    }
-    pl.spp_chunk = chunk;
-    return pl;
-}
-
+// ---- render (the frame driver: host/frame.h) --------------------------------
 int64_t rt_tiles_total(const rt_params* p) {
     if (!p || p->width <= 0 || p->height <= 0) return RT_ERR_ARG;
-    return (int64_t)((p->width + TILE_W - 1) / TILE_W) * ((p->height + TILE_H - 1) / TILE_H);
+    return tiles_total(p->width, p->height);
 }
 int64_t rt_tiles_owned(const rt_params* p) {
     if (!p || p->width <= 0 || p->height <= 0 || p->world < 1 || p->rank < 0 || p->rank >= p->world) return RT_ERR_ARG;
-    int64_t total = rt_tiles_total(p);
-    return (total - p->rank + p->world - 1) / p->world;
+    return tiles_owned(tiles_total(p->width, p->height), p->rank, p->world);
 }
 
 int rt_render_tiles_device(const rt_scene* s, const rt_camera* cam, const rt_params* p, double* d_tiles, void* hip_stream,
                            rt_stats* stats) {
     return guard([&] {
         REQUIRE(s && cam && d_tiles, "null argument");
-        if (!s->committed) throw RtError(RT_ERR_NOT_COMMITTED, "rt_scene_commit has not been called");
-        if (device_count() < 1) throw RtError(RT_ERR_NO_DEVICE, "no HIP device: librtamd has no CPU fallback");
-        auto t0 = std::chrono::steady_clock::now();
-        RenderPlan pl = make_plan(p);
+        require_committed(*s);
+        require_device();
+        const CallClock clock;
+        const RenderPlan pl = make_plan(p);
         DeviceScope dev_scope(p->device);  // (d_tiles and hip_stream must belong to it; the caller's current device is restored)
-        CameraDev cd = make_camera(*cam);
+        const CameraDev cd = make_camera(*cam);
         if (stats) std::memset(stats, 0, sizeof(*stats));
         render_tiles(*s, cd, pl, d_tiles, hip_stream, stats);
-        if (stats) {
-            stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            // pixels actually inside the image among this rank's tiles
-            uint64_t px = 0;
-            for (int64_t lt = 0; lt < pl.tiles_owned; lt++) {
-                int64_t t = lt * pl.world + pl.rank;
-                int tx = (int)(t % pl.tiles_x), ty = (int)(t / pl.tiles_x);
-                int w = std::min(TILE_W, pl.width - tx * TILE_W), h = std::min(TILE_H, pl.height - ty * TILE_H);
-                px += (uint64_t)w * h;
-            }
-            stats->samples = px * (uint64_t)pl.spp;
-        }
+        clock.stamp(stats, pixels_in_image(pl) * (uint64_t)pl.spp);
         return (int)RT_OK;
     });
 }
@@ -740,36 +580,14 @@ int rt_render_accumulate_device(const rt_scene* s, const rt_camera* cam, const r
                                 double* d_accum, void* hip_stream, rt_stats* stats) {
     return guard([&] {
         REQUIRE(s && cam && p && d_accum, "null argument");
-        if (!s->committed) throw RtError(RT_ERR_NOT_COMMITTED, "rt_scene_commit has not been called");
-        if (device_count() < 1) throw RtError(RT_ERR_NO_DEVICE, "no HIP device: librtamd has no CPU fallback");
-        auto t0 = std::chrono::steady_clock::now();
-        RenderPlan pl = make_plan(p);
-        REQUIRE(sample_begin >= 0 && sample_begin < sample_end && sample_end <= pl.spp, "sample range: 0 <= begin < end <= spp");
-        REQUIRE(pl.integrator == 0 || pl.integrator == 1, "resumable rendering: integrators 0 and 1");
-        pl.s_first = sample_begin;
-        pl.s_last = sample_end;
-        pl.ext_accum = d_accum;
-        DeviceScope dev_scope(p->device);  // (d_accum and hip_stream must belong to it)
-        CameraDev cd = make_camera(*cam);
-        if (stats) std::memset(stats, 0, sizeof(*stats));
-        render_tiles(*s, cd, pl, nullptr, hip_stream, stats);
-        if (stats) {
-            stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            uint64_t px = 0;
-            for (int64_t lt = 0; lt < pl.tiles_owned; lt++) {
-                int64_t t = lt * pl.world + pl.rank;
-                int tx = (int)(t % pl.tiles_x), ty = (int)(t / pl.tiles_x);
-                px += (uint64_t)std::min(TILE_W, pl.width - tx * TILE_W) * std::min(TILE_H, pl.height - ty * TILE_H);
-            }
-            stats->samples = px * (uint64_t)(sample_end - sample_begin);
-        }
+        accumulate_device(*s, *cam, *p, sample_begin, sample_end, d_accum, hip_stream, stats);
         return (int)RT_OK;
     });
 }
 int rt_accum_finalize_device(const rt_params* p, const double* d_accum, double* d_tiles, void* hip_stream) {
     return guard([&] {
         REQUIRE(p && d_accum && d_tiles, "null argument");
-        if (device_count() < 1) throw RtError(RT_ERR_NO_DEVICE, "no HIP device: librtamd has no CPU fallback");
+        require_device();
         const RenderPlan pl = make_plan(p);
         DeviceScope dev_scope(p->device);
         finalize_tiles(pl, d_accum, d_tiles, hip_stream);
@@ -779,33 +597,13 @@ int rt_accum_finalize_device(const rt_params* p, const double* d_accum, double* 
 
 int64_t rt_accum_state_doubles(const rt_params* p) {
     const int64_t n = rt_tiles_owned(p);
-    return n < 0 ? n : std::max<int64_t>(1, n) * TILE_PIX * 3;
+    return n < 0 ? n : (int64_t)row_doubles(n);
 }
-namespace {
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) dev_free(p);
-    }
-};
-}  // namespace
 int rt_render_accumulate(const rt_scene* s, const rt_camera* cam, const rt_params* p, int32_t sample_begin, int32_t sample_end,
                          double* accum_state, rt_stats* stats) {
     return guard([&] {
         REQUIRE(s && cam && p && accum_state, "null argument");
-        if (device_count() < 1) throw RtError(RT_ERR_NO_DEVICE, "no HIP device: librtamd has no CPU fallback");
-        const int64_t n = rt_accum_state_doubles(p);
-        REQUIRE(n > 0, "bad image size or partition");
-        DeviceScope dev_scope(p->device);
-        DevBuf acc;
-        acc.p = dev_alloc((size_t)n * sizeof(double));
-        // the state always goes to the device: a rank that owns no tile (more ranks than tiles) launches nothing, and what comes back must
-        // be what went in -- zeros at sample_begin == 0 -- not uninitialised device memory
-        if (sample_begin == 0) std::memset(accum_state, 0, (size_t)n * sizeof(double));
-        dev_copy_to_device(acc.p, accum_state, (size_t)n * sizeof(double));
-        const int rc = rt_render_accumulate_device(s, cam, p, sample_begin, sample_end, (double*)acc.p, nullptr, stats);
-        if (rc != RT_OK) return rc;
-        dev_copy_to_host(accum_state, acc.p, (size_t)n * sizeof(double));
+        accumulate_host(*s, *cam, *p, sample_begin, sample_end, accum_state, stats);
         return (int)RT_OK;
     });
 }
@@ -813,18 +611,7 @@ int rt_accum_finalize(const rt_params* p, const double* accum_state, double* out
     return guard([&] {
         REQUIRE(p && accum_state && out_rgb, "null argument");
         REQUIRE(p->world == 1 && p->rank == 0, "rt_accum_finalize stitches a whole frame: rank / world must be 0 / 1");
-        if (device_count() < 1) throw RtError(RT_ERR_NO_DEVICE, "no HIP device: librtamd has no CPU fallback");
-        const RenderPlan pl = make_plan(p);
-        const size_t n = (size_t)std::max<int64_t>(1, pl.tiles_owned) * TILE_PIX * 3, frame_bytes = (size_t)pl.width * pl.height * 3 * sizeof(double);
-        DeviceScope dev_scope(p->device);
-        DevBuf acc, tiles, frame;
-        acc.p = dev_alloc(n * sizeof(double));
-        tiles.p = dev_alloc(n * sizeof(double));
-        frame.p = dev_alloc(frame_bytes);
-        dev_copy_to_device(acc.p, accum_state, n * sizeof(double));
-        finalize_tiles(pl, (const double*)acc.p, (double*)tiles.p, nullptr);
-        assemble_frame(pl, (const double*)tiles.p, pl.tiles_owned, (double*)frame.p, nullptr);
-        dev_copy_to_host(out_rgb, frame.p, frame_bytes);
+        finalize_host(*p, accum_state, out_rgb);
         return (int)RT_OK;
     });
 }
@@ -847,81 +634,7 @@ int rt_render_adaptive(const rt_scene* s, const rt_camera* cam, const rt_params*
         REQUIRE(!std::isnan(cfg->threshold) && cfg->threshold >= 0., "threshold must be >= 0 (not NaN)");
         if (p->kernel == 6 || p->integrator == 2)
             throw RtError(RT_ERR_UNSUPPORTED, "rt_render_adaptive runs with kernels 0 / 1 / 2 / 5 and integrators 0 / 1");
-        const RenderPlan full = make_plan(p);
-        if (!s->committed) throw RtError(RT_ERR_NOT_COMMITTED, "rt_scene_commit has not been called");
-        if (!adaptive_test || device_count() < 1) throw RtError(RT_ERR_NO_DEVICE, "no HIP device: librtamd has no CPU fallback");
-        auto t0 = std::chrono::steady_clock::now();
-        DeviceScope dev_scope(p->device);
-        const CameraDev cd = make_camera(*cam);
-        const int64_t T = full.tiles_total;
-        const size_t acc_bytes = (size_t)T * TILE_PIX * 3 * sizeof(double), frame_bytes = (size_t)full.width * full.height * 3 * sizeof(double);
-        // the frame's running sums S, the half snapshot S_m, a pass's compact accumulator (also the finalized tiles at the end), the active
-        // list, the stop flags and errors of a test, the tiles' final spp, the frame
-        DevBuf acc, half, compact, list, stop, err, tile_spp, frame;
-        acc.p = dev_alloc(acc_bytes);
-        half.p = dev_alloc(acc_bytes);
-        compact.p = dev_alloc(acc_bytes);
-        list.p = dev_alloc((size_t)T * sizeof(int32_t));
-        stop.p = dev_alloc((size_t)T * sizeof(int32_t));
-        err.p = dev_alloc((size_t)T * sizeof(double));
-        tile_spp.p = dev_alloc((size_t)T * sizeof(int32_t));
-        frame.p = dev_alloc(frame_bytes);
-        std::vector<int32_t> active((size_t)T), n_t((size_t)T, full.spp), h_stop;
-        for (int64_t t = 0; t < T; t++) active[(size_t)t] = (int32_t)t;
-        auto tile_px = [&](int64_t t) {
-            const int tx = (int)(t % full.tiles_x), ty = (int)(t / full.tiles_x);
-            return (uint64_t)std::min(TILE_W, full.width - tx * TILE_W) * (uint64_t)std::min(TILE_H, full.height - ty * TILE_H);
-        };
-        rt_stats sum{};
-        uint64_t samples = 0;
-        bool first_pass = true;
-        const int h = cfg->min_spp / 2;
-        // passes [0, h), [h, 2h), [2h, 4h), ... capped at spp; a test after every pass that ends at n = 2m < spp
-        for (int begin = 0, end = h; begin < full.spp && !active.empty(); begin = end, end = (int)std::min<int64_t>((int64_t)end * 2, full.spp)) {
-            const int64_t na = (int64_t)active.size();
-            dev_copy_to_device(list.p, active.data(), (size_t)na * sizeof(int32_t));
-            if (begin > 0) adaptive_copy_tiles((double*)compact.p, nullptr, (const double*)acc.p, (const int32_t*)list.p, na, nullptr);
-            RenderPlan pl = make_plan(p, na);
-            pl.s_first = begin;
-            pl.s_last = end;
-            pl.ext_accum = (double*)compact.p;
-            pl.tile_list = (const int32_t*)list.p;
-            rt_stats st{};
-            render_tiles(*s, cd, pl, nullptr, nullptr, &st);
-            adaptive_copy_tiles((double*)acc.p, (const int32_t*)list.p, (const double*)compact.p, nullptr, na, nullptr);
-            for (int32_t t : active) samples += tile_px(t) * (uint64_t)(end - begin);
-            if (first_pass) {
-                sum = st;
-                first_pass = false;
-            } else {
-                sum.kernel_ms += st.kernel_ms;
-                sum.launches += st.launches;
-            }
-            if (begin == 0) {  // S_h: the first half snapshot, every tile
-                adaptive_copy_tiles((double*)half.p, nullptr, (const double*)acc.p, nullptr, T, nullptr);
-            } else if (end < full.spp) {
-                adaptive_test(full, (const double*)acc.p, (double*)half.p, (const int32_t*)list.p, na, end, end / 2, cfg->threshold, (int32_t*)stop.p,
-                              (double*)err.p, nullptr);
-                h_stop.resize((size_t)na);
-                dev_copy_to_host(h_stop.data(), stop.p, (size_t)na * sizeof(int32_t));
-                std::vector<int32_t> next;
-                for (int64_t i = 0; i < na; i++) {
-                    if (h_stop[(size_t)i]) n_t[(size_t)active[(size_t)i]] = end;
-                    else next.push_back(active[(size_t)i]);
-                }
-                active.swap(next);
-            }
-        }
-        dev_copy_to_device(tile_spp.p, n_t.data(), (size_t)T * sizeof(int32_t));
-        adaptive_finalize(full, (const double*)acc.p, (const int32_t*)tile_spp.p, (double*)compact.p, nullptr);
-        assemble_frame(full, (const double*)compact.p, T, (double*)frame.p, nullptr);
-        dev_copy_to_host(out_rgb, frame.p, frame_bytes);
-        if (out_tile_spp) std::memcpy(out_tile_spp, n_t.data(), (size_t)T * sizeof(int32_t));
-        if (stats) {
-            *stats = sum;
-            stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            stats->samples = samples;
-        }
+        render_adaptive(*s, *cam, *p, *cfg, out_rgb, out_tile_spp, stats);
         return (int)RT_OK;
     });
 }
@@ -931,20 +644,15 @@ int rt_render_sppm_tiles_device(const rt_scene* s, const rt_camera* cam, const r
     return guard([&] {
         REQUIRE(s && cam && p && cfg && d_tiles, "null argument");
         REQUIRE(p->spp > 0, "spp must be positive");
-        if (!s->committed) throw RtError(RT_ERR_NOT_COMMITTED, "rt_scene_commit has not been called");
-        if (device_count() < 1) throw RtError(RT_ERR_NO_DEVICE, "no HIP device: librtamd has no CPU fallback");
-        auto t0 = std::chrono::steady_clock::now();
-        rt_params q = *p;
-        q.integrator = 0;
-        RenderPlan pl = make_plan(&q);
+        require_committed(*s);
+        require_device();
+        const CallClock clock;
+        const RenderPlan pl = make_sppm_plan(*p);
         DeviceScope dev_scope(p->device);
-        CameraDev cd = make_camera(*cam);
+        const CameraDev cd = make_camera(*cam);
         rt_stats st{};
         render_sppm(*s, cd, pl, *cfg, d_tiles, nullptr, hip_stream, &st, nullptr);
-        if (stats) {
-            *stats = st;
-            stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        }
+        clock.finish(stats, st);
         return (int)RT_OK;
     });
 }
@@ -980,294 +688,45 @@ int rt_camera_frame_from(const rt_camera* cam, rt_camera_frame* out) {
         return (int)RT_OK;
     });
 }
-static int render_host(const rt_scene* s, const CameraDev& cd, const rt_params* p, double* out_rgb, rt_stats* stats);
+static void require_finite(const rt_camera_frame& f) {
+    for (const double* v : {f.origin, f.lower_left_corner, f.horizontal, f.vertical, f.u, f.v, f.w})
+        for (int i = 0; i < 3; i++) REQUIRE(std::isfinite(v[i]), "camera frame must be finite");
+    REQUIRE(std::isfinite(f.lens_radius), "camera frame must be finite");
+}
 int rt_render_camera_frame(const rt_scene* s, const rt_camera_frame* frame, const rt_params* p, double* out_rgb, rt_stats* stats) {
     return guard([&] {
         REQUIRE(s && frame && p && out_rgb, "null argument");
-        for (const double* v : {frame->origin, frame->lower_left_corner, frame->horizontal, frame->vertical, frame->u, frame->v, frame->w})
-            for (int i = 0; i < 3; i++) REQUIRE(std::isfinite(v[i]), "camera frame must be finite");
-        REQUIRE(std::isfinite(frame->lens_radius), "camera frame must be finite");
-        return render_host(s, camera_from_frame(*frame), p, out_rgb, stats);
+        require_finite(*frame);
+        render_frame(*s, camera_from_frame(*frame), *p, out_rgb, stats);
+        return (int)RT_OK;
     });
 }
 int rt_render(const rt_scene* s, const rt_camera* cam, const rt_params* p, double* out_rgb, rt_stats* stats) {
     return guard([&] {
         REQUIRE(s && cam && p && out_rgb, "null argument");
-        return render_host(s, make_camera(*cam), p, out_rgb, stats);
+        render_frame(*s, make_camera(*cam), *p, out_rgb, stats);
+        return (int)RT_OK;
     });
 }
-static int render_host(const rt_scene* s, const CameraDev& cd, const rt_params* p, double* out_rgb, rt_stats* stats) {
-    {
-        if (!s->committed) throw RtError(RT_ERR_NOT_COMMITTED, "rt_scene_commit has not been called");
-        if (device_count() < 1) throw RtError(RT_ERR_NO_DEVICE, "no HIP device: librtamd has no CPU fallback");
-        auto t0 = std::chrono::steady_clock::now();
-        DeviceScope dev_scope(p->device);
-        RenderPlan pl = make_plan(p);
-        if (stats) std::memset(stats, 0, sizeof(*stats));
-        struct Buf {
-            void* p = nullptr;
-            ~Buf() {
-                if (p) dev_free(p);
-            }
-        } tiles, frame;
-        size_t tile_bytes = (size_t)std::max<int64_t>(1, pl.tiles_owned) * TILE_PIX * 3 * sizeof(double);
-        size_t frame_bytes = (size_t)pl.width * pl.height * 3 * sizeof(double);
-        tiles.p = dev_alloc(tile_bytes);
-        frame.p = dev_alloc(frame_bytes);
-        rt_stats st{};
-        render_tiles(*s, cd, pl, (double*)tiles.p, nullptr, &st);
-        if (pl.world == 1) {
-            assemble_frame(pl, (const double*)tiles.p, pl.tiles_owned, (double*)frame.p, nullptr);
-            dev_copy_to_host(out_rgb, frame.p, frame_bytes);
-        } else {
-            // only this rank's tiles: others stay 0 in the caller's frame
-            std::vector<double> h((size_t)pl.tiles_owned * TILE_PIX * 3);
-            dev_copy_to_host(h.data(), tiles.p, h.size() * sizeof(double));
-            std::memset(out_rgb, 0, frame_bytes);
-            for (int64_t lt = 0; lt < pl.tiles_owned; lt++) {
-                int64_t t = lt * pl.world + pl.rank;
-                int tx = (int)(t % pl.tiles_x), ty = (int)(t / pl.tiles_x);
-                for (int pix = 0; pix < TILE_PIX; pix++) {
-                    int x = tx * TILE_W + (pix & 7), y = ty * TILE_H + (pix >> 3);
-                    if (x >= pl.width || y >= pl.height) continue;
-                    for (int c = 0; c < 3; c++) out_rgb[((size_t)y * pl.width + x) * 3 + c] = h[((size_t)lt * TILE_PIX + pix) * 3 + c];
-                }
-            }
-        }
-        if (stats) {
-            *stats = st;
-            stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            uint64_t px = 0;
-            for (int64_t lt = 0; lt < pl.tiles_owned; lt++) {
-                int64_t t = lt * pl.world + pl.rank;
-                int tx = (int)(t % pl.tiles_x), ty = (int)(t / pl.tiles_x);
-                px += (uint64_t)std::min(TILE_W, pl.width - tx * TILE_W) * std::min(TILE_H, pl.height - ty * TILE_H);
-            }
-            stats->samples = px * (uint64_t)pl.spp;
-        }
-        return (int)RT_OK;
-    }
-}
 
-}  // extern "C"
-
-// ---- the frame across the GPUs of one node (camera.rs:74-126 has the fan-out and the stitch inside capture_image) ----
-namespace {
-struct DevMem {  // device memory that remembers which device it lives on
-    void* p = nullptr;
-    int device = -1;
-    DevMem() = default;
-    DevMem(const DevMem&) = delete;
-    DevMem& operator=(const DevMem&) = delete;
-    size_t size = 0;
-    void alloc(int dev, size_t bytes) {
-        dev_set_device(dev);
-        p = frame_pool_take(dev, bytes);
-        device = dev;
-        size = bytes;
-    }
-    ~DevMem() {
-        if (!p) return;
-        try {
-            dev_set_device(device);
-            frame_pool_give(device, size, p);
-        } catch (...) {
-        }
-    }
-};
-struct ExchangeLease {
-    Exchange* e = nullptr;
-    bool failed = false;  // an exchange call threw: the communicators are destroyed instead of going back into the cache
-    ~ExchangeLease() { exchange_close(e, failed); }
-};
-}  // namespace
-
-// per_rank(rank plan, destination rows on the rank's device, stats) renders one rank's tiles; it runs on its own host thread with
-// the rank's device current.
-template <class F>
-static int render_fanout(const rt_params* p, int n_devices, const int* device_ids, double* out_rgb, rt_stats* stats, F&& per_rank) {
-    REQUIRE(p && out_rgb, "null argument");
-    REQUIRE(p->world == 1 && p->rank == 0, "rt_render_multi partitions the frame itself: rank / world must be 0 / 1");
-    const int visible = device_count();
-    if (visible < 1) throw RtError(RT_ERR_NO_DEVICE, "no HIP device: librtamd has no CPU fallback");
-    REQUIRE(n_devices >= 0 && n_devices <= 4096, "n_devices out of range");
-    const int n = n_devices == 0 ? visible : n_devices;
-    std::vector<int> ids((size_t)n);
-    for (int i = 0; i < n; i++) {
-        ids[(size_t)i] = device_ids ? device_ids[i] : i;
-        if (ids[(size_t)i] < 0 || ids[(size_t)i] >= visible)
-            throw RtError(RT_ERR_NO_DEVICE, "device ordinal " + std::to_string(ids[(size_t)i]) + " of rank " + std::to_string(i) + " is not visible (" +
-                                                std::to_string(visible) + " device(s))");
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    auto ms_since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(t - t0).count(); };
-    const int caller_device = dev_get_device();
-    struct Restore {
-        int d;
-        ~Restore() {
-            try {
-                dev_set_device(d);
-            } catch (...) {
-            }
-        }
-    } restore{caller_device};
-    const bool force = tuning().multi_force_rccl != 0;
-    const int root = ids[0];
-    std::vector<RenderPlan> plans((size_t)n);
-    for (int i = 0; i < n; i++) {
-        rt_params q = *p;
-        q.rank = i;
-        q.world = n;
-        q.device = -1;
-        plans[(size_t)i] = make_plan(&q);
-    }
-    const int64_t stride = plans[0].tiles_owned;  // rank 0 owns the most tiles: every rank's rows are padded to it
-    const size_t row_doubles = (size_t)std::max<int64_t>(1, stride) * TILE_PIX * 3;
-    const size_t frame_bytes = (size_t)p->width * p->height * 3 * sizeof(double);
-    DevMem gathered, frame;
-    gathered.alloc(root, (size_t)n * row_doubles * sizeof(double));
-    frame.alloc(root, frame_bytes);
-    // a rank on the root's device renders straight into its slot of the gathered buffer; the others (every rank when the
-    // exchange is forced) into a row of their own on their device, which then travels
-    std::vector<DevMem> rows((size_t)n);
-    std::vector<double*> dst((size_t)n);
-    std::vector<int> uniq;  // comm rank r = uniq[r]; the root's device first
-    auto comm_rank = [&](int dev) {
-        for (size_t r = 0; r < uniq.size(); r++)
-            if (uniq[r] == dev) return (int)r;
-        uniq.push_back(dev);
-        return (int)uniq.size() - 1;
-    };
-    comm_rank(root);
-    std::vector<RowMove> moves((size_t)n, RowMove{0, nullptr, 0, nullptr, 0});  // moves[i].count == 0: rank i's rows stay where they are rendered
-    size_t n_moves = 0;
-    for (int i = 0; i < n; i++) {
-        double* slot = (double*)gathered.p + (size_t)i * row_doubles;
-        if (ids[(size_t)i] == root && !force) {
-            dst[(size_t)i] = slot;
-        } else {
-            rows[(size_t)i].alloc(ids[(size_t)i], row_doubles * sizeof(double));
-            dst[(size_t)i] = (double*)rows[(size_t)i].p;
-            const size_t count = (size_t)plans[(size_t)i].tiles_owned * TILE_PIX * 3;
-            if (count) {
-                moves[(size_t)i] = RowMove{comm_rank(ids[(size_t)i]), (const double*)rows[(size_t)i].p, 0, slot, count};
-                n_moves++;
-            }
-        }
-    }
-    // the communicators BEFORE the renders start (creating them is the expensive part of a first call and no part of the exchange)
-    ExchangeLease lease;
-    double comm_init_ms = 0.;
-    if (n_moves) {
-        const auto tc = std::chrono::steady_clock::now();
-        bool created = false;
-        lease.e = exchange_open(uniq, &created);
-        if (created) comm_init_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc).count();
-    }
-    std::mutex post_mu;  // one rank at a time drives the communicators (exchange_post)
-    std::vector<rt_stats> st((size_t)n);
-    std::vector<int> rc((size_t)n, (int)RT_OK);
-    std::vector<std::string> msg((size_t)n);
-    std::vector<double> posted_ms((size_t)n, 0.);
-    auto work = [&](int i) {
-        try {
-            dev_set_device(ids[(size_t)i]);
-            std::memset(&st[(size_t)i], 0, sizeof(rt_stats));
-            per_rank(plans[(size_t)i], dst[(size_t)i], &st[(size_t)i]);
-            if (moves[(size_t)i].count) {  // this rank's rows leave NOW: the ranks still rendering do not hold them up
-                std::lock_guard<std::mutex> g(post_mu);
-                try {
-                    exchange_post(lease.e, moves[(size_t)i]);
-                } catch (...) {
-                    lease.failed = true;
-                    throw;
-                }
-                posted_ms[(size_t)i] = ms_since(std::chrono::steady_clock::now());
-            }
-        } catch (const RtError& e) {
-            rc[(size_t)i] = e.code;
-            msg[(size_t)i] = e.msg;
-        } catch (const std::exception& e) {
-            rc[(size_t)i] = RT_ERR_INTERNAL;
-            msg[(size_t)i] = e.what();
-        } catch (...) {
-            rc[(size_t)i] = RT_ERR_INTERNAL;
-            msg[(size_t)i] = "unknown error";
-        }
-    };
-    {
-        std::vector<std::thread> th;
-        for (int i = 1; i < n; i++) th.emplace_back(work, i);
-        work(0);  // rank 0 on the calling thread, as the reference's caller blocks in capture_image
-        for (auto& t : th) t.join();
-    }
-    const auto t1 = std::chrono::steady_clock::now();
-    // ---- the exchange: every posted row has to arrive in its slot on the root device (also after a failed rank: nothing may still be in
-    //      flight when the buffers go back to the pool)
-    if (lease.e) {
-        try {
-            exchange_wait(lease.e);
-        } catch (...) {
-            lease.failed = true;
-            throw;
-        }
-    }
-    for (int i = 0; i < n; i++)
-        if (rc[(size_t)i] != RT_OK) throw RtError(rc[(size_t)i], "rank " + std::to_string(i) + " (device " + std::to_string(ids[(size_t)i]) + "): " + msg[(size_t)i]);
-    const auto t2 = std::chrono::steady_clock::now();
-    dev_set_device(root);
-    rt_params whole = *p;
-    whole.rank = 0;
-    whole.world = n;
-    assemble_frame(make_plan(&whole), (const double*)gathered.p, stride, (double*)frame.p, nullptr);
-    dev_copy_to_host(out_rgb, frame.p, frame_bytes);
-    const auto t3 = std::chrono::steady_clock::now();
-    if (stats) {
-        for (int i = 0; i < n; i++) {
-            stats[i] = st[(size_t)i];
-            uint64_t px = 0;
-            const RenderPlan& pl = plans[(size_t)i];
-            for (int64_t lt = 0; lt < pl.tiles_owned; lt++) {
-                const int64_t t = lt * pl.world + pl.rank;
-                const int tx = (int)(t % pl.tiles_x), ty = (int)(t / pl.tiles_x);
-                px += (uint64_t)std::min(TILE_W, pl.width - tx * TILE_W) * std::min(TILE_H, pl.height - ty * TILE_H);
-            }
-            stats[i].samples = px * (uint64_t)pl.spp;
-            stats[i].posted_ms = posted_ms[(size_t)i];
-        }
-        stats[0].seconds = std::chrono::duration<double>(t3 - t0).count();
-        stats[0].exchange_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();  // the last rank's finish (the join) -> all rows on the root
-        stats[0].reserved[2] = (uint64_t)(stats[0].exchange_ms * 1e3);
-        stats[0].reserved[3] = (uint64_t)n_moves;
-        stats[0].stitch_copy_ms = std::chrono::duration<double, std::milli>(t3 - t2).count();
-        stats[0].comm_init_ms = comm_init_ms;
-    }
-    return (int)RT_OK;
-}
-
-extern "C" {
-
+// ---- the frame across the GPUs of one node (host/frame.cpp: render_fanout) ----
 int rt_render_multi(const rt_scene* s, const rt_camera* cam, const rt_params* p, int n_devices, const int* device_ids, double* out_rgb,
                     rt_stats* stats) {
     return guard([&] {
         REQUIRE(s && cam, "null argument");
-        if (!s->committed) throw RtError(RT_ERR_NOT_COMMITTED, "rt_scene_commit has not been called");
-        const CameraDev cd = make_camera(*cam);
-        return render_fanout(p, n_devices, device_ids, out_rgb, stats,
-                             [&](const RenderPlan& pl, double* d_rows, rt_stats* st) { render_tiles(*s, cd, pl, d_rows, nullptr, st); });
+        require_committed(*s);
+        render_fanout(*s, make_camera(*cam), nullptr, p, n_devices, device_ids, out_rgb, stats);
+        return (int)RT_OK;
     });
 }
 int rt_render_multi_camera_frame(const rt_scene* s, const rt_camera_frame* frame, const rt_params* p, int n_devices, const int* device_ids,
                                  double* out_rgb, rt_stats* stats) {
     return guard([&] {
         REQUIRE(s && frame, "null argument");
-        for (const double* v : {frame->origin, frame->lower_left_corner, frame->horizontal, frame->vertical, frame->u, frame->v, frame->w})
-            for (int i = 0; i < 3; i++) REQUIRE(std::isfinite(v[i]), "camera frame must be finite");
-        REQUIRE(std::isfinite(frame->lens_radius), "camera frame must be finite");
-        if (!s->committed) throw RtError(RT_ERR_NOT_COMMITTED, "rt_scene_commit has not been called");
-        const CameraDev cd = camera_from_frame(*frame);
-        return render_fanout(p, n_devices, device_ids, out_rgb, stats,
-                             [&](const RenderPlan& pl, double* d_rows, rt_stats* st) { render_tiles(*s, cd, pl, d_rows, nullptr, st); });
+        require_finite(*frame);
+        require_committed(*s);
+        render_fanout(*s, camera_from_frame(*frame), nullptr, p, n_devices, device_ids, out_rgb, stats);
+        return (int)RT_OK;
     });
 }
 int rt_render_sppm_multi(const rt_scene* s, const rt_camera* cam, const rt_params* p, const rt_sppm_config* cfg, int n_devices,
@@ -1275,13 +734,9 @@ int rt_render_sppm_multi(const rt_scene* s, const rt_camera* cam, const rt_param
     return guard([&] {
         REQUIRE(s && cam && cfg && p, "null argument");
         REQUIRE(p->spp > 0, "spp must be positive");
-        if (!s->committed) throw RtError(RT_ERR_NOT_COMMITTED, "rt_scene_commit has not been called");
-        const CameraDev cd = make_camera(*cam);
-        rt_params q = *p;
-        q.integrator = 0;  // as rt_render_sppm_tiles_device: the plan of the final pass; render_sppm switches the integrator
-        return render_fanout(&q, n_devices, device_ids, out_rgb, stats, [&](const RenderPlan& pl, double* d_rows, rt_stats* st) {
-            render_sppm(*s, cd, pl, *cfg, d_rows, nullptr, nullptr, st, nullptr);
-        });
+        require_committed(*s);
+        render_fanout(*s, make_camera(*cam), cfg, p, n_devices, device_ids, out_rgb, stats);
+        return (int)RT_OK;
     });
 }
 int rt_rccl_version(void) { return exchange_library_version(); }
@@ -1303,36 +758,7 @@ int rt_render_sppm(const rt_scene* s, const rt_camera* cam, const rt_params* p, 
         REQUIRE(p->spp == 0 || out_rgb, "null output buffer");
         REQUIRE(p->world == 1 && p->rank == 0, "rt_render_sppm renders the whole frame on one GPU (world must be 1); "
                                                "the tile-partitioned form is rt_render_sppm_tiles_device");
-        if (!s->committed) throw RtError(RT_ERR_NOT_COMMITTED, "rt_scene_commit has not been called");
-        if (device_count() < 1) throw RtError(RT_ERR_NO_DEVICE, "no HIP device: librtamd has no CPU fallback");
-        auto t0 = std::chrono::steady_clock::now();
-        DeviceScope dev_scope(p->device);
-        rt_params q = *p;
-        if (q.spp == 0) q.spp = 1;  // make_plan wants a positive spp; the pre-pass-only case never launches the render
-        q.integrator = 0;
-        RenderPlan pl = make_plan(&q);
-        pl.spp = p->spp;
-        CameraDev cd = make_camera(*cam);
-        struct Buf {
-            void* p = nullptr;
-            ~Buf() {
-                if (p) dev_free(p);
-            }
-        } tiles, frame;
-        size_t frame_bytes = (size_t)pl.width * pl.height * 3 * sizeof(double);
-        tiles.p = dev_alloc((size_t)std::max<int64_t>(1, pl.tiles_owned) * TILE_PIX * 3 * sizeof(double));
-        frame.p = dev_alloc(frame_bytes);
-        rt_stats st{};
-        render_sppm(*s, cd, pl, *cfg, (double*)tiles.p, stats_out, nullptr, &st, photons_stored);
-        if (p->spp > 0) {
-            assemble_frame(pl, (const double*)tiles.p, pl.tiles_owned, (double*)frame.p, nullptr);
-            dev_copy_to_host(out_rgb, frame.p, frame_bytes);
-        }
-        if (stats) {
-            *stats = st;
-            stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            stats->samples = (uint64_t)pl.width * pl.height * (uint64_t)p->spp;
-        }
+        render_sppm_frame(*s, *cam, *p, *cfg, out_rgb, stats_out, photons_stored, stats);
         return (int)RT_OK;
     });
 }
@@ -1344,16 +770,13 @@ int rt_render_aov(const rt_scene* s, const rt_camera* cam, const rt_params* p, i
         REQUIRE(aov_spp > 0, "aov_spp must be positive");
         REQUIRE(p->world == 1 && p->rank == 0, "rt_render_aov renders whole frames: rank / world must be 0 / 1");
         REQUIRE(p->kernel >= 0 && p->kernel <= 2, "rt_render_aov walks with kernel 0 (auto), 1 or 2");
-        if (!s->committed) throw RtError(RT_ERR_NOT_COMMITTED, "rt_scene_commit has not been called");
-        if (!render_aov || device_count() < 1) throw RtError(RT_ERR_NO_DEVICE, "no HIP device: librtamd has no CPU fallback");
-        auto t0 = std::chrono::steady_clock::now();
+        require_committed(*s);
+        require_device(render_aov != nullptr);
+        const CallClock clock;
         DeviceScope dev_scope(p->device);
         rt_stats st{};
         render_aov(*s, make_camera(*cam), p->width, p->height, p->seed, p->t_min, p->kernel, aov_spp, out_aov, &st);
-        if (stats) {
-            *stats = st;
-            stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        }
+        clock.finish(stats, st);
         return (int)RT_OK;
     });
 }
@@ -1387,7 +810,7 @@ int rt_denoise(const rt_denoise_config* cfg, int32_t width, int32_t height, cons
                double* out_rgb, double* out_variance) {
     return guard([&] {
         check_denoise_args(cfg, width, height, rgb, variance, aov, out_rgb, out_variance);
-        if (!denoise_host || device_count() < 1) throw RtError(RT_ERR_NO_DEVICE, "no HIP device: librtamd has no CPU fallback");
+        require_device(denoise_host != nullptr);
         denoise_host(*cfg, width, height, rgb, variance, aov, out_rgb, out_variance);
         return (int)RT_OK;
     });
@@ -1396,7 +819,7 @@ int rt_denoise_device(const rt_denoise_config* cfg, int32_t width, int32_t heigh
                       const double* d_aov, double* d_out_rgb, double* d_out_variance, void* hip_stream) {
     return guard([&] {
         check_denoise_args(cfg, width, height, d_rgb, d_variance, d_aov, d_out_rgb, d_out_variance);
-        if (!denoise_device || device_count() < 1) throw RtError(RT_ERR_NO_DEVICE, "no HIP device: librtamd has no CPU fallback");
+        require_device(denoise_device != nullptr);
         denoise_device(*cfg, width, height, d_rgb, d_variance, d_aov, d_out_rgb, d_out_variance, hip_stream);
         return (int)RT_OK;
     });
@@ -1474,15 +897,8 @@ static int env_debug(const rt_scene* s, int device, const std::function<void()>&
         const int n_dev = device_count();
         if (n_dev < 1 || !env_debug_linked()) throw RtError(RT_ERR_NO_DEVICE, "no HIP device");
         REQUIRE(device >= 0 && device < n_dev, "no such device");
-        const int cur = dev_get_device();
-        dev_set_device(device);
-        try {
-            f();
-        } catch (...) {
-            dev_set_device(cur);
-            throw;
-        }
-        dev_set_device(cur);
+        DeviceScope dev_scope(device);
+        f();
         return (int)RT_OK;
     });
 }

@@ -1,5 +1,5 @@
-// Host-callable interface of the tile-adaptive sampling kernels (device/adaptive.inc, compiled into kernels.hip); rt_render_adaptive in
-// abi.cpp drives them between render_tiles passes.  WEAK declarations, as in device/denoise.h: a build of the host half
+// Host-callable interface of the tile-adaptive sampling kernels (device/adaptive.inc, compiled into kernels.hip); render_adaptive in
+// host/frame.cpp drives them between render_tiles passes.  WEAK declarations, as in device/denoise.h: a build of the host half
 // alone (the sanitizer builds) still links, and the entry point reports RT_ERR_NO_DEVICE there.
 #pragma once
 #include <cstdint>

@@ -1,6 +1,6 @@
 // The one data-path exchange of the multi-GPU frame (camera.rs:113-123 is its CPU form: the row bands travel
 // through a channel and are stitched by the caller): every rank's tile-major rows go to the root device, over xGMI, through
-// RCCL.  One process drives all devices (rt_render_multi, abi.cpp): the communicators come from ncclCommInitAll and live in
+// RCCL.  One process drives all devices (rt_render_multi: render_fanout in host/frame.cpp): the communicators come from ncclCommInitAll and live in
 // a per-process cache keyed by the device list (creating them costs far more than the exchange); a row travels as one grouped
 // ncclSend / ncclRecv pair, posted the moment its rank has finished rendering (round 5; round 4 posted all rows in one group after
 // the ranks had joined) -- each peer's row crosses its own direct link to the root, 7 links in parallel on an 8-GPU node --

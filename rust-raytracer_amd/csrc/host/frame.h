@@ -1,0 +1,112 @@
+// The frame-level host driver: what a render call does around the kernels -- the plan of a launch, the tile arithmetic of a partition,
+// the device buffers of a frame and the stitch into the caller's memory, and the drivers themselves (one frame on one GPU, resumable
+// rendering with host-held state, the pass loop of tile-adaptive sampling, the fan-out over the GPUs of a node, the SPPM frame).
+// Plain C++17: the device is reached through device/device.h, device/adaptive.h and device/denoise.h only.  Everything throws RtError;
+// the extern "C" boundary (abi.cpp) checks its arguments, calls in here and turns exceptions into status codes.
+#pragma once
+#include <chrono>
+#include <cstdint>
+
+#include "device/device.h"
+#include "host/scene.h"
+#include "rtamd.h"
+
+#define REQUIRE(c, msg) \
+    if (!(c)) throw rtamd::RtError(RT_ERR_ARG, msg)
+
+namespace rtamd {
+
+// ---- the tiles of a frame and of a rank's partition (rank r of `world` owns the tiles t with t % world == r) ----
+int64_t tiles_total(int width, int height);
+int64_t tiles_owned(int64_t total, int rank, int world);
+size_t row_doubles(int64_t tiles_owned);        // f64 in a rank's tile-major rows (an accumulator state, a row of the gather): never 0
+size_t frame_bytes(int width, int height);      // the stitched f64 RGB frame
+uint64_t tile_pixels(const RenderPlan& pl, int64_t t);  // pixels of image tile t that lie inside the image
+uint64_t pixels_in_image(const RenderPlan& pl);         // the same over the tiles of pl's rank: rt_stats.samples = this x samples per pixel
+
+// owned >= 0: a plan for that many tiles in place of the rank's partition (render_adaptive's passes over a tile list)
+RenderPlan make_plan(const rt_params* p, int64_t owned = -1);
+// the plan of an SPPM call is that of its final pass under integrator 0 (render_sppm switches the integrator); spp == 0 -- the pre-pass
+// alone, which never launches the render -- is planned as 1 and put back
+RenderPlan make_sppm_plan(const rt_params& p);
+
+void require_committed(const rt_scene& s);
+void require_device(bool linked = true);  // linked: the weakly referenced device function of the call is there (device/adaptive.h, denoise.h)
+
+// the clock of a call and what every render call reports at its end: rt_stats.seconds = the wall time since the clock was made
+struct CallClock {
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    double seconds() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+    void stamp(rt_stats* stats, uint64_t samples) const {  // the render wrote *stats itself
+        if (!stats) return;
+        stats->seconds = seconds();
+        stats->samples = samples;
+    }
+    void finish(rt_stats* stats, const rt_stats& st) const {  // *stats is written on success only
+        if (!stats) return;
+        *stats = st;
+        stats->seconds = seconds();
+    }
+    void finish(rt_stats* stats, const rt_stats& st, uint64_t samples) const {
+        finish(stats, st);
+        if (stats) stats->samples = samples;
+    }
+};
+
+// rt_params.device >= 0 makes that device current for the call only: the caller's current device comes back
+struct DeviceScope {
+    int prev = -1;  // what the end of the scope makes current again; -1: nothing
+    explicit DeviceScope(int want) {
+        if (want < 0) return;
+        prev = dev_get_device();
+        if (prev != want) dev_set_device(want);
+        else prev = -1;
+    }
+    ~DeviceScope() {
+        if (prev < 0) return;
+        try {
+            dev_set_device(prev);
+        } catch (...) {
+        }
+    }
+    DeviceScope(const DeviceScope&) = delete;
+    DeviceScope& operator=(const DeviceScope&) = delete;
+};
+
+// device memory of the current device, allocated and freed per call (the idle-frame pool below is render_fanout's alone)
+struct DevBuf {
+    void* const p;
+    explicit DevBuf(size_t bytes) : p(dev_alloc(bytes)) {}
+    ~DevBuf() { dev_free(p); }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    double* f64() const { return (double*)p; }
+    int32_t* i32() const { return (int32_t*)p; }
+};
+
+size_t frame_pool_release();  // frees the idle frame-sized buffers render_fanout keeps between calls; returns the bytes (rt_release_workspaces)
+
+// rows on the device (rank-major, `stride` tiles per rank) -> the stitched frame in d_frame -> the caller's out_rgb (HOST)
+void stitch_to_host(const RenderPlan& pl, const double* d_rows, int64_t stride, double* d_frame, double* out_rgb);
+
+// ---- the drivers: each begins where its entry point's null / range checks end ----
+// rt_render, rt_render_camera_frame: one frame on one GPU; world > 1 scatters only this rank's tiles into a zeroed frame
+void render_frame(const rt_scene& s, const CameraDev& cd, const rt_params& p, double* out_rgb, rt_stats* stats);
+// resumable rendering: the samples [begin, end) into the caller's accumulator on the device; the same with the state held by the host;
+// a complete host-held state -> the frame
+void accumulate_device(const rt_scene& s, const rt_camera& cam, const rt_params& p, int32_t begin, int32_t end, double* d_accum, void* stream,
+                       rt_stats* stats);
+void accumulate_host(const rt_scene& s, const rt_camera& cam, const rt_params& p, int32_t begin, int32_t end, double* accum_state, rt_stats* stats);
+void finalize_host(const rt_params& p, const double* accum_state, double* out_rgb);
+// rt_render_adaptive: the passes over the active tiles and the stopping tests between them
+void render_adaptive(const rt_scene& s, const rt_camera& cam, const rt_params& p, const rt_adaptive_config& cfg, double* out_rgb,
+                     int32_t* out_tile_spp, rt_stats* stats);
+// rt_render_multi*, rt_render_sppm_multi (cfg: its configuration, null for the path tracer): one host thread per rank, the gather on
+// device_ids[0], the stitch
+void render_fanout(const rt_scene& s, const CameraDev& cd, const rt_sppm_config* cfg, const rt_params* p, int n_devices, const int* device_ids,
+                   double* out_rgb, rt_stats* stats);
+// rt_render_sppm: pre-pass and final render of a whole frame on one GPU
+void render_sppm_frame(const rt_scene& s, const rt_camera& cam, const rt_params& p, const rt_sppm_config& cfg, double* out_rgb, double* stats_out,
+                       uint64_t photons_stored[2], rt_stats* stats);
+
+}  // namespace rtamd

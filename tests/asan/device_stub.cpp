@@ -10,6 +10,10 @@
 //   exchange_post  copies one row (what a grouped ncclSend / ncclRecv pair does), counts it and refuses overlapping calls;
 //                  RTAMD_STUB_STAGGER_MS=k makes rank r's render take k * r milliseconds, so the ranks finish one after the other;
 //   assemble_frame is the stitch of camera.rs:115-123 restated on the host (tile t of rank r sits at row r, slot t / world).
+//   adaptive_*     the three steps between rt_render_adaptive's passes on host memory.  render_tiles honours plan.tile_list and adds
+//                  value(t, pix, c) x (samples in the pass) per pass, so the finished frame is the pattern whatever stops.  adaptive_test
+//                  looks at no value: image tile t stops at the first test whose n >= 4 << (t % 4) (so t % 4 == 3 never stops below
+//                  32 spp), which gives tile_spp and rt_stats.samples in closed form (tests/test_multi_stub.py).
 // Device memory is malloc'ed per allocation, so a slot computed wrongly is a heap overflow that ASan reports.
 #include <chrono>
 #include <cstdlib>
@@ -18,6 +22,7 @@
 #include <mutex>
 #include <thread>
 
+#include "device/adaptive.h"
 #include "device/device.h"
 namespace rtamd {
 static int stub_devices() {
@@ -55,7 +60,7 @@ void render_tiles(const rt_scene&, const CameraDev&, const RenderPlan& pl, doubl
     if (pl.ext_accum) {  // resumable rendering: every sample index of the range adds the pattern once (s_first == 0 initialises)
         const int n = (pl.s_last < 0 ? pl.spp : pl.s_last) - pl.s_first;
         for (int64_t lt = 0; lt < pl.tiles_owned; lt++) {
-            const int64_t t = lt * pl.world + pl.rank;
+            const int64_t t = pl.tile_list ? pl.tile_list[lt] : lt * pl.world + pl.rank;
             for (int pix = 0; pix < TILE_PIX; pix++)
                 for (int c = 0; c < 3; c++) {
                     double& a = pl.ext_accum[((size_t)lt * TILE_PIX + pix) * 3 + c];
@@ -91,6 +96,27 @@ void assemble_frame(const RenderPlan& pl, const double* gathered, int64_t stride
 void finalize_tiles(const RenderPlan& pl, const double* acc, double* tiles, void*) {
     if (stub_devices() < 1) none();
     for (int64_t i = 0; i < pl.tiles_owned * TILE_PIX * 3; i++) tiles[i] = acc[i] / pl.spp;
+}
+void adaptive_copy_tiles(double* dst, const int32_t* dst_list, const double* src, const int32_t* src_list, int64_t n, void*) {
+    if (stub_devices() < 1) none();
+    for (int64_t i = 0; i < n; i++)
+        std::memcpy(dst + (size_t)(dst_list ? dst_list[i] : i) * TILE_PIX * 3, src + (size_t)(src_list ? src_list[i] : i) * TILE_PIX * 3,
+                    TILE_PIX * 3 * sizeof(double));
+}
+void adaptive_test(const RenderPlan&, const double* accum, double* half, const int32_t* list, int64_t n_active, int n, int, double, int32_t* stop,
+                   double* err, void*) {
+    if (stub_devices() < 1) none();
+    for (int64_t i = 0; i < n_active; i++) {
+        const int32_t t = list[i];
+        stop[i] = n >= (4 << (t % 4)) ? 1 : 0;
+        err[i] = 0.;
+        if (!stop[i]) std::memcpy(half + (size_t)t * TILE_PIX * 3, accum + (size_t)t * TILE_PIX * 3, TILE_PIX * 3 * sizeof(double));
+    }
+}
+void adaptive_finalize(const RenderPlan& pl, const double* accum, const int32_t* tile_spp, double* tiles, void*) {
+    if (stub_devices() < 1) none();
+    for (int64_t t = 0; t < pl.tiles_total; t++)
+        for (int i = 0; i < TILE_PIX * 3; i++) tiles[(size_t)t * TILE_PIX * 3 + i] = accum[(size_t)t * TILE_PIX * 3 + i] / tile_spp[t];
 }
 void debug_rng_device(uint64_t, uint64_t, uint64_t, int, uint64_t*) { none(); }
 void debug_rng_floats_device(uint64_t, uint64_t, uint64_t, int, double, double, double*, double*) { none(); }

@@ -108,6 +108,25 @@ def test_resumable_render_with_host_held_state_on_the_stub():
         rtamd.accum_finalize(rtamd.default_params(width=52, height=28, spp=16, rank=1, world=2), state)
 
 
+def test_adaptive_pass_loop_on_the_stub():
+    """rt_render_adaptive's pass loop -- the active list, the compact accumulator of a pass, the scatter back, the half snapshot, the stops
+    -- on the stub, whose adaptive_test looks at no value: image tile t stops at the first test whose n >= 4 << (t % 4).  With min_spp 6
+    and spp 23 (not 6 times a power of two) the passes are [0, 3), [3, 6), [6, 12), [12, 23) with tests at n = 6 and n = 12, so
+    tile_spp = 6, 12, 23, 23 for t % 4 = 0, 1, 2, 3.  The stub's render adds value x (samples in the pass), so the finished frame is the
+    pattern whatever stops; 52 x 28 has partial tiles on both edges (a wrong slot is a heap overflow under ASan)."""
+    world, cam = _world()
+    w, h, spp, min_spp = 52, 28, 23, 6
+    img, tile_spp, st = world.render_adaptive(cam, w, h, spp, min_spp=min_spp, threshold=0.5, seed=6)
+    assert np.array_equal(img, _expected(w, h, 6))
+    tx, ty = (w + 7) // 8, (h + 7) // 8
+    t = np.arange(tx * ty).reshape(ty, tx)
+    tests = [n for n in (min_spp << k for k in range(31)) if n < spp]
+    want = np.array([next((n for n in tests if n >= 4 << (i % 4)), spp) for i in range(tx * ty)], dtype=np.int32).reshape(ty, tx)
+    assert np.array_equal(tile_spp, want) and set(want.ravel()) == {6, 12, 23}
+    px = np.minimum(8, w - (t % tx) * 8) * np.minimum(8, h - (t // tx) * 8)
+    assert st["samples"] == int((px * want).sum())
+    assert st["launches"] == 4 and st["kernel_ms"] == 4.0           # summed over the four passes (the stub reports 1 and 1.0 per pass)
+
 
 def test_rows_travel_as_their_ranks_finish_not_after_the_join(monkeypatch):
     """RTAMD_STUB_STAGGER_MS makes rank r's (stub) render take 30 r ms: a rank's rows are handed to the exchange by its own thread the moment

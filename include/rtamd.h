@@ -219,8 +219,8 @@ int rt_object_mesh_obj(rt_scene* s, const char* obj_path, int material, int synt
 /* objects/transform.rs:17 Transform::new(rotate_in_degree, scale, translate, obj): M = T*S*Rx*Ry*Rz
  * Transforms may nest (a Transform whose object is, or contains, another Transform) up to 8 levels; rt_scene_commit refuses a deeper
  * chain with RT_ERR_UNSUPPORTED.  A scene that nests renders through kernels 1 and 2 (the automatic choice is kernel 2) with every
- * integrator; kernels 5 / 6 refuse it with RT_ERR_UNSUPPORTED (rt_scene_info.accel_compact = 0).  A light under a Transform is refused
- * at commit; a ConstantMedium under a Transform, at any depth, renders through kernel 1 only, as at depth 1. */
+ * integrator; kernels 5 / 6 refuse it with RT_ERR_UNSUPPORTED (rt_scene_info.accel_compact = 0).  A light of rt_scene_set_lights under a Transform is refused
+ * at commit (an area light, rt_scene_set_area_lights, may lie under Transforms); a ConstantMedium under a Transform, at any depth, renders through kernel 1 only, as at depth 1. */
 int rt_object_transform(rt_scene* s, const double rotate_deg[3], const double scale[3], const double translate[3], int object);
 /* Transform as the reference stores it (transform.rs:9-14: obj, trans, inverse_trans; row-major 4x4).  inverse_trans may be
  * NULL (computed as try_inverse does; RT_ERR_SINGULAR if there is none). */
@@ -266,7 +266,8 @@ int rt_object_children(const rt_scene* s, int object, int capacity, int* out);  
 int rt_world_new(rt_scene* s, int n, const int* objects, uint64_t bvh_seed);
 /* World::new's `lights: Vec<Arc<dyn Light>>` (world.rs:18; scene.rs:110 passes the XZRectLight): the objects that the
  * mixture-pdf integrator samples.  Each must be a sphere or an XZ rectangle in world space (the reference's two Light
- * impls, light.rs:67-86,127-146); RT_ERR_UNSUPPORTED for lights under a Transform.  A background (rt_scene_set_background) is a
+ * impls, light.rs:67-86,127-146); RT_ERR_UNSUPPORTED for lights under a Transform.  Every other emissive shape -- an XY or YZ
+ * rectangle, a cube, triangles and meshes, any of them under Transforms -- goes to rt_scene_set_area_lights below.  A background (rt_scene_set_background) is a
  * light of integrator 1 only where the scene switched env sampling on (rt_scene_set_env_sampling below): then it is one more strategy
  * of the light half of the mixture, and a scene lit by nothing else needs no object lights.  Without that switch integrator 1 reaches
  * the background by the BSDF and light-sampled directions of the mixture only.  rt_render_sppm* refuses a scene with a background
@@ -336,6 +337,46 @@ typedef struct rt_env_sampling {
 } rt_env_sampling;
 int rt_scene_set_env_sampling(rt_scene* s, const rt_env_sampling* cfg);
 int rt_scene_get_env_sampling(const rt_scene* s, rt_env_sampling* out);  /* what was set (0, 0 stays 0, 0) */
+/* ---- area lights: emissive rectangles, cubes and meshes as lights of integrator 1 (no reference counterpart) ----
+ * A second light list beside rt_scene_set_lights (which keeps its meaning, its refusals and its bits).  An area light is any object whose
+ * leaves are rectangles (any axis), cubes or triangles: whole meshes, lists and BVH nodes of such leaves, and any of these under up to 8
+ * nested Transforms.  Set before rt_scene_commit; n == 0 clears the list, and a scene with an empty list keeps its blob, its fingerprint,
+ * its kernels and every image.  RT_ERR_ARG: an unknown id, a call after commit, a subtree that holds a sphere, a moving sphere or a medium,
+ * a leaf whose material is not a DiffuseLight, a Transform chain deeper than 8.
+ *   lowering  rt_scene_commit lowers the list to ONE table of world-space triangles, in f64 without contraction, objects in list order:
+ *             a rectangle with corners P00, P10, P01, P11 (the first in-plane axis varies first: x for XY and XZ, y for YZ) gives
+ *             (P00, P10, P11) and (P00, P11, P01); a cube its six sides in rt_object_children order, each as a rectangle;
+ *             rt_object_triangle its three positions; a mesh its triangles in the order of `indices` (not of its inner BVH); a list / BVH
+ *             node its children in order; a Transform maps its child's vertices by its stored `trans` (vec3.rs:174-178, w = 1), innermost
+ *             first.  Per triangle (a, b, c): e0 = b - a, e1 = c - a, n = cross(e0, e1), area2 = sqrt(sqlen(n)); a triangle whose area2 is
+ *             0 or not finite is dropped.  Per light L: q_k = max(1, floor(area2_k / area2_max_L * 4294967295.0)) as uint32, area2_max_L
+ *             the light's largest area2; the inclusive prefix sums of q within the light and total_L are uint64.
+ *             At commit: more than 1024 triangles over all area lights is RT_ERR_UNSUPPORTED (the pdf below is a linear scan), an area
+ *             light with no triangle of non-zero area RT_ERR_ARG.  The table is part of the blob, so rt_scene_fingerprint tells a scene
+ *             with area lights from the same scene without them.
+ *   draw      from light L at point o, three gen_f64 draws xi1..xi3: triangle k = the first whose inclusive prefix sum exceeds
+ *             min(total_L - 1, (uint64)(xi1 * (double)total_L)); u = xi2, v = xi3, and if u + v > 1.0 then u = 1.0 - u, v = 1.0 - v;
+ *             p = a + (e0 * u + e1 * v), dir = p - o.
+ *   pdf       of (o, d) for light L: the sum, from 0.0 in table order, over the light's triangles that Triangle::hit (mesh.rs:57-102, on
+ *             (a, e0, e1), t in [0.001, +inf]) accepts, of (((double)q_k / (double)total_L) * dist2) / (cosine * (0.5 * area2_k)) with
+ *             dist2 = (t * t) * sqlen(d) and cosine = fabs(dot(d, n_k) / (sqrt(sqlen(d)) * area2_k)); a term whose cosine is not > 0 is
+ *             skipped.  Emission is two-sided (material.rs:209-211 has no face test), hence the fabs.
+ *   mixture   with L object lights, M area lights and E in {0, 1} environment strategies (env sampling above) n = L + M + E; the light half
+ *             picks (uint32)(gen_f64() * n), clamped to n - 1: [0, L) the object lights, [L, L + M) the area lights, L + M the environment;
+ *             pdf = 0.5 * ((the sum of the n pdfs, in that order) / n) + 0.5 * cosine / PI.  Weight, termination and what a miss adds are
+ *             unchanged.  A scene with area lights and no object lights renders under integrator 1.
+ * Only integrator 1 on kernels 1 / 2 changes (the automatic choice is kernel 2, or 1 without an accel): integrator 0 ignores the list, bit
+ * for bit; kernels 5 / 6 under integrator 1 and rt_render_sppm* (the photon pass has no emitter for them) are RT_ERR_UNSUPPORTED for a
+ * scene with area lights; media and the book-2 kinds stay refused under integrator 1. */
+int rt_scene_set_area_lights(rt_scene* s, int n, const int* objects);
+typedef struct rt_area_tri {
+    double a[3], e0[3], e1[3], n[3];
+    double area2;
+    uint32_t q;
+    int32_t light;     /* index into the list of rt_scene_set_area_lights */
+} rt_area_tri;
+/* the lowered table of a committed scene (host only, no device): writes min(capacity, N) records, returns N */
+int rt_scene_area_light_tris(const rt_scene* s, int capacity, rt_area_tri* out);
 /* scene.rs:16-112 cornell_box_scene(): the reference's only built-in scene, numbers verbatim.
  * cube_obj_path = "data/mesh/cube.obj" of the reference. */
 int rt_scene_cornell_box(rt_scene* s, const char* cube_obj_path, double aspect_ratio, uint64_t bvh_seed, rt_camera* cam_out);
@@ -561,6 +602,12 @@ int rt_debug_schedule(int64_t tiles_owned, int n_waves, int s_begin, int s_end, 
 int rt_debug_env_table_device(const rt_scene* s, int device, int* w, int* h, uint32_t* q_host);
 int rt_debug_env_sample_device(const rt_scene* s, int device, size_t n, const double* xi4_host, double* out_host);
 int rt_debug_env_pdf_device(const rt_scene* s, int device, size_t n, const double* dirs_host, double* pdf_host);
+/* area light diagnostics on HIP device `device` (a committed scene with area lights; RT_ERR_NO_DEVICE without a GPU).
+ * sample: in_host n*7 = {o[3], xi0, xi1, xi2, xi3}: xi0 picks one of the M area lights by the mixture's clamped product (uint32)(xi0 * M),
+ * xi1..xi3 are the three draws -> out_host n*4 = {dir[3], pdf}.  pdf: rays_host n*6 = {o[3], d[3]} -> n pdfs.  Both pdfs are the sum of the
+ * pdfs of all M area lights, in list order from 0.0 (not divided by M). */
+int rt_debug_area_sample_device(const rt_scene* s, int device, size_t n, const double* in_host, double* out_host);
+int rt_debug_area_pdf_device(const rt_scene* s, int device, size_t n, const double* rays_host, double* pdf_host);
 
 #ifdef __cplusplus
 }

@@ -66,6 +66,9 @@ namespace rtamd {
 void debug_env_table_device(const rt_scene& s, int* w, int* h, uint32_t* q_host) __attribute__((weak));
 void debug_env_eval_device(const rt_scene& s, int mode, size_t n, const double* in, double* out) __attribute__((weak));
 }  // namespace rtamd
+namespace rtamd {
+void debug_area_eval_device(const rt_scene& s, int mode, size_t n, const double* in, double* out) __attribute__((weak));  // (likewise)
+}  // namespace rtamd
 static bool env_debug_linked() { return &rtamd::debug_env_table_device != nullptr && &rtamd::debug_env_eval_device != nullptr; }
 
 extern "C" {
@@ -415,6 +418,24 @@ int rt_scene_set_lights(rt_scene* s, int n, const int* objects) {
         }
         s->lights = v;
         return (int)RT_OK;
+    });
+}
+int rt_scene_set_area_lights(rt_scene* s, int n, const int* objects) {
+    return guard([&] {
+        not_committed_only(s);
+        REQUIRE(n >= 0 && (n == 0 || objects), "bad area light list");
+        for (int i = 0; i < n; i++) check_area_light(*s, objects[i]);
+        s->area_lights.assign(objects, objects + n);
+        return (int)RT_OK;
+    });
+}
+int rt_scene_area_light_tris(const rt_scene* s, int capacity, rt_area_tri* out) {
+    return guard([&] {
+        REQUIRE(s && (out || capacity <= 0), "null argument");
+        require_committed(*s);
+        const std::vector<rt_area_tri>& t = s->flat.area_tris;
+        for (int i = 0; i < capacity && i < (int)t.size(); i++) out[i] = t[i];
+        return (int)t.size();
     });
 }
 int rt_scene_set_background(rt_scene* s, const rt_background* bg) {
@@ -915,6 +936,20 @@ int rt_debug_env_pdf_device(const rt_scene* s, int device, size_t n, const doubl
     return env_debug(s, device, [&] {
         REQUIRE(n > 0 && dirs_host && pdf_host, "bad argument");
         debug_env_eval_device(*s, 1, n, dirs_host, pdf_host);
+    });
+}
+int rt_debug_area_sample_device(const rt_scene* s, int device, size_t n, const double* in_host, double* out_host) {
+    return env_debug(s, device, [&] {
+        REQUIRE(n > 0 && in_host && out_host, "bad argument");
+        if (&rtamd::debug_area_eval_device == nullptr) throw RtError(RT_ERR_NO_DEVICE, "no HIP device");
+        debug_area_eval_device(*s, 0, n, in_host, out_host);
+    });
+}
+int rt_debug_area_pdf_device(const rt_scene* s, int device, size_t n, const double* rays_host, double* pdf_host) {
+    return env_debug(s, device, [&] {
+        REQUIRE(n > 0 && rays_host && pdf_host, "bad argument");
+        if (&rtamd::debug_area_eval_device == nullptr) throw RtError(RT_ERR_NO_DEVICE, "no HIP device");
+        debug_area_eval_device(*s, 1, n, rays_host, pdf_host);
     });
 }
 int rt_debug_schedule(int64_t tiles_owned, int n_waves, int s_begin, int s_end, int sub_spp, int job_units, int* out25) {

@@ -105,6 +105,27 @@ struct EnvTabHdr {
 };
 static_assert(sizeof(EnvTabHdr) == 32, "EnvTabHdr: 32 bytes");
 static const int ENV_MAX_DIM = 8192;
+// Area lights (rt_scene_set_area_lights): the emissive rectangles, cubes and triangles that integrator 1 samples beside the
+// object lights, lowered at commit to world-space triangles.  One table in the cold part of the blob, only for a scene that has such
+// lights: AreaHdr, AreaLightDev[n_lights], AreaTriDev[n_tris] (the triangles of light L are [first, first + count), in lowering order).
+struct AreaHdr {
+    uint32_t n_lights, n_tris;
+    uint32_t pad[2];
+};
+struct AreaLightDev {
+    uint32_t first, count;
+    uint64_t total;        // the sum of its triangles' q
+};
+struct AreaTriDev {
+    double a[3], e0[3], e1[3], n[3];  // a vertex, the edges b - a and c - a, n = cross(e0, e1)
+    double area2;          // |n| = twice the area
+    uint64_t cum;          // inclusive prefix sum of q within its light
+    uint32_t q;            // quantised selection weight: max(1, floor(area2 / area2_max * 4294967295.0))
+    uint32_t light;
+    uint64_t pad;
+};
+static_assert(sizeof(AreaHdr) == 16 && sizeof(AreaLightDev) == 16 && sizeof(AreaTriDev) == 128, "area light table: 16 / 16 / 128 bytes");
+static const int AREA_MAX_TRIS = 1024;  // over all area lights of a scene (the pdf is a linear scan)
 struct TexDev {   // material.rs:48-84
     int32_t type;  // 0 Constant, 1 Checker, 2 Image, 3 Noise (D9: Perlin marble, book 2)
     int32_t t0, t1;        // Checker: constant-texture ids (.0 when sines < 0, .1 otherwise)
@@ -195,6 +216,9 @@ struct FlatView {  // by-value kernel argument
     uint32_t off_bg;
     // cold part: one EnvDev when the scene enabled env sampling (rt_scene_set_env_sampling); 0 = none (the blob is unchanged)
     uint32_t off_env;
+    // cold part: the area light table (AreaHdr ...) when the scene has area lights (rt_scene_set_area_lights); 0 = none
+    // (the blob is unchanged)
+    uint32_t off_area;
 };
 
 // ---------------------------------------------------------------------------

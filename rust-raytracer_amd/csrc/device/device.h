@@ -49,6 +49,9 @@ void debug_hit_device(const rt_scene& s, int kernel, size_t n, const double* ray
 // mode 1: n pdfs (in n*3 directions -> out n)
 void debug_env_table_device(const rt_scene& s, int* w, int* h, uint32_t* q_host);
 void debug_env_eval_device(const rt_scene& s, int mode, size_t n, const double* in, double* out);
+// area light diagnostics on the current device: mode 0: n draws (in n*7 {o, xi0..xi3} -> out n*4 {dir, pdf}),
+// mode 1: n pdfs (in n*6 {o, d} -> out n)
+void debug_area_eval_device(const rt_scene& s, int mode, size_t n, const double* in, double* out);
 int device_count();
 // thin HIP wrappers so abi.cpp stays free of HIP headers
 void* dev_alloc(size_t n);

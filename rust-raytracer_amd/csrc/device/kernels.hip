@@ -1722,6 +1722,93 @@ DEV bool mixture_step_env(const Acc& A, const char* env, const Rec& rec, Rng& rn
     return true;
 }
 
+// Area lights (no reference counterpart): emissive rectangles, cubes and meshes, lowered by the host to one table of
+// world-space triangles in the cold part of the blob (flat.h: AreaHdr, AreaLightDev[], AreaTriDev[]); every operation below is in the order
+// rtamd.h pins.  Only the INTEG_AREA variants and the diagnostics call these; the table stays in global memory.
+struct AreaTab {
+    const AreaLightDev* lights;
+    const AreaTriDev* tris;
+    uint32_t n_lights;
+};
+DEV AreaTab area_tab(const char* tab) {
+    AreaTab a;
+    a.n_lights = ((const AreaHdr*)tab)->n_lights;
+    a.lights = (const AreaLightDev*)(tab + sizeof(AreaHdr));
+    a.tris = (const AreaTriDev*)(tab + sizeof(AreaHdr) + (size_t)a.n_lights * sizeof(AreaLightDev));
+    return a;
+}
+// a direction from o towards a point of light `li`, drawn uniformly over its area: a triangle by its share of the area, then a point of it
+__device__ __attribute__((noinline)) D3 area_sample(const char* tab, uint32_t li, D3 o, double x1, double x2, double x3) {
+    const AreaTab a = area_tab(tab);
+    const AreaLightDev l = a.lights[li];
+    uint64_t t = (uint64_t)(x1 * (double)l.total);
+    if (t > l.total - 1ull) t = l.total - 1ull;
+    const AreaTriDev* T = a.tris + l.first;
+    uint32_t lo = 0u, hi = l.count - 1u;  // the first triangle whose inclusive prefix sum exceeds t (t < T[count - 1].cum)
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (T[mid].cum > t) hi = mid;
+        else lo = mid + 1u;
+    }
+    const AreaTriDev* k = T + lo;
+    double u = x2, v = x3;
+    if (u + v > 1.0) {
+        u = 1.0 - u;
+        v = 1.0 - v;
+    }
+    const D3 p = add(mk(k->a[0], k->a[1], k->a[2]), add(muls(mk(k->e0[0], k->e0[1], k->e0[2]), u), muls(mk(k->e1[0], k->e1[1], k->e1[2]), v)));
+    return sub(p, o);
+}
+// the solid-angle density at o of area_sample's directions for light `li`: every triangle the ray (o, d) crosses adds its term (a linear scan)
+__device__ __attribute__((noinline)) double area_pdf(const char* tab, uint32_t li, D3 o, D3 d) {
+    const AreaTab a = area_tab(tab);
+    const AreaLightDev l = a.lights[li];
+    const double total = (double)l.total, d2 = sqlen(d), dl = sqrt(d2);
+    double sum = 0.0;
+    for (uint32_t i = 0; i < l.count; i++) {
+        const AreaTriDev* k = a.tris + l.first + i;
+        double t, b1, b2;
+        if (!tri_hit_v(mk(k->a[0], k->a[1], k->a[2]), mk(k->e0[0], k->e0[1], k->e0[2]), mk(k->e1[0], k->e1[1], k->e1[2]), o, d, 0.001, INFINITY, t, b1, b2)) continue;
+        const double area2 = k->area2;
+        const double dist2 = (t * t) * d2;
+        const double cosine = fabs(dot(d, mk(k->n[0], k->n[1], k->n[2])) / (dl * area2));
+        if (!(cosine > 0.)) continue;
+        sum = sum + (((double)k->q / total) * dist2) / (cosine * (0.5 * area2));
+    }
+    return sum;
+}
+// mixture_step with the area lights as strategies [n_lights, n_lights + M) of the light half and the environment, where the scene samples
+// it (env != nullptr), as the last one (INTEG_AREA; rtamd.h "area lights"): n_lights may be 0
+DEV bool mixture_step_area(const Acc& A, const char* area, const char* env, const Rec& rec, Rng& rng, D3 att, D3& beta, D3& dir, int* err) {
+    const double PI = 3.14159265358979323846264338327950288;
+    const uint32_t M = ((const AreaHdr*)area)->n_lights;
+    const uint32_t n = A.n_lights + M + (env ? 1u : 0u);
+    if (rng.gen_f64() < 0.5) {
+        uint32_t li = (uint32_t)(rng.gen_f64() * (double)n);
+        if (li >= n) li = n - 1u;
+        if (li < A.n_lights) {
+            dir = light_random(A, A.lights[li], rec.p, rng, err);
+        } else if (li < A.n_lights + M) {
+            const double x1 = rng.gen_f64(), x2 = rng.gen_f64(), x3 = rng.gen_f64();
+            dir = area_sample(area, li - A.n_lights, rec.p, x1, x2, x3);
+        } else {
+            const double x1 = rng.gen_f64(), x2 = rng.gen_f64(), x3 = rng.gen_f64(), x4 = rng.gen_f64();
+            dir = env_sample(env, x1, x2, x3, x4);
+        }
+    }
+    double cosine = dot(rec.normal, unit(dir, err));
+    double scattering_pdf = (cosine < 0.) ? 0. : cosine / PI;
+    double lp = 0.;
+    for (uint32_t i = 0; i < A.n_lights; i++) lp = lp + light_pdf_value(A, A.lights[i], rec.p, dir);
+    for (uint32_t i = 0; i < M; i++) lp = lp + area_pdf(area, i, rec.p, dir);
+    if (env) lp = lp + env_pdf(env, dir, err);
+    double pdf_val = 0.5 * (lp / (double)n) + 0.5 * scattering_pdf;
+    double wgt = scattering_pdf / pdf_val;
+    if (!(wgt > 0.)) return false;
+    beta = muls(elemul(beta, att), wgt);
+    return true;
+}
+
 // ------------------------------------------------------------ pt_kernel ---
 // INTEG: 0 = sample_ray with BSDF sampling; 1 = light/cosine mixture pdf; 2 = the reference's literal SPPM sample_ray:
 // the first Diffuse hit adds the pixel's pre-computed photon estimates and ends the path (photon_mapper.rs:345-352)
@@ -2163,6 +2250,9 @@ __device__ __attribute__((noinline)) UnitInfo next_unit(uint32_t* wst_, uint32_t
 static constexpr int INTEG_BG = 4;
 // INTEG & INTEG_ENV (on top of 1 | INTEG_BG): integrator 1 with the background as a light (env sampling)
 static constexpr int INTEG_ENV = 8;
+// INTEG & INTEG_AREA (on top of 1 | INTEG_BG): integrator 1 of a scene with area lights.  One family for every background
+// kind (0 included: a miss then adds nothing, by a branch) and for env sampling on or off (a run-time test of the table's presence)
+static constexpr int INTEG_AREA = 16;
 template <bool LDS, int GENERAL, int ACCEL, int INTEG, bool MEDIA = false, bool POOL = false>
 __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, RenderK rk, double* __restrict__ ring, double* accum,
                                                       unsigned int* tickets, unsigned int* __restrict__ counter, int* __restrict__ err) {
@@ -2225,6 +2315,9 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
             staged = (uint32_t)rk.n_top * (uint32_t)sizeof(Node2);
         }
     }
+    // INTEG_AREA: the env table behind the blob, where the scene samples its background and the table is not all zero; else null
+    const char* area_env = nullptr;
+    if ((INTEG & INTEG_AREA) && sv.off_env != 0u && ((const EnvTabHdr*)(sv.base + sv.total_bytes))->total != 0ull) area_env = sv.base + sv.total_bytes;
     uint32_t* stk = (uint32_t*)(smem + staged) + threadIdx.x;
     const int stk_stride = (int)blockDim.x;
     const int lane = threadIdx.x & 63;
@@ -2400,7 +2493,8 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
                             go = false;
                         } else if ((INTEG & 3) == 1 && diffuse) {
                             PH_EV(14);
-                            if (INTEG & INTEG_ENV) go = mixture_step_env(A, sv.base + sv.total_bytes, rec, rng, att, beta, ndir, err);
+                            if (INTEG & INTEG_AREA) go = mixture_step_area(A, sv.base + sv.off_area, area_env, rec, rng, att, beta, ndir, err);
+                            else if (INTEG & INTEG_ENV) go = mixture_step_env(A, sv.base + sv.total_bytes, rec, rng, att, beta, ndir, err);
                             else go = mixture_step(A, rec, rng, att, beta, ndir, err);
                         } else {
                             beta = elemul(beta, att);
@@ -2411,7 +2505,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
                             done = false;
                         }
                     }
-                } else if ((INTEG & INTEG_BG) && h.node < 0) {  // a miss sees the background: L += beta (x) B(d), then the path ends
+                } else if ((INTEG & INTEG_BG) && h.node < 0 && (!(INTEG & INTEG_AREA) || sv.off_bg != 0u)) {  // a miss sees the background: L += beta (x) B(d), then the path ends
                     L = add(L, elemul(beta, background_radiance<GENERAL>((const BgDev*)(sv.base + sv.off_bg), A.texs, A.texels, d, err)));
                 }
                 if (done) {
@@ -3823,6 +3917,31 @@ __global__ void env_eval_kernel(FlatView sv, int mode, size_t n, const double* _
         out[k] = live ? env_pdf(tab, mk(in[3 * k], in[3 * k + 1], in[3 * k + 2]), err) : 0.;
     }
 }
+// rt_debug_area_sample_device (mode 0: in = n x {o, xi0..xi3}, out = n x {dir, pdf}) and rt_debug_area_pdf_device (mode 1: in = n x {o, d});
+// pdf = the sum over all area lights, in list order
+__global__ void area_eval_kernel(FlatView sv, int mode, size_t n, const double* __restrict__ in, double* __restrict__ out) {
+    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const char* tab = sv.base + sv.off_area;
+    const uint32_t M = ((const AreaHdr*)tab)->n_lights;
+    const size_t stride = mode == 0 ? 7 : 6;
+    const D3 o = mk(in[stride * k], in[stride * k + 1], in[stride * k + 2]);
+    D3 d;
+    if (mode == 0) {
+        uint32_t li = (uint32_t)(in[7 * k + 3] * (double)M);
+        if (li >= M) li = M - 1u;
+        d = area_sample(tab, li, o, in[7 * k + 4], in[7 * k + 5], in[7 * k + 6]);
+    } else {
+        d = mk(in[6 * k + 3], in[6 * k + 4], in[6 * k + 5]);
+    }
+    double p = 0.;
+    for (uint32_t i = 0; i < M; i++) p = p + area_pdf(tab, i, o, d);
+    if (mode == 0) {
+        out[4 * k] = d.x; out[4 * k + 1] = d.y; out[4 * k + 2] = d.z; out[4 * k + 3] = p;
+    } else {
+        out[k] = p;
+    }
+}
 
 // ------------------------------------------------------------ host side ---
 int device_count() {
@@ -4089,6 +4208,12 @@ static pt_fn pick_pt_kernel_env(bool nest) {
     constexpr int E = INTEG_ENV | INTEG_BG | 1;
     return nest ? pt_kernel<LDS, 3, ACCEL, E> : pt_kernel<LDS, 1, ACCEL, E>;
 }
+// the area light variants (INTEG_AREA on top of 1 | INTEG_BG): integrator 1 of a scene with area lights, whatever its background
+template <int ACCEL, bool LDS>
+static pt_fn pick_pt_kernel_area(bool nest) {
+    constexpr int E = INTEG_AREA | INTEG_BG | 1;
+    return nest ? pt_kernel<LDS, 3, ACCEL, E> : pt_kernel<LDS, 1, ACCEL, E>;
+}
 
 static void render_tiles_wf(const rt_scene& s, const FlatView& view, const CameraDev& cam, const RenderPlan& plan, const Tuning& tun, double* d_tiles,
                             hipStream_t stream, rt_stats* st, int dev, const DevInfo& di, uint32_t stack6, uint32_t n_entry6, size_t lds_pt, uint32_t stack6w,
@@ -4175,12 +4300,18 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
     if (bg && (kernel == 5 || kernel == 6))
         throw RtError(RT_ERR_UNSUPPORTED, "kernels 5 / 6 have no background variant: a scene with a background renders with kernel 1 or 2 (kernel 0 picks one)");
     if (bg && plan.integrator == 2) throw RtError(RT_ERR_UNSUPPORTED, "the SPPM integrator has no background (the photon pass has no environment emitter)");
+    // area lights (rt_scene_set_area_lights): strategies of integrator 1 on kernels 1 and 2; integrator 0 ignores them
+    const bool area = view.off_area != 0u && plan.integrator == 1;
+    if (area && (kernel == 5 || kernel == 6))
+        throw RtError(RT_ERR_UNSUPPORTED, "kernels 5 / 6 have no area light variant: integrator 1 renders a scene with area lights with kernel 1 or 2 (kernel 0 picks one)");
+    if (view.off_area != 0u && plan.integrator == 2)
+        throw RtError(RT_ERR_UNSUPPORTED, "the SPPM integrator does not render a scene with area lights (the photon pass has no emitter for them)");
     // auto: the cooperative kernel as soon as an instance is more than a handful of triangles (Cornell box + torus instance, 64 spp,
     // kernel 5 / kernel 2 in Msamples/s: 120 triangles 1351 / 1182 (kernel 2 LDS-resident), 1 600: 1263 / 822, 25 600: 1035 / 517,
     // 102 400: 861 / 427, 409 600: 746 / 370; the 12-triangle cube of the reference's Cornell box: 2507 / 2533)
     // (kernel 6, the wavefront form of the same service, reaches 766 Msamples/s on C4 where kernel 5 reaches 891 and kernel 2 469: it is
     // since round 4 kernel 5 takes up to 64 instances too, so kernel 6 runs by request only)
-    if (kernel == 0 && bg)
+    if (kernel == 0 && (bg || area))
         kernel = accel2_usable ? 2 : 1;
     if (kernel == 0)
         kernel = accel2_usable ? ((coop_usable && view.max_inst_nodes2 >= 64u) ? 5 : (wf_usable && !coop_usable && view.max_inst_nodes2 >= 64u) ? 6 : 2) : 1;
@@ -4205,7 +4336,7 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
     const size_t hot_bytes = (kernel == 2 || kernel == 5) ? hot2 - (size_t)view.n_nodes2 * sizeof(Node2) + nodew : hot1;
     const bool lds = hot_bytes > 0 && hot_bytes + stack_bytes <= lds_max && !tun.no_lds && kernel != 5;  // kernel 5: scene in L2/HBM always
     const int integ = plan.integrator;
-    if (integ == 1 && view.n_lights == 0 && !env) throw RtError(RT_ERR_ARG, "integrator 1 (light importance sampling) needs rt_scene_set_lights");
+    if (integ == 1 && view.n_lights == 0 && !env && !area) throw RtError(RT_ERR_ARG, "integrator 1 (light importance sampling) needs rt_scene_set_lights");
     if (integ == 2 && !plan.sppm_est) throw RtError(RT_ERR_ARG, "integrator 2 (SPPM) is reached through rt_render_sppm");
     if (integ != 0 && book2)
         throw RtError(RT_ERR_UNSUPPORTED, "the book-2 extensions (moving spheres, noise textures, an open shutter) render with integrator 0 (kernels 1 and 2)");
@@ -4254,6 +4385,9 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
     if (bg && env && integ == 1)  // (media and the book-2 kinds were refused above: GENERAL is 1 or 3 here)
         fn = (kernel == 2) ? (lds ? pick_pt_kernel_env<2, true>(nest) : pick_pt_kernel_env<2, false>(nest))
                            : (lds ? pick_pt_kernel_env<1, true>(nest) : pick_pt_kernel_env<1, false>(nest));
+    if (area)  // (likewise GENERAL 1 or 3; the variant tests the background and the env table at run time)
+        fn = (kernel == 2) ? (lds ? pick_pt_kernel_area<2, true>(nest) : pick_pt_kernel_area<2, false>(nest))
+                           : (lds ? pick_pt_kernel_area<1, true>(nest) : pick_pt_kernel_area<1, false>(nest));
     // scene too large for LDS: spend what is left after the stacks on the shallowest BVH levels (the Node2 array is depth-sorted)
     int n_top = 0, n_topq = 0;
     if (kernel == 2 && !lds && lds_max > stack_bytes) {
@@ -4279,7 +4413,7 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
     const int grid = di.cus * blocks_per_cu;
     // a rank that owns fewer tiles than the launch has waves: single-unit jobs (below) folded out of order (next_unit_pool)
     const bool pool = POOL_MODE && SINGLE_UNITS_BELOW_WAVES && plan.tiles_owned < (int64_t)grid * (PT_BLOCK / 64) &&
-                      ((kernel == 2 && !media && !book2 && !nest && !bg) || (kernel == 5 && fn_coop == fn_coop_early));
+                      ((kernel == 2 && !media && !book2 && !nest && !bg && !area) || (kernel == 5 && fn_coop == fn_coop_early));
     if (pool && kernel == 2) {
         fn = pick_pt_kernel_pool(lds, general, integ);  // (same resources as the variant the occupancy was asked for)
         if (smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
@@ -4749,6 +4883,8 @@ void render_sppm(const rt_scene& s, const CameraDev& cam, RenderPlan plan, const
     const Tuning tun = tuning();  // one snapshot per call
     if (s.flat.view.off_bg != 0u)
         throw RtError(RT_ERR_UNSUPPORTED, "SPPM does not render a scene with a background: the photon pass has no environment emitter (DESIGN.md s4g)");
+    if (s.flat.view.off_area != 0u)
+        throw RtError(RT_ERR_UNSUPPORTED, "SPPM does not render a scene with area lights: the photon pass has no emitter for them (DESIGN.md s4i)");
     if (s.lights.empty()) throw RtError(RT_ERR_ARG, "SPPM needs lights (rt_scene_set_lights)");
     if (s.flat.view.n_msph != 0u || s.flat.view.has_noise != 0u || plan.time1 > plan.time0)
         throw RtError(RT_ERR_UNSUPPORTED, "the photon passes have no notion of time: the book-2 extensions (moving spheres, noise textures, an open shutter) render with integrator 0");
@@ -5035,6 +5171,22 @@ void debug_env_eval_device(const rt_scene& s, int mode, size_t n, const double* 
     HIP_CHECK(hipMemset(err.p, 0, 4));
     HIP_CHECK(hipMemcpy(din.p, in, n_in, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(env_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, view, mode, n, (const double*)din.p, (double*)dout.p, (int*)err.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpy(out, dout.p, n_out, hipMemcpyDeviceToHost));
+}
+void debug_area_eval_device(const rt_scene& s, int mode, size_t n, const double* in, double* out) {
+    if (!s.committed) throw RtError(RT_ERR_NOT_COMMITTED, "scene not committed");
+    if (s.flat.view.off_area == 0u) throw RtError(RT_ERR_ARG, "the scene has no area lights (rt_scene_set_area_lights)");
+    int dev = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    FlatView view = s.flat.view;
+    view.base = device_blob(s, dev);
+    const size_t n_in = n * (mode == 0 ? 7 : 6) * sizeof(double), n_out = n * (mode == 0 ? 4 : 1) * sizeof(double);
+    DevBuf din, dout;
+    din.alloc(n_in);
+    dout.alloc(n_out);
+    HIP_CHECK(hipMemcpy(din.p, in, n_in, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(area_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, view, mode, n, (const double*)din.p, (double*)dout.p);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpy(out, dout.p, n_out, hipMemcpyDeviceToHost));
 }

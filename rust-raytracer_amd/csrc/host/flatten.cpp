@@ -297,6 +297,129 @@ uint32_t append(std::vector<char>& blob, const std::vector<T>& v) {
     return (uint32_t)off;
 }
 
+// ---- area lights (rtamd.h "area lights"): objects -> world-space triangles, in the order the header pins ----
+struct AreaLower {
+    const rt_scene& s;
+    std::vector<const double*> xf;  // the Transforms above the current object, outermost first (their stored `trans`)
+    std::vector<rt_area_tri>& out;
+    int light;
+    void tri(const double* pa, const double* pb, const double* pc) {
+        double v[3][3];
+        const double* src[3] = {pa, pb, pc};
+        for (int k = 0; k < 3; k++) {
+            double p[3] = {src[k][0], src[k][1], src[k][2]};
+            for (size_t l = xf.size(); l-- > 0;) {  // innermost first (xf_point, vec3.rs:174-178)
+                const double* t = xf[l];
+                double o[3];
+                for (int i = 0; i < 3; i++) o[i] = t[i * 4 + 0] * p[0] + t[i * 4 + 1] * p[1] + t[i * 4 + 2] * p[2] + t[i * 4 + 3] * 1.;
+                for (int i = 0; i < 3; i++) p[i] = o[i];
+            }
+            for (int i = 0; i < 3; i++) v[k][i] = p[i];
+        }
+        rt_area_tri r{};
+        for (int i = 0; i < 3; i++) {
+            r.a[i] = v[0][i];
+            r.e0[i] = v[1][i] - v[0][i];
+            r.e1[i] = v[2][i] - v[0][i];
+        }
+        r.n[0] = r.e0[1] * r.e1[2] - r.e0[2] * r.e1[1];
+        r.n[1] = r.e0[2] * r.e1[0] - r.e0[0] * r.e1[2];
+        r.n[2] = r.e0[0] * r.e1[1] - r.e0[1] * r.e1[0];
+        r.area2 = std::sqrt(r.n[0] * r.n[0] + r.n[1] * r.n[1] + r.n[2] * r.n[2]);
+        r.light = light;
+        if (!(r.area2 > 0.) || !std::isfinite(r.area2)) return;  // degenerate: dropped
+        out.push_back(r);
+    }
+    void rect(const ObjectRec& o) {
+        double P[4][3];  // P00, P10, P01, P11: the first in-plane axis varies first
+        const double a[2] = {o.a0, o.a1}, b[2] = {o.b0, o.b1};
+        for (int j = 0; j < 2; j++)
+            for (int i = 0; i < 2; i++) {
+                double* p = P[2 * j + i];
+                if (o.axis == 2) { p[0] = a[i]; p[1] = b[j]; p[2] = o.k; }
+                else if (o.axis == 1) { p[0] = a[i]; p[1] = o.k; p[2] = b[j]; }
+                else { p[0] = o.k; p[1] = a[i]; p[2] = b[j]; }
+            }
+        tri(P[0], P[1], P[3]);
+        tri(P[0], P[3], P[2]);
+    }
+    void lower(int id) {
+        const ObjectRec& o = s.objects[id];
+        switch (o.type) {
+            case OBJ_RECT:
+                rect(o);
+                break;
+            case OBJ_TRIANGLE: {
+                const double* P = s.meshes[o.mesh]->pos.data();
+                tri(P + 3 * o.ia, P + 3 * o.ib, P + 3 * o.ic);
+                break;
+            }
+            case OBJ_MESH:  // the order of `indices`, not of the inner BVH
+                for (int t = 0; t < o.tri_count; t++) lower(o.tri_first + t);
+                break;
+            case OBJ_TRANSFORM:
+                xf.push_back(o.M);
+                lower(o.children[0]);
+                xf.pop_back();
+                break;
+            case OBJ_CUBE:
+            case OBJ_LIST:
+            case OBJ_BVH:
+                for (int c : o.children) lower(c);
+                break;
+            default:
+                throw RtError(RT_ERR_ARG, "an area light holds rectangles, cubes and triangles only");
+        }
+    }
+};
+// the table as the blob holds it (common/flat.h: AreaHdr, AreaLightDev[], AreaTriDev[]); `tris` = what rt_scene_area_light_tris reports
+std::vector<char> lower_area_lights(const rt_scene& s, std::vector<rt_area_tri>& tris) {
+    tris.clear();
+    const size_t n_lights = s.area_lights.size();
+    std::vector<AreaLightDev> lights(n_lights);
+    for (size_t l = 0; l < n_lights; l++) {
+        check_area_light(s, s.area_lights[l]);
+        AreaLower lo{s, {}, tris, (int)l};
+        lights[l].first = (uint32_t)tris.size();
+        lo.lower(s.area_lights[l]);
+        lights[l].count = (uint32_t)(tris.size() - lights[l].first);
+        if (tris.size() > (size_t)AREA_MAX_TRIS)
+            throw RtError(RT_ERR_UNSUPPORTED, "the area lights of a scene hold at most 1024 triangles (their pdf is a linear scan)");
+        if (lights[l].count == 0u) throw RtError(RT_ERR_ARG, "area light " + std::to_string(l) + " has no triangle of non-zero area");
+    }
+    std::vector<AreaTriDev> dev(tris.size());
+    for (size_t l = 0; l < n_lights; l++) {
+        const uint32_t first = lights[l].first, end = first + lights[l].count;
+        double amax = 0.;
+        for (uint32_t k = first; k < end; k++) amax = std::fmax(amax, tris[k].area2);
+        uint64_t cum = 0;
+        for (uint32_t k = first; k < end; k++) {
+            rt_area_tri& t = tris[k];
+            const double f = std::floor(t.area2 / amax * 4294967295.0);
+            t.q = f >= 1. ? (uint32_t)f : 1u;
+            cum += t.q;
+            AreaTriDev& d = dev[k];
+            for (int i = 0; i < 3; i++) {
+                d.a[i] = t.a[i]; d.e0[i] = t.e0[i]; d.e1[i] = t.e1[i]; d.n[i] = t.n[i];
+            }
+            d.area2 = t.area2;
+            d.cum = cum;
+            d.q = t.q;
+            d.light = (uint32_t)l;
+            d.pad = 0;
+        }
+        lights[l].total = cum;
+    }
+    AreaHdr hdr{};
+    hdr.n_lights = (uint32_t)n_lights;
+    hdr.n_tris = (uint32_t)tris.size();
+    std::vector<char> tab(sizeof(hdr) + lights.size() * sizeof(AreaLightDev) + dev.size() * sizeof(AreaTriDev));
+    std::memcpy(tab.data(), &hdr, sizeof(hdr));
+    std::memcpy(tab.data() + sizeof(hdr), lights.data(), lights.size() * sizeof(AreaLightDev));
+    if (!dev.empty()) std::memcpy(tab.data() + sizeof(hdr) + lights.size() * sizeof(AreaLightDev), dev.data(), dev.size() * sizeof(AreaTriDev));
+    return tab;
+}
+
 }  // namespace
 
 void flatten(rt_scene& s) {
@@ -782,6 +905,10 @@ void flatten(rt_scene& s) {
     }
     v.off_lights = append(f.blob, lights);
     v.n_lights = (uint32_t)(lights.size() / 2);
+    v.off_area = 0u;
+    f.area_tris.clear();
+    if (!s.area_lights.empty())  // (a scene without area lights keeps its blob, and its fingerprint, byte for byte)
+        v.off_area = append(f.blob, lower_area_lights(s, f.area_tris));
     v.off_vpos = append(f.blob, b.vpos);  // kept for introspection; the kernels read tripre instead
     v.off_vnrm = append(f.blob, b.vnrm);
     v.off_texels = append(f.blob, texels);

@@ -198,6 +198,33 @@ bool bounding_box(const rt_scene& s, int o, Box& out) {
     return true;
 }
 
+static void check_area_light_rec(const rt_scene& s, int id, int xf_depth) {
+    const ObjectRec& o = s.objects[id];
+    switch (o.type) {
+        case OBJ_RECT:
+        case OBJ_TRIANGLE:
+            if (s.materials[o.material].type != MAT_DIFFUSE_LIGHT)
+                throw RtError(RT_ERR_ARG, "every leaf of an area light must have a DiffuseLight material");
+            return;
+        case OBJ_TRANSFORM:
+            if (xf_depth + 1 > (int)XF_MAX_DEPTH) throw RtError(RT_ERR_ARG, "an area light lies under more than 8 nested Transforms");
+            check_area_light_rec(s, o.children[0], xf_depth + 1);
+            return;
+        case OBJ_CUBE:
+        case OBJ_MESH:
+        case OBJ_LIST:
+        case OBJ_BVH:
+            for (int c : o.children) check_area_light_rec(s, c, xf_depth);
+            return;
+        default:
+            throw RtError(RT_ERR_ARG, "an area light holds rectangles, cubes and triangles only (no sphere, moving sphere or medium)");
+    }
+}
+void check_area_light(const rt_scene& s, int o) {
+    check_obj(s, o);
+    check_area_light_rec(s, o, 0);
+}
+
 // aabb.rs:33-45
 static Box surrounding(const Box& a, const Box& b) {
     Box r;
@@ -386,9 +413,12 @@ int add_mesh(rt_scene& s, int n_vert, const double* pos, const double* nrm, int 
         }
         tris.push_back(push(s, std::move(o)));
     }
+    const int tri_first = tris.front();
     int bvh = add_bvh_build(s, std::move(tris), bvh_seed);
     ObjectRec m;
     m.type = OBJ_MESH;
+    m.tri_first = tri_first;
+    m.tri_count = n_tri;
     m.material = mat;
     m.mesh = mesh_id;
     m.children = {bvh};

@@ -54,6 +54,7 @@ struct ObjectRec {
     double density = 0;                         // medium: d of ConstantMedium::new (neg_inv_density = -1 / d); material = phase function
     int mesh = -1;                              // triangle / mesh: index into Scene::meshes
     uint32_t ia = 0, ib = 0, ic = 0;            // triangle vertex indices
+    int tri_first = -1, tri_count = 0;          // mesh: its triangles are the objects [tri_first, tri_first + tri_count), in the order of `indices`
     double M[16], Minv[16];                     // transform (row-major)
     bool has_box = false;
     Box box;
@@ -73,6 +74,8 @@ struct FlatScene {
     uint32_t xf_nest = 0;
     // a light of rt_scene_set_lights is (part of) the boundary of a ConstantMedium: the SPPM photon pass refuses such scenes
     bool light_in_medium = false;
+    // the area light table as rt_scene_area_light_tris reports it; empty for a scene without area lights
+    std::vector<rt_area_tri> area_tris;
 };
 
 struct DeviceCopy {
@@ -91,6 +94,7 @@ struct rt_scene {
     std::vector<std::unique_ptr<rtamd::MeshData>> meshes;
     int root = -1;
     std::vector<int> lights;  // World::new's lights (object ids)
+    std::vector<int> area_lights;  // rt_scene_set_area_lights (object ids; flattened only when non-empty: DESIGN.md s4i)
     rt_background background{};  // rt_scene_set_background; kind 0 = none (flattened only when kind != 0: DESIGN.md s4g)
     rt_env_sampling env_sampling{};  // rt_scene_set_env_sampling; flattened only when enabled
     bool committed = false;
@@ -133,6 +137,9 @@ int add_bvh_build(rt_scene& s, std::vector<int> objs, uint64_t bvh_seed);
 void check_obj(const rt_scene& s, int o);
 void check_mat(const rt_scene& s, int m);
 bool bounding_box(const rt_scene& s, int o, Box& out);
+// rt_scene_set_area_lights' checks on one object (throws RT_ERR_ARG): only rectangles, cubes and triangles with a DiffuseLight material,
+// in lists / BVH nodes / meshes, under at most XF_MAX_DEPTH nested Transforms
+void check_area_light(const rt_scene& s, int o);
 
 // flatten.cpp
 void flatten(rt_scene& s);

@@ -338,19 +338,23 @@ class World {
     Camera cam;
     // bg: rt_scene_set_background before the commit (nullptr: none, the reference's black)
     // env: rt_scene_set_env_sampling before the commit (nullptr: off)
+    // area_lights: rt_scene_set_area_lights before the commit -- emissive rectangles, cubes and meshes (also under Transforms) that
+    // integrator 1 samples beside `lights`, the reference's two Light shapes
     World(const HitableList& hitable_list, Camera camera, const HitableList& lights = {}, uint64_t bvh_seed = 1, const rt_background* bg = nullptr,
-          const rt_env_sampling* env = nullptr)
+          const rt_env_sampling* env = nullptr, const HitableList& area_lights = {})
         : cam(camera) {
         check(rt_scene_create(&s_));
         try {
             Emitter e(s_, bvh_seed);
-            std::vector<int> ids, lids;
+            std::vector<int> ids, lids, aids;
             for (auto& h : hitable_list) ids.push_back(e.once(h.get()));
             for (auto& l : lights) lids.push_back(e.once(l.get()));  // a light shared with the hitable list is emitted once
+            for (auto& l : area_lights) aids.push_back(e.once(l.get()));
             check(rt_world_new(s_, (int)ids.size(), ids.data(), bvh_seed));
             if (!lids.empty()) check(rt_scene_set_lights(s_, (int)lids.size(), lids.data()));
             if (bg) check(rt_scene_set_background(s_, bg));
             if (env) check(rt_scene_set_env_sampling(s_, env));
+            if (!aids.empty()) check(rt_scene_set_area_lights(s_, (int)aids.size(), aids.data()));
             check(rt_scene_commit(s_));
         } catch (...) {
             rt_scene_destroy(s_);
@@ -406,6 +410,12 @@ class World {
         rt_env_sampling e{};
         check(rt_scene_get_env_sampling(s_, &e));
         return e;
+    }
+    // rt_scene_area_light_tris: the world-space triangles the area lights were lowered to
+    std::vector<rt_area_tri> area_light_tris() const {
+        std::vector<rt_area_tri> t((size_t)check(rt_scene_area_light_tris(s_, 0, nullptr)));
+        if (!t.empty()) check(rt_scene_area_light_tris(s_, (int)t.size(), t.data()));
+        return t;
     }
     ~World() { rt_scene_destroy(s_); }
     World(const World&) = delete;

@@ -81,6 +81,11 @@ class rt_env_sampling(C.Structure):
     _fields_ = [("enabled", C.c_int32), ("width", C.c_int32), ("height", C.c_int32)]
 
 
+class rt_area_tri(C.Structure):
+    _fields_ = [("a", C.c_double * 3), ("e0", C.c_double * 3), ("e1", C.c_double * 3), ("n", C.c_double * 3), ("area2", C.c_double),
+                ("q", C.c_uint32), ("light", C.c_int32)]
+
+
 BACKGROUND_KINDS = ("none", "constant", "gradient", "texture")
 SKY = ((1.0, 1.0, 1.0), (0.5, 0.7, 1.0))  # book 1's ray_color: white straight down, (0.5, 0.7, 1.0) straight up
 
@@ -158,6 +163,8 @@ _SIGS = [
     ("rt_scene_set_lights", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     ("rt_scene_set_background", C.c_int, [C.c_void_p, C.POINTER(rt_background)]),
     ("rt_scene_get_background", C.c_int, [C.c_void_p, C.POINTER(rt_background)]),
+    ("rt_scene_set_area_lights", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    ("rt_scene_area_light_tris", C.c_int, [C.c_void_p, C.c_int, C.POINTER(rt_area_tri)]),
     ("rt_scene_set_env_sampling", C.c_int, [C.c_void_p, C.POINTER(rt_env_sampling)]),
     ("rt_scene_get_env_sampling", C.c_int, [C.c_void_p, C.POINTER(rt_env_sampling)]),
     ("rt_scene_cornell_box", C.c_int, [C.c_void_p, C.c_char_p, C.c_double, C.c_uint64, C.POINTER(rt_camera)]),
@@ -211,6 +218,8 @@ _SIGS = [
     ("rt_debug_env_table_device", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
     ("rt_debug_env_sample_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, _dp]),
     ("rt_debug_env_pdf_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, _dp]),
+    ("rt_debug_area_sample_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, _dp]),
+    ("rt_debug_area_pdf_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, _dp]),
 ]
 ABI_SYMBOLS = [s[0] for s in _SIGS]
 
@@ -454,13 +463,32 @@ class World:
         return OBJECT_TYPES[d.type], {"material": d.material, "axis": d.axis, "v": list(d.v), "children": list(kids[:d.n_children])}
 
     # --- World::new / commit ---
-    def new(self, hitable_list, lights=(), bvh_seed=1):
-        """World::new(hitable_list, cam, lights) (world.rs:15-25): root = BVHNode::new(hitable_list); then commit."""
+    def new(self, hitable_list, lights=(), bvh_seed=1, area_lights=()):
+        """World::new(hitable_list, cam, lights) (world.rs:15-25): root = BVHNode::new(hitable_list); then commit.
+        area_lights: objects for set_area_lights."""
         arr = (C.c_int * len(hitable_list))(*hitable_list)
         _chk(self.L.rt_world_new(self.h, len(hitable_list), arr, int(bvh_seed)))
         if len(lights):
             self.set_lights(list(lights))
+        if len(area_lights):
+            self.set_area_lights(list(area_lights))
         return self.commit()
+
+    def set_area_lights(self, objs):
+        """rt_scene_set_area_lights (before commit): emissive rectangles, cubes, triangles and meshes -- lists and BVH nodes of them, under
+        up to 8 nested Transforms -- that integrator 1 samples beside the object lights; an empty list clears it."""
+        arr = (C.c_int * len(objs))(*objs)
+        _chk(self.L.rt_scene_set_area_lights(self.h, len(objs), arr))
+        return self
+
+    def area_light_tris(self):
+        """rt_scene_area_light_tris: the world-space triangles a committed scene's area lights were lowered to, as a numpy record array
+        with the fields a, e0, e1, n (f64 [3]), area2 (f64), q (uint32), light (int32)"""
+        n = _chk(self.L.rt_scene_area_light_tris(self.h, 0, None))
+        out = np.zeros(n, dtype=AREA_TRI_DTYPE)
+        if n:
+            _chk(self.L.rt_scene_area_light_tris(self.h, n, out.ctypes.data_as(C.POINTER(rt_area_tri))))
+        return out
 
     def set_lights(self, lights):
         arr = (C.c_int * len(lights))(*lights)
@@ -728,6 +756,25 @@ class World:
         out = np.zeros(d.shape[0], dtype=np.float64)
         _chk(self.L.rt_debug_env_pdf_device(self.h, int(device), d.shape[0], d.ctypes.data_as(_dp), out.ctypes.data_as(_dp)))
         return out
+
+    def debug_area_sample(self, o_xi, device=0):
+        """rt_debug_area_sample_device: [n, 7] = origin, xi0 (picks the area light), xi1..xi3 -> [n, 4] = direction, pdf (summed over
+        all area lights)"""
+        x = np.ascontiguousarray(o_xi, dtype=np.float64).reshape(-1, 7)
+        out = np.zeros((x.shape[0], 4), dtype=np.float64)
+        _chk(self.L.rt_debug_area_sample_device(self.h, int(device), x.shape[0], x.ctypes.data_as(_dp), out.ctypes.data_as(_dp)))
+        return out
+
+    def debug_area_pdf(self, rays, device=0):
+        """rt_debug_area_pdf_device: rays [n, 6] = origin, direction (any length) -> pdf [n] per solid angle, summed over all area lights"""
+        r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        out = np.zeros(r.shape[0], dtype=np.float64)
+        _chk(self.L.rt_debug_area_pdf_device(self.h, int(device), r.shape[0], r.ctypes.data_as(_dp), out.ctypes.data_as(_dp)))
+        return out
+
+
+AREA_TRI_DTYPE = np.dtype([("a", "<f8", 3), ("e0", "<f8", 3), ("e1", "<f8", 3), ("n", "<f8", 3), ("area2", "<f8"), ("q", "<u4"), ("light", "<i4")])
+assert AREA_TRI_DTYPE.itemsize == C.sizeof(rt_area_tri) == 112
 
 
 def load_scene_file(path, commit=True):

@@ -160,6 +160,19 @@ pub struct rt_env_sampling {
     pub height: i32,
 }
 
+/// include/rtamd.h rt_area_tri (rt_scene_area_light_tris): one world-space triangle of a lowered area light
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct rt_area_tri {
+    pub a: [c_double; 3],
+    pub e0: [c_double; 3],
+    pub e1: [c_double; 3],
+    pub n: [c_double; 3],
+    pub area2: c_double,
+    pub q: u32,
+    pub light: i32,
+}
+
 /// include/rtamd.h rt_adaptive_config (rt_default_adaptive_config fills it)
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -279,6 +292,8 @@ extern "C" {
     pub fn rt_scene_set_root(s: *mut rt_scene, object: c_int) -> c_int;
     pub fn rt_scene_set_background(s: *mut rt_scene, bg: *const rt_background) -> c_int;
     pub fn rt_scene_get_background(s: *const rt_scene, out: *mut rt_background) -> c_int;
+    pub fn rt_scene_set_area_lights(s: *mut rt_scene, n: c_int, objects: *const c_int) -> c_int;
+    pub fn rt_scene_area_light_tris(s: *const rt_scene, capacity: c_int, out: *mut rt_area_tri) -> c_int;
     pub fn rt_scene_set_env_sampling(s: *mut rt_scene, cfg: *const rt_env_sampling) -> c_int;
     pub fn rt_scene_get_env_sampling(s: *const rt_scene, out: *mut rt_env_sampling) -> c_int;
     pub fn rt_scene_cornell_box(s: *mut rt_scene, cube_obj_path: *const c_char, aspect_ratio: c_double, bvh_seed: u64, cam_out: *mut rt_camera) -> c_int;
@@ -326,6 +341,8 @@ extern "C" {
     pub fn rt_debug_env_table_device(s: *const rt_scene, device: c_int, w: *mut c_int, h: *mut c_int, q_host: *mut u32) -> c_int;
     pub fn rt_debug_env_sample_device(s: *const rt_scene, device: c_int, n: usize, xi4_host: *const c_double, out_host: *mut c_double) -> c_int;
     pub fn rt_debug_env_pdf_device(s: *const rt_scene, device: c_int, n: usize, dirs_host: *const c_double, pdf_host: *mut c_double) -> c_int;
+    pub fn rt_debug_area_sample_device(s: *const rt_scene, device: c_int, n: usize, in_host: *const c_double, out_host: *mut c_double) -> c_int;
+    pub fn rt_debug_area_pdf_device(s: *const rt_scene, device: c_int, n: usize, rays_host: *const c_double, pdf_host: *mut c_double) -> c_int;
 }
 
 // ------------------------------------------------------------------ errors ----
@@ -500,6 +517,10 @@ impl SceneBuilder {
     pub fn set_lights(&mut self, lights: &[Id]) -> Result<(), RtError> {
         check(unsafe { rt_scene_set_lights(self.raw, lights.len() as c_int, lights.as_ptr()) }).map(|_| ())
     }
+    /// rt_scene_set_area_lights: emissive rectangles, cubes and meshes (also under Transforms) as lights of integrator 1 (before commit)
+    pub fn set_area_lights(&mut self, objects: &[Id]) -> Result<(), RtError> {
+        check(unsafe { rt_scene_set_area_lights(self.raw, objects.len() as c_int, objects.as_ptr()) }).map(|_| ())
+    }
     /// rt_scene_set_background: what a ray that leaves the scene sees (before commit)
     pub fn set_background(&mut self, bg: &rt_background) -> Result<(), RtError> {
         check(unsafe { rt_scene_set_background(self.raw, bg) }).map(|_| ())
@@ -557,6 +578,13 @@ impl Scene {
         let mut b = rt_background::default();
         check(unsafe { rt_scene_get_background(self.raw, &mut b) })?;
         Ok(b)
+    }
+    /// rt_scene_area_light_tris: the world-space triangles the area lights were lowered to
+    pub fn area_light_tris(&self) -> Result<Vec<rt_area_tri>, RtError> {
+        let n = check(unsafe { rt_scene_area_light_tris(self.raw, 0, std::ptr::null_mut()) })?;
+        let mut t = vec![rt_area_tri::default(); n as usize];
+        check(unsafe { rt_scene_area_light_tris(self.raw, n, t.as_mut_ptr()) })?;
+        Ok(t)
     }
     pub fn env_sampling(&self) -> Result<rt_env_sampling, RtError> {
         let mut e = rt_env_sampling::default();

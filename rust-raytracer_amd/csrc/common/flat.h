@@ -185,14 +185,14 @@ struct FlatView {  // by-value kernel argument
     // the reference-order program's tables in GLOBAL memory, for the out-of-line walk that settles an exact tie (tie_resolve, kernels.hip)
     uint32_t off_tie_view;
     uint32_t n_nodes;
-    uint32_t stage_bytes;  // kernel 1 stages bytes [0, stage_bytes) into LDS: [meta|boxes|spheres|rects|tris|xforms|vpos]
+    uint32_t stage_bytes;  // kernel 1 stages bytes [0, stage_bytes) into LDS: [meta|boxes|spheres|rects|tris|tripre|xforms] (vpos: cold part)
     uint32_t kinds_mask;   // bit k set if some node has kind k
     uint32_t total_bytes;
     // accel (kernel 2)
     uint32_t accel_ok;        // 0: no accel was built (unbounded item, depth overflow, ...): kernel 1 only
     uint32_t off_n2, off_items2, off_inst2;
     uint32_t root2;           // root ref
-    uint32_t stage2_begin, stage2_end;  // kernel 2 stages [stage2_begin, stage2_end): [spheres|rects|tris|xforms|vpos|n2|items2|inst2]
+    uint32_t stage2_begin, stage2_end;  // kernel 2 stages [stage2_begin, stage2_end): [spheres|rects|tris|tripre|xforms|items2|inst2|tripre2|n2]
     uint32_t stack2;          // stack entries a lane can need
     uint32_t off_tripre;      // per triangle {pa, pb-pa, pc-pa, pad}: 10 f64 (hot part, after tris)
     uint32_t off_lights, n_lights;  // cold part: per light {NK_SPHERE | NK_RECT_XZ, payload index}

@@ -237,4 +237,227 @@ static uint32_t accel_build_bvh_impl(AccelBuild& out, std::vector<AccelItem>& it
     return build(c, 0, (int)items.size(), depth0, true);
 }
 
+// ---- the accel of a scene: the stages of build_scene_accel, in the order it calls them -------------------------------------------
+namespace {
+
+bool is_f32(double x) { return (double)(float)x == x; }
+
+// An instance's item in the enclosing space carries the Transform's own bounding box (the box of the 8 transformed corners
+// of the child's box, transform.rs:104-150): loose for a rotated mesh.  For culling, the union of the transformed boxes of the
+// instance's ITEMS is as valid (affine images of the items lie inside it; the f64 rounding of M * corner is orders of
+// magnitude below the pad added at build time) and tighter: fewer rays enter the object-space BVH for nothing.
+// (innermost chains first: an instance's own item box, in its parent's context, is tightened before the parent's items are unioned)
+void tighten_instance_boxes(std::vector<AccelContext>& ctx, const std::vector<size_t>& by_depth) {
+    for (size_t k = by_depth.size(); k-- > 0;) {
+        const size_t i = by_depth[k];
+        const auto& c = ctx[i];
+        if (c.items.empty() || !c.M) continue;
+        Box tb = empty_box();
+        for (const auto& it : c.items)
+            for (int corner = 0; corner < 8; corner++) {
+                const double x = (corner & 1) ? it.box.mx[0] : it.box.mn[0], y = (corner & 2) ? it.box.mx[1] : it.box.mn[1],
+                             z = (corner & 4) ? it.box.mx[2] : it.box.mn[2];
+                for (int a = 0; a < 3; a++) {
+                    const double w = c.M[4 * a] * x + c.M[4 * a + 1] * y + c.M[4 * a + 2] * z + c.M[4 * a + 3];
+                    tb.mn[a] = std::fmin(tb.mn[a], w);
+                    tb.mx[a] = std::fmax(tb.mx[a], w);
+                }
+            }
+        bool finite = true;
+        for (int a = 0; a < 3; a++) finite = finite && std::isfinite(tb.mn[a]) && std::isfinite(tb.mx[a]);
+        if (!finite) continue;
+        const uint32_t want = NK_INSTANCE | ((uint32_t)(i - 1) << NK_BITS);
+        for (auto& pc : ctx)
+            for (auto& it : pc.items)
+                if (it.kp == want)
+                    for (int a = 0; a < 3; a++) {  // never larger than the Transform's own box; a margin of 2^-40 of its size for the rounding
+                        const double m = std::ldexp(std::fabs(tb.mx[a]) + std::fabs(tb.mn[a]), -40);
+                        it.box.mn[a] = std::fmax(it.box.mn[a], tb.mn[a] - m);
+                        it.box.mx[a] = std::fmin(it.box.mx[a], tb.mx[a] + m);
+                    }
+    }
+}
+
+// Which instances can kernels 5 / 6 defer?  Those that hold nothing but triangles with f32 vertices (flat.h "Compact instance data").
+// The others are entered in the lane: their items in the world's context become NK_INSTANCE_INLINE.  Also bounds every instance's
+// object-space ray origins (inst_oo); an instance beyond the range the box tests are proven for rules the accel out.
+void classify_instances(SceneAccel& a, std::vector<AccelContext>& ctx, const std::vector<size_t>& by_depth, const TriTables& t) {
+    a.compact_cand.assign(ctx.size() - 1, 1);
+    a.inst_oo.assign(ctx.size() - 1, 0.);
+    for (size_t i : by_depth) {
+        if (!a.ab.ok) break;
+        auto& c = ctx[i];
+        // object-space origin bound: |M^-1 o| <= sum_b |Minv[a][b]| * |o|max + |Minv[a][3]|, composed along the chain (the
+        // parent's bound is its own object-space one; by_depth computes it first)
+        const double o_parent = c.parent == 0 ? a.origin_limit : a.inst_oo[c.parent - 1];
+        double oo = 0.;
+        for (int k = 0; k < 3; k++)
+            oo = std::fmax(oo, (std::fabs(c.Minv[4 * k]) + std::fabs(c.Minv[4 * k + 1]) + std::fabs(c.Minv[4 * k + 2])) * o_parent +
+                                   std::fabs(c.Minv[4 * k + 3]));
+        for (auto& it : c.items)  // hit points inside the instance also serve as origins of secondary rays (in world space only)
+            for (int k = 0; k < 3; k++) oo = std::fmax(oo, std::fmax(std::fabs(it.box.mn[k]), std::fabs(it.box.mx[k])));
+        if (!(oo < 68719476736.)) { a.ab.ok = false; break; }
+        a.inst_oo[i - 1] = oo;
+        char& cand = a.compact_cand[i - 1];
+        for (auto& it : c.items) {
+            if ((it.kp & NK_MASK) != NK_TRI) { cand = 0; break; }
+            const uint32_t tri = it.kp >> NK_BITS;
+            for (int c3 = 0; c3 < 3 && cand; c3++)
+                for (int k = 0; k < 3; k++)
+                    if (!is_f32(t.vpos[3 * (size_t)t.tris[4 * (size_t)tri + c3] + k])) cand = 0;
+            if (!cand) break;
+        }
+        if (!cand) {
+            const uint32_t want = NK_INSTANCE | ((uint32_t)(i - 1) << NK_BITS);
+            for (auto& it : ctx[0].items)
+                if (it.kp == want) it.kp = NK_INSTANCE_INLINE | ((uint32_t)(i - 1) << NK_BITS);
+        }
+    }
+}
+
+// The world BVH, then the BVHs of the inline instances, then those of the deferrable ones: the inline instances' leaves sit right
+// behind the world's in the item array, and kernels 5 / 6 stage that prefix in LDS.
+void build_bvhs(SceneAccel& a, std::vector<AccelContext>& ctx, const std::vector<size_t>& by_depth, bool nested, double media_extent,
+                const TriTables& t) {
+    AccelBuild& ab = a.ab;
+    if (ctx[0].items.empty()) ab.ok = false;
+    if (!ab.ok) return;
+    // E_w: largest |coordinate| of the world items; boxes are padded so that rounding a ray origin with
+    // max-abs coordinate <= 64*E_w to f32 (relative error 2^-24) can never make the f32 slab test cull a box
+    // the exact test keeps: 4 * 2^-24 * |o|max covers of = fl32(o) and c = fl32(of * iv)  (derivation above box32
+    // in csrc/device/kernels.hip, which also needs every coordinate below 2^36 in magnitude); the pad is THREE times that
+    // (12 * 2^-24 * |o|max) since round 3 so that box32w, the test of the LDS-resident node table, needs no widening factor
+    // on the far side (its proof, above box32w, uses the extra margin against the relative error of the slab parameters)
+    double ew = media_extent;
+    for (auto& it : ctx[0].items)
+        for (int k = 0; k < 3; k++) ew = std::fmax(ew, std::fmax(std::fabs(it.box.mn[k]), std::fabs(it.box.mx[k])));
+    if (!(ew > 0.) || !std::isfinite(ew)) {
+        ab.ok = false;
+        return;
+    }
+    a.origin_limit = 64. * ew;
+    const double pad_w = 3. * std::ldexp(a.origin_limit, -22);  // 12 * 2^-24 * |o|max
+    if (!(a.origin_limit < 68719476736.)) ab.ok = false;  // 2^36
+    a.root2 = accel_build_bvh(ab, ctx[0].items, pad_w, 0);
+    const int depth_tlas = ab.max_depth;
+    a.world_depth = (uint32_t)depth_tlas;
+    ab.inst.assign(2 * (ctx.size() - 1), 0u);
+    classify_instances(a, ctx, by_depth, t);
+    // (the world BVH was built above with the items' kinds as they were: its leaf items are patched below, after the build)
+    // stack depth at which each context's BVH starts: below its parent's deepest level and one REF_RESTORE entry per level
+    std::vector<int> end_depth(ctx.size(), depth_tlas);
+    for (int pass = 0; pass < 2; pass++) {
+        for (size_t i : by_depth) {  // (a parent holds an instance item: never deferrable, so pass 0 builds it before its children)
+            if (!ab.ok) break;
+            if ((a.compact_cand[i - 1] != 0) != (pass == 1)) continue;  // pass 0: inline instances, pass 1: deferrable ones
+            auto& c = ctx[i];
+            const size_t nodes_before = ab.nodes.size();
+            const int depth_before = ab.max_depth;
+            const int start = end_depth[c.parent] + 1;
+            ab.max_depth = start;
+            uint32_t r = accel_build_bvh(ab, c.items, 3. * std::ldexp(a.inst_oo[i - 1], -22), start);
+            end_depth[i] = ab.max_depth;
+            if (pass == 1) {
+                a.max_inst_nodes = std::max<uint32_t>(a.max_inst_nodes, (uint32_t)(ab.nodes.size() - nodes_before));
+                a.inst_depth = std::max<uint32_t>(a.inst_depth, (uint32_t)std::max(1, ab.max_depth - depth_tlas + 1));
+            }
+            ab.max_depth = std::max(ab.max_depth, depth_before);
+            ab.inst[2 * (i - 1)] = nested ? c.chain : c.xform;
+            ab.inst[2 * (i - 1) + 1] = r;
+        }
+        if (pass == 0) {
+            a.n_world_items = (uint32_t)(ab.items.size() / 2);
+            a.stack_inline = (uint32_t)(ab.max_depth + 2);
+        }
+    }
+    for (size_t j = 0; j < ab.items.size() / 2; j++) {  // the world leaves' instance items, as classified
+        const uint32_t kp = ab.items[2 * j];
+        if ((kp & NK_MASK) == NK_INSTANCE && !a.compact_cand[kp >> NK_BITS]) ab.items[2 * j] = NK_INSTANCE_INLINE | (kp & ~NK_MASK);
+    }
+}
+
+// Relabels the Node2 array by depth (all BVHs interleaved): the first K nodes are the K shallowest, which is what the kernels cache
+// in LDS when the whole scene does not fit.  The world-space nodes then all have an index below world_top.
+void sort_nodes_by_depth(SceneAccel& a) {
+    AccelBuild& ab = a.ab;
+    const size_t nn = ab.nodes.size();
+    std::vector<int> depth(nn, 0);
+    std::vector<uint32_t> stack, world;
+    auto walk = [&](uint32_t root, bool is_world) {
+        if ((root >> REF_TAG_SHIFT) != 0u) return;
+        depth[root] = 0;
+        stack.assign(1, root);
+        while (!stack.empty()) {
+            uint32_t n = stack.back();
+            stack.pop_back();
+            if (is_world) world.push_back(n);
+            for (int k = 0; k < 2; k++) {
+                uint32_t c = ab.nodes[n].child[k];
+                if ((c >> REF_TAG_SHIFT) == 0u) {
+                    depth[c] = depth[n] + 1;
+                    stack.push_back(c);
+                }
+            }
+        }
+    };
+    walk(a.root2, true);
+    for (size_t i = 0; i + 1 < ab.inst.size(); i += 2) walk(ab.inst[i + 1], false);
+    std::vector<uint32_t> order(nn);
+    for (size_t i = 0; i < nn; i++) order[i] = (uint32_t)i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return depth[x] < depth[y]; });
+    std::vector<uint32_t> new_of(nn);
+    for (size_t i = 0; i < nn; i++) new_of[order[i]] = (uint32_t)i;
+    auto remap = [&](uint32_t r) { return ((r >> REF_TAG_SHIFT) == 0u) ? new_of[r] : r; };
+    std::vector<Node2> sorted(nn);
+    for (size_t i = 0; i < nn; i++) {
+        Node2 nd = ab.nodes[order[i]];
+        nd.child[0] = remap(nd.child[0]);
+        nd.child[1] = remap(nd.child[1]);
+        sorted[i] = nd;
+    }
+    ab.nodes.swap(sorted);
+    a.root2 = remap(a.root2);
+    for (size_t i = 0; i + 1 < ab.inst.size(); i += 2) ab.inst[i + 1] = remap(ab.inst[i + 1]);
+    for (uint32_t n : world) a.world_top = std::max(a.world_top, new_of[n] + 1);
+}
+
+// per item slot, the triangle's {pa, e0, e1} record (zeros for non-triangles)
+std::vector<double> triangles_in_item_order(const AccelBuild& ab, const std::vector<double>& tripre) {
+    std::vector<double> tripre2;
+    if (tripre.empty()) return tripre2;
+    const size_t n_items = ab.items.size() / 2;
+    tripre2.assign(n_items * 10, 0.0);
+    for (size_t j = 0; j < n_items; j++) {
+        uint32_t kp = ab.items[2 * j];
+        if ((kp & NK_MASK) == NK_TRI) {
+            const double* src = &tripre[(size_t)(kp >> NK_BITS) * 10];
+            std::copy(src, src + 10, &tripre2[j * 10]);
+        }
+    }
+    return tripre2;
+}
+
+}  // namespace
+
+SceneAccel build_scene_accel(std::vector<AccelContext>& ctx, bool usable, bool nested, double media_extent, const TriTables& t) {
+    SceneAccel a;
+    a.ab.ok = usable;
+    // contexts by chain depth, outermost first (a nested instance's item lives in its parent's context; scenes of depth <= 1: 1, 2, 3 ...)
+    std::vector<size_t> by_depth;
+    for (size_t i = 1; i < ctx.size(); i++) by_depth.push_back(i);
+    std::stable_sort(by_depth.begin(), by_depth.end(), [&](size_t x, size_t y) { return ctx[x].depth < ctx[y].depth; });
+    if (a.ab.ok) tighten_instance_boxes(ctx, by_depth);
+    build_bvhs(a, ctx, by_depth, nested, media_extent, t);
+    if (a.ab.max_depth + 2 > ACCEL_MAX_STACK) a.ab.ok = false;
+    if (a.ab.ok) {
+        sort_nodes_by_depth(a);
+        a.tripre2 = triangles_in_item_order(a.ab, t.tripre);
+    } else {  // an unusable accel leaves no tables behind (the depths and counts stay what they were when it gave up)
+        a.ab.nodes.clear();
+        a.ab.items.clear();
+        a.ab.inst.clear();
+    }
+    return a;
+}
+
 }  // namespace rtamd

@@ -71,7 +71,7 @@ void render_aov(const rt_scene& s, const CameraDev& cam, int width, int height, 
     // t_min >= 0, and the per-lane stacks in LDS
     const double cam_abs = std::fmax(std::fmax(std::fabs(cam.origin[0]), std::fabs(cam.origin[1])), std::fabs(cam.origin[2])) + std::fabs(cam.lens_radius);
     const bool camera_ok = cam_abs <= view.origin_limit2 && std::isfinite(cam_abs) && t_min >= 0.;
-    const size_t stack_bytes = (size_t)view.stack2 * 64 * sizeof(uint32_t);
+    const size_t stack_bytes = walk_stack_bytes(view.stack2, 64);
     const bool accel_usable = view.accel_ok && camera_ok && stack_bytes <= di.lds_max;
     if (kernel == 0) kernel = accel_usable ? 2 : 1;
     if (kernel == 2 && !accel_usable)

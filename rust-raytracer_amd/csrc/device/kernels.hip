@@ -871,6 +871,31 @@ DEV bool box32(float lox, float loy, float loz, float hix, float hiy, float hiz,
 // candidates are then taken up to  bound = max(best t, min(T[j], exit[j]))  instead of the best t, and the boxes are culled against
 // that.  The root a sphere test returns does not depend on how far the range reaches (it is the smallest admissible one), so the
 // closest hit is what the plain walk finds, and T[j] is what a walk restricted to those items would find (up to exit[j]).
+//
+// The stack.  A lane's stack is a column of LDS words, `stride` words apart (row k = entry k of every lane of the workgroup), and every
+// call of traverse2 owns the whole column: callers that run several walks for one ray (traverse2_media's TRACK / LIMIT walks, the
+// instance walks of kernels 5 / 6 after their DEFER walk) run them one after another, each from an empty stack.
+//   * WIDE (the LDS-resident node table): row 0 holds REF_DONE, written by traverse2 itself on entry (a resumed SLICE walk rewrites
+//     the value its column already has); the walk's entries start at row 1.  A pop is therefore unconditional -- `sp -= step;
+//     cur = stk[sp]` -- and the pop of an empty stack returns the sentinel, on which the node loop and the outer loop both end.
+//     Nothing pops after that.  The plain form keeps its emptiness test and starts at row 0: measured, the sentinel gains it
+//     nothing (C4 / C5 reduced inside their spread) and costs the book-2 variant 5 % in spills.
+//   * A REF_RESTORE marker (instance entry) is an ordinary entry: popping it leaves the rows below as they were, sentinel included.
+//   * Capacity.  With depth(n) = the value accel.cpp's build() has for node n (the root of the world BVH is 0; the root of an
+//     instance's BVH is one more than the deepest level of its parent's, accel.cpp build_bvhs: `start = end_depth[parent] + 1`),
+//     the walk holds at most depth(cur) entries while it is at cur: 0 at the root; a push or a step to one child goes one level
+//     down with at most one entry more; a pop returns to an entry pushed at some node m, i.e. to depth(m) + 1 with the <= depth(m)
+//     entries m had; entering an instance from a leaf (depth <= end_depth[parent]) pushes the marker and continues at depth
+//     start = end_depth[parent] + 1.  Hence entries <= max_depth, rows used <= max_depth + 1 with the sentinel, and every column
+//     is sized max_depth + 2 rows or more (FlatView::stack2 = max_depth + 2, stack2_inline likewise for the world-and-inline-
+//     instances part; kernels 5 / 6 take the larger of that and world_depth2 + 2): the sentinel fits with a row to spare and
+//     no size changed with it.  One row too few would not reach a neighbour's column but the ring / job bookkeeping behind the stacks.
+// walk_stack_bytes / coop_stack_rows: the one place the launches and the kernels size these columns from.
+__host__ __device__ inline size_t walk_stack_bytes(uint32_t rows, uint32_t threads) { return (size_t)rows * threads * sizeof(uint32_t); }
+__host__ __device__ inline uint32_t coop_stack_rows(const FlatView& v) {  // kernel 5 (its two walks never share a stack) and the hit queries of kernels 5 / 6
+    const uint32_t d = (v.world_depth2 > v.inst_depth2 ? v.world_depth2 : v.inst_depth2) + 2u;
+    return d > v.stack2_inline ? d : v.stack2_inline;
+}
 struct MediaTrack {
     uint32_t lim[2];  // program index of the medium's BEGIN node; 0: slot unused
     double exitt[2];  // the medium's exit t on this ray (rec2.t)
@@ -930,9 +955,10 @@ DEV Hit traverse2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, d
     if (WIDE) ray32_wide_addr(r, A.n2w_lds);
     int sp = 0;  // stack offset in words (a multiple of stride): avoids an integer multiply per push/pop
     // WIDE: the stack pointer is the LDS byte address itself (one add per push / pop instead of shift-add + add)
-    const uint32_t spw0 = WIDE ? (uint32_t)(uintptr_t)(AS_L uint32_t*)stk : 0u;
     const uint32_t spw_step = 4u * (uint32_t)stride;
-    uint32_t spw = spw0;
+    // ... and row 0 of the lane's column is the sentinel (see "The stack" above): the first free row is row 1
+    uint32_t spw = WIDE ? (uint32_t)(uintptr_t)(AS_L uint32_t*)stk + spw_step : 0u;
+    if (WIDE) *(AS_L uint32_t*)stk = REF_DONE;
     uint32_t cur = WIDE ? wide_ref(A.root2) : A.root2;
     if (resume) {
         cur = ws->cur;
@@ -980,11 +1006,9 @@ DEV Hit traverse2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, d
                     cur = c0;
                 } else if (h1) {
                     cur = c1;
-                } else if (spw != spw0) {
+                } else {  // (an empty stack gives the sentinel)
                     spw -= spw_step;
                     cur = *(const AS_L uint32_t*)(uintptr_t)spw;
-                } else {
-                    cur = REF_DONE;
                 }
                 continue;
             }
@@ -1139,12 +1163,8 @@ DEV Hit traverse2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, d
             if (WIDE) ray32_wide_addr(r, A.n2w_lds);
         }
         if (WIDE) {
-            if (spw != spw0) {
-                spw -= spw_step;
-                cur = *(const AS_L uint32_t*)(uintptr_t)spw;
-            } else {
-                cur = REF_DONE;
-            }
+            spw -= spw_step;
+            cur = *(const AS_L uint32_t*)(uintptr_t)spw;
         } else if (sp > 0) {
             sp -= stride;
             cur = stk[sp];
@@ -2325,7 +2345,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
     const int wave = threadIdx.x >> 6;
     // bookkeeping in LDS behind the stacks: per wave RING_UNITS x {tile, sample block, samples | flags, paths still running} and
     // 8 words of job / ring state; per block the launch constants next_unit() reads
-    uint32_t* book = (uint32_t*)(smem + staged) + (size_t)((ACCEL == 2) ? sv.stack2 : 0u) * PT_BLOCK;
+    uint32_t* book = (uint32_t*)(smem + staged + walk_stack_bytes((ACCEL == 2) ? sv.stack2 : 0u, PT_BLOCK));
     uint32_t* rmeta = book + (size_t)wave * RING_UNITS * 4;
     uint32_t* wst = book + (size_t)(PT_BLOCK / 64) * RING_UNITS * 4 + (size_t)wave * 8;
     int* cfg = (int*)(book + (size_t)(PT_BLOCK / 64) * (RING_UNITS * 4 + 8));
@@ -3220,7 +3240,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel_coop(FlatView sv, CamK cam
     const int lane = threadIdx.x & 63;
     const uint64_t lanemask_lt = (1ull << lane) - 1ull;
     const int wave = threadIdx.x >> 6;
-    uint32_t* book = (uint32_t*)(smem + staged) + (size_t)rk.coop_stack * PT_BLOCK;  // stacks: max(world depth, object-space depth) + 2 entries
+    uint32_t* book = (uint32_t*)(smem + staged + walk_stack_bytes((uint32_t)rk.coop_stack, PT_BLOCK));  // stacks: max(world depth, object-space depth) + 2 entries
     uint32_t* rmeta = book + (size_t)wave * RING_UNITS * 4;
     uint32_t* wst = book + (size_t)(PT_BLOCK / 64) * RING_UNITS * 4 + (size_t)wave * 8;
     int* cfg = (int*)(book + (size_t)(PT_BLOCK / 64) * (RING_UNITS * 4 + 8));
@@ -4272,14 +4292,14 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
     // t_min >= 0 (box32's proof); otherwise kernel 1 (reference order) renders.
     double cam_abs = std::fmax(std::fmax(std::fabs(cam.origin[0]), std::fabs(cam.origin[1])), std::fabs(cam.origin[2])) + std::fabs(cam.lens_radius);
     const bool camera_ok = cam_abs <= view.origin_limit2 && std::isfinite(cam_abs) && plan.t_min >= 0.;
-    const size_t stack2_bytes = (size_t)view.stack2 * PT_BLOCK * sizeof(uint32_t);
+    const size_t stack2_bytes = walk_stack_bytes(view.stack2, PT_BLOCK);
     const size_t hot1 = (size_t)view.stage_bytes, hot2 = (size_t)(view.stage2_end - view.stage2_begin);
     const bool accel2_usable = view.accel_ok && camera_ok && stack2_bytes <= lds_max;  // per-lane stacks live in LDS
     const bool media = (view.kinds_mask & (1u << NK_MEDIUM_BEGIN)) != 0;               // kernel 1, or kernel 2's MEDIA variant (traverse2_media)
     // kernel 5 = kernel 2's BVH with the cooperative instance service (pt_kernel_coop): for scenes with LARGE mesh instances
     // the two walks of kernel 5 never share a stack; the world-space walk includes the instances it enters in the lane (NK_INSTANCE_INLINE)
-    const uint32_t stack5 = std::max(std::max(view.world_depth2, view.inst_depth2) + 2u, view.stack2_inline);
-    const size_t stack5_bytes = (size_t)stack5 * PT_BLOCK * sizeof(uint32_t);
+    const uint32_t stack5 = coop_stack_rows(view);
+    const size_t stack5_bytes = walk_stack_bytes(stack5, PT_BLOCK);
     const size_t coop_world = coop_world_bytes(view);  // world-level tables, always in LDS for this kernel
     const size_t coop_lds = (size_t)3 * COOP_RING * sizeof(uint16_t) + 8 * sizeof(uint32_t) + ((sizeof(CoopArgs) + 15) & ~size_t(15)) + coop_world;  // + three rings of pool-slot ids, counters, argument block
     const bool coop_usable = accel2_usable && general && !media && !book2 && view.coop_data_ok != 0 && view.n_inst2 >= 1 && view.n_inst2 <= (uint32_t)COOP_MAX_INST &&
@@ -4288,10 +4308,10 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
     const uint32_t stack6 = std::max<uint32_t>(std::max(view.world_depth2 + 2u, view.stack2_inline), (uint32_t)WF_ENTRY_STACK + 1u);
     const uint32_t n_entry6 = std::min<uint32_t>((uint32_t)COOP_ENTRY_NODES, view.n_nodes2);
     const size_t wf_lds_pt = coop_world + (size_t)std::min<uint32_t>(128u, view.world_top2) * sizeof(Node2) + (size_t)n_entry6 * sizeof(NodeQ) +
-                             (size_t)stack6 * PT_BLOCK * sizeof(uint32_t) + ((size_t)WF_BOOK_WORDS + CFG_WORDS + 8) * sizeof(uint32_t);
+                             walk_stack_bytes(stack6, PT_BLOCK) + ((size_t)WF_BOOK_WORDS + CFG_WORDS + 8) * sizeof(uint32_t);
     const uint32_t stack6w = view.inst_depth2 + 2u;
     const size_t wf_tables_w = coop_a16(view.stage_bytes - view.off_xforms) + coop_a16(8u * view.n_inst2) + coop_a16((uint32_t)sizeof(QGrid) * view.n_inst2);
-    const size_t wf_lds_walk_min = wf_tables_w + (size_t)stack6w * WF_WALK_BLOCK * sizeof(uint32_t);
+    const size_t wf_lds_walk_min = wf_tables_w + walk_stack_bytes(stack6w, WF_WALK_BLOCK);
     const bool wf_usable = accel2_usable && general && !media && !book2 && view.coop_data_ok != 0 && view.n_inst2 >= 1 && view.n_inst2 <= (uint32_t)WF_MAX_INST &&
                            coop_world <= 32768 && wf_lds_pt <= lds_max && wf_lds_walk_min <= lds_max && plan.max_depth < (1 << 24);
     // a background (rt_scene_set_background): kernels 1 and 2 only (kernels 5 / 6 have no background variants), never the SPPM pass
@@ -4630,7 +4650,7 @@ static void render_tiles_wf(const rt_scene& s, const FlatView& view, const Camer
     if (bpc < 1) bpc = 1;
     const int grid = di.cus * bpc;
     // the walk launch: two 512-thread workgroups per CU when the stacks allow it; what is left of that share of LDS caches NodeQ
-    const size_t stacks_w = (size_t)stack6w * WF_WALK_BLOCK * sizeof(uint32_t);
+    const size_t stacks_w = walk_stack_bytes(stack6w, WF_WALK_BLOCK);
     size_t share = lds_max / 2;
     if (tables_w + stacks_w > share) share = lds_max;
     uint32_t n_topq_w = (uint32_t)std::min<size_t>((share - tables_w - stacks_w) / sizeof(NodeQ), view.n_nodes2);
@@ -4901,12 +4921,12 @@ void render_sppm(const rt_scene& s, const CameraDev& cam, RenderPlan plan, const
     FlatView view = s.flat.view;
     view.base = device_blob(s, dev);
     double cam_abs = std::fmax(std::fmax(std::fabs(cam.origin[0]), std::fabs(cam.origin[1])), std::fabs(cam.origin[2])) + std::fabs(cam.lens_radius);
-    bool accel = view.accel_ok && cam_abs <= view.origin_limit2 && std::isfinite(cam_abs) && (size_t)view.stack2 * 256 * 4 <= di.lds_max;
+    bool accel = view.accel_ok && cam_abs <= view.origin_limit2 && std::isfinite(cam_abs) && walk_stack_bytes(view.stack2, 256) <= di.lds_max;
     const bool nest = s.flat.xf_nest != 0u;  // nested Transforms: the photon / eye passes take kernel 1's chain walk (their accel walks have none)
     if (nest) accel = false;
     // per-lane accel stacks: stack2 entries, as render_tiles gives kernel 2 and its MEDIA variants (traverse2_media's walks take the
     // column one after another; a boundary's reference-order walk uses none)
-    const size_t smem = accel ? (size_t)view.stack2 * 256 * sizeof(uint32_t) : 0;
+    const size_t smem = accel ? walk_stack_bytes(view.stack2, 256) : 0;
     // photon pass: stage the accel's hot tables into LDS when at least two 256-thread blocks still fit on a CU
     const size_t hot2 = (size_t)(view.stage2_end - view.stage2_begin);
     const size_t smem_photon = hot2 + smem;
@@ -5210,8 +5230,8 @@ void debug_hit_device(const rt_scene& s, int kernel, size_t n, const double* ray
         throw RtError(RT_ERR_UNSUPPORTED, "the instance walks of kernels 5 / 6 need 1..64 instances of which at least one holds only f32-vertex triangles");
     if (view.kinds_mask & (1u << NK_MEDIUM_BEGIN))
         throw RtError(RT_ERR_UNSUPPORTED, "closest-hit queries on a scene with a ConstantMedium need the path's random stream");
-    size_t smem = (kernel == 2 || kernel == 3) ? view.stack2 * 64 * sizeof(uint32_t) : 0;
-    if (kernel == 5 || kernel == 6) smem = (size_t)std::max(std::max(view.world_depth2, view.inst_depth2) + 2u, view.stack2_inline) * 64 * sizeof(uint32_t);
+    size_t smem = (kernel == 2 || kernel == 3) ? walk_stack_bytes(view.stack2, 64) : 0;
+    if (kernel == 5 || kernel == 6) smem = walk_stack_bytes(coop_stack_rows(view), 64);
     if (kernel == 3) {  // kernel 2's LDS node table (NodeW, box32w) in isolation: the table must fit beside the stacks
         smem += ((size_t)(view.n_nodes2 + NODEW_CHUNK - 1) / NODEW_CHUNK) * 3 * NODEW_FAR;
         if (smem > 160 * 1024) throw RtError(RT_ERR_UNSUPPORTED, "the NodeW table of this scene does not fit in LDS");

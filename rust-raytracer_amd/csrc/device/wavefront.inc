@@ -221,7 +221,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel_wf(FlatView sv, CamK cam, 
     const int lane = threadIdx.x & 63;
     const uint64_t lanemask_lt = (1ull << lane) - 1ull;
     const int wave = threadIdx.x >> 6;
-    uint32_t* book = (uint32_t*)(smem + staged) + (size_t)rk.coop_stack * PT_BLOCK;
+    uint32_t* book = (uint32_t*)(smem + staged + walk_stack_bytes((uint32_t)rk.coop_stack, PT_BLOCK));
     uint32_t* rmeta = book + (size_t)wave * WF_RING_UNITS * 4;
     uint32_t* wst = book + (size_t)(PT_BLOCK / 64) * WF_RING_UNITS * 4 + (size_t)wave * WF_WST;
     int* cfg = (int*)(book + WF_BOOK_WORDS);

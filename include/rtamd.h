@@ -325,7 +325,7 @@ int rt_scene_get_background(const rt_scene* s, rt_background* out);
  *           the sum taken lights first.  Weight, termination and what a miss adds are unchanged.  The cosine half reaches every
  *           direction the BSDF scatters into, so the estimator is unbiased whatever the table's resolution.
  * width = height = 0: automatic -- a kind-3 background whose texture is an ImageTexture gets one cell per texel, both axes halved
- * (integer division) until the table is at most 4096 x 2048; every other background 256 x 128.  The table lives in device memory
+ * together (integer division, an axis never below 1) while the width exceeds 4096 or the height 2048; every other background 256 x 128.  The table lives in device memory
  * beside the scene's upload, is freed with it and is not part of the blob; the blob gains a 16-byte record {1, W, H}, so
  * rt_scene_fingerprint tells a scene with env sampling from one without and two table sizes apart.
  * RT_ERR_ARG: enabled outside 0 / 1, a negative size, only one of width / height zero, a size above 8192 x 8192, a call after commit;

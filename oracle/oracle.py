@@ -97,6 +97,21 @@ def lib():
     L.orc_vec3_op.argtypes = [C.c_int, c_double_p, c_double_p, C.c_double, c_double_p]
     L.orc_schlick.restype = C.c_double
     L.orc_schlick.argtypes = [C.c_double, C.c_double]
+    L.orc_mesh_data.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p]
+    L.orc_triangle.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]
+    L.orc_bvh_children.argtypes = [C.c_void_p, C.c_int, c_int_p]
+    L.orc_get_transform.argtypes = [C.c_void_p, C.c_int, c_double_p]
+    L.orc_set_background.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, C.c_int, C.c_double]
+    L.orc_set_env_sampling.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.orc_set_area_lights.argtypes = [C.c_void_p, C.c_int, c_int_p, c_double_p]
+    L.orc_area_tris.argtypes = [C.c_void_p, C.c_int, c_double_p, c_u32_p, c_int_p, c_u64_p]
+    L.orc_background.argtypes = [C.c_void_p, C.c_int64, c_double_p, c_double_p]
+    L.orc_env_table.argtypes = [C.c_void_p, c_int_p, c_int_p, c_u32_p, c_u64_p]
+    L.orc_env_sample.argtypes = [C.c_void_p, C.c_int64, c_double_p, c_double_p]
+    L.orc_env_pdf.argtypes = [C.c_void_p, C.c_int64, c_double_p, c_double_p]
+    L.orc_area_sample.argtypes = [C.c_void_p, C.c_int64, c_double_p, c_double_p]
+    L.orc_area_pdf.argtypes = [C.c_void_p, C.c_int64, c_double_p, c_double_p]
+    L.orc_light_counters.argtypes = [C.c_void_p, c_u64_p]
     _LIB = L
     return L
 
@@ -110,6 +125,9 @@ class OracleError(RuntimeError):
 
 
 COUNTER_NAMES = ("n_aabb", "n_sphere", "n_rect", "n_tri", "n_xform", "n_segments", "n_samples")
+# what the mixture steps and the path ends of a render did: light-half picks per kind of strategy, cosine halves, paths that ended in a
+# miss after at least one bounce, paths that ended by !(wgt > 0)
+LIGHT_COUNTER_NAMES = ("n_pick_object", "n_pick_area", "n_pick_env", "n_cosine_half", "n_miss_after_bounce", "n_wgt_end")
 # SURVEY.md s8d byte weights (reference-precision payload per test)
 B_AABB, B_SPHERE, B_RECT, B_TRI, B_XFORM = 56, 36, 44, 160, 256
 
@@ -129,6 +147,8 @@ class Scene:
         self.L = lib()
         self.h = self.L.orc_scene_new()
         self.camera = None
+        self._desc = {}  # object id -> (type name, dict) in the shape of rtamd's World.describe, for the leaves and containers of area lights
+        self._info = {"trans": {}, "mesh": {}, "pos": None}
 
     def __del__(self):
         try:
@@ -191,20 +211,29 @@ class Scene:
         return self._chk(self.L.orc_moving_sphere(self.h, _d3(center0), _d3(center1), float(time0), float(time1), float(radius), mat), "MovingSphere")
 
     def XYRectangle(self, xy0, xy1, z, mat):
-        return self._chk(self.L.orc_rect(self.h, 2, float(xy0[0]), float(xy0[1]), float(xy1[0]), float(xy1[1]), float(z), mat), "XYRectangle")
+        return self._rect(2, xy0, xy1, z, mat, "XYRectangle")
 
     def XZRectangle(self, xz0, xz1, y, mat):
-        return self._chk(self.L.orc_rect(self.h, 1, float(xz0[0]), float(xz0[1]), float(xz1[0]), float(xz1[1]), float(y), mat), "XZRectangle")
+        return self._rect(1, xz0, xz1, y, mat, "XZRectangle")
 
     def YZRectangle(self, yz0, yz1, x, mat):
-        return self._chk(self.L.orc_rect(self.h, 0, float(yz0[0]), float(yz0[1]), float(yz1[0]), float(yz1[1]), float(x), mat), "YZRectangle")
+        return self._rect(0, yz0, yz1, x, mat, "YZRectangle")
 
     def Cube(self, box_min, box_max, mat):
-        return self._chk(self.L.orc_cube(self.h, _d3(box_min), _d3(box_max), mat), "Cube")
+        o = self._chk(self.L.orc_cube(self.h, _d3(box_min), _d3(box_max), mat), "Cube")
+        mn, mx = [float(x) for x in box_min], [float(x) for x in box_max]
+        sides = [(2, mn[0], mn[1], mx[0], mx[1], mn[2]), (2, mn[0], mn[1], mx[0], mx[1], mx[2]), (1, mn[0], mn[2], mx[0], mx[2], mn[1]),
+                 (1, mn[0], mn[2], mx[0], mx[2], mx[1]), (0, mn[1], mn[2], mx[1], mx[2], mn[0]), (0, mn[1], mn[2], mx[1], mx[2], mx[0])]
+        for k, (axis, a0, b0, a1, b1, kk) in enumerate(sides):  # cube.rs:16-61: its six sides are the six objects before it
+            self._desc[o - 6 + k] = ("Rect", {"material": mat, "axis": axis, "v": [a0, b0, a1, b1, kk], "children": []})
+        self._desc[o] = ("Cube", {"material": mat, "axis": 0, "v": [], "children": list(range(o - 6, o))})
+        return o
 
     def HitableList(self, ids):
         arr = (C.c_int * len(ids))(*ids)
-        return self._chk(self.L.orc_list(self.h, len(ids), arr), "HitableList")
+        o = self._chk(self.L.orc_list(self.h, len(ids), arr), "HitableList")
+        self._desc[o] = ("HitableList", {"material": -1, "axis": 0, "v": [], "children": list(ids)})
+        return o
 
     def BVHNode_construct(self, left, right):
         return self._chk(self.L.orc_bvh_construct(self.h, left, right), "BVHNode::construct")
@@ -218,11 +247,53 @@ class Scene:
         n = np.ascontiguousarray(normals, dtype=np.float64).reshape(-1, 3)
         i = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1, 3)
         assert p.shape == n.shape
-        return self._chk(self.L.orc_mesh(self.h, p.shape[0], p.ctypes.data_as(c_double_p), n.ctypes.data_as(c_double_p),
-                                         i.shape[0], i.ctypes.data_as(c_u32_p), mat, int(seed)), "Mesh")
+        o = self._chk(self.L.orc_mesh(self.h, p.shape[0], p.ctypes.data_as(c_double_p), n.ctypes.data_as(c_double_p),
+                                      i.shape[0], i.ctypes.data_as(c_u32_p), mat, int(seed)), "Mesh")
+        self._desc[o] = ("Mesh", {"material": mat, "axis": 0, "v": [], "children": []})
+        self._info["mesh"][o] = (p.copy(), [tuple(int(x) for x in t) for t in i])
+        return o
+
+    def MeshData(self, positions, normals):
+        """shared vertex arrays for Triangle (mesh.rs:8-14): returns a mesh id, not an object id"""
+        p = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
+        n = np.ascontiguousarray(normals, dtype=np.float64).reshape(-1, 3)
+        assert p.shape == n.shape
+        md = self._chk(self.L.orc_mesh_data(self.h, p.shape[0], p.ctypes.data_as(c_double_p), n.ctypes.data_as(c_double_p)), "MeshData")
+        self._info["pos"] = p.copy()  # lowering_info() knows one vertex array for Triangle leaves: the last one registered
+        return md
+
+    def Triangle(self, mesh, a, b, c, mat):
+        o = self._chk(self.L.orc_triangle(self.h, mesh, int(a), int(b), int(c), mat), "Triangle")
+        self._desc[o] = ("Triangle", {"material": mat, "axis": 0, "v": [float(a), float(b), float(c)], "children": []})
+        return o
 
     def Transform(self, rotate_in_degree, scale, translate, obj):
-        return self._chk(self.L.orc_transform(self.h, _d3(rotate_in_degree), _d3(scale), _d3(translate), obj), "Transform")
+        o = self._chk(self.L.orc_transform(self.h, _d3(rotate_in_degree), _d3(scale), _d3(translate), obj), "Transform")
+        m = (C.c_double * 16)()
+        self._chk(self.L.orc_get_transform(self.h, o, m), "Transform")
+        self._desc[o] = ("Transform", {"material": -1, "axis": 0, "v": [], "children": [obj]})
+        self._info["trans"][o] = np.array(m[:]).reshape(4, 4)
+        return o
+
+    def _rect(self, axis, p0, p1, k, mat, what):
+        v = [float(p0[0]), float(p0[1]), float(p1[0]), float(p1[1]), float(k)]
+        o = self._chk(self.L.orc_rect(self.h, axis, v[0], v[1], v[2], v[3], v[4], mat), what)
+        self._desc[o] = ("Rect", {"material": mat, "axis": axis, "v": v, "children": []})
+        return o
+
+    def describe(self, obj):
+        """(type name, dict(material, axis, v, children)) as rtamd's World.describe reports it, for what an area light may consist of:
+        rectangles, cubes, triangles, meshes, lists, BVH nodes (children = the objects it was built over) and Transforms"""
+        if obj not in self._desc:  # a BVHNode (BVHNode::new makes inner ones of its own): {left, right} as the tree was built
+            kids = (C.c_int * 2)()
+            self._chk(self.L.orc_bvh_children(self.h, obj, kids), "describe")
+            return "BVHNode", {"material": -1, "axis": 0, "v": [], "children": [kids[0], kids[1]]}
+        return self._desc[obj]
+
+    def lowering_info(self):
+        """what tests/area_ref.lower_vertices needs beside describe(): the stored `trans` of every Transform, every Mesh's (positions,
+        index triples) and the vertex array of the Triangle leaves"""
+        return self._info
 
     def Camera(self, look_from, look_at, vup, vfov, aspect_ratio, aperture, focus_dist):
         self.camera = dict(look_from=tuple(look_from), look_at=tuple(look_at), vup=tuple(vup), vfov=vfov,
@@ -262,6 +333,69 @@ class Scene:
         sc = np.ascontiguousarray(scale if scale is not None else np.ones(len(ids)), dtype=np.float64).reshape(-1)
         self._chk(self.L.orc_set_lights(self.h, len(ids), arr, fl.ctypes.data_as(c_double_p), sc.ctypes.data_as(c_double_p)), "set_lights")
 
+    # background / env sampling / area lights (include/rtamd.h; no reference counterpart)
+    def set_background(self, kind, color0=(0.0, 0.0, 0.0), color1=(0.0, 0.0, 0.0), texture=-1, scale=1.0):
+        """rt_scene_set_background: kind 0 none, 1 color0, 2 gradient color0 (down) -> color1 (up), 3 `texture` by direction"""
+        self._chk(self.L.orc_set_background(self.h, int(kind), _d3(color0), _d3(color1), int(texture), float(scale)), "set_background")
+
+    def set_env_sampling(self, width=0, height=0, enabled=True):
+        """rt_scene_set_env_sampling: the background as strategy L + M of integrator 1 (after set_background); 0, 0 = automatic size.
+        A table whose total is 0 leaves the strategy off."""
+        self._chk(self.L.orc_set_env_sampling(self.h, 1 if enabled else 0, int(width), int(height)), "set_env_sampling")
+
+    def set_area_lights(self, lights):
+        """rt_scene_set_area_lights after the lowering: per light, its (a, b, c) world-space vertex triples in table order (what
+        tests/area_ref.lower_vertices returns); e0, e1, n, area2, the degenerate drop, q and the prefix sums are computed here."""
+        counts = (C.c_int * max(1, len(lights)))(*[len(l) for l in lights])
+        v = np.ascontiguousarray([t for l in lights for t in l], dtype=np.float64).reshape(-1)
+        self._chk(self.L.orc_set_area_lights(self.h, len(lights), counts, v.ctypes.data_as(c_double_p)), "set_area_lights")
+        self._n_area = len(lights)
+
+    def area_light_tris(self):
+        """the lowered table as a dict of arrays (a, e0, e1, n [N, 3], area2, q uint32, light int32) and the per-light totals"""
+        n = self.L.orc_area_tris(self.h, 0, None, None, None, None)
+        d = np.zeros((n, 13), dtype=np.float64)
+        q = np.zeros(n, dtype=np.uint32)
+        light = np.zeros(n, dtype=np.int32)
+        tot = np.zeros(max(1, getattr(self, "_n_area", 0)), dtype=np.uint64)
+        self.L.orc_area_tris(self.h, n, d.ctypes.data_as(c_double_p), q.ctypes.data_as(c_u32_p), light.ctypes.data_as(c_int_p), tot.ctypes.data_as(c_u64_p))
+        tab = dict(a=d[:, 0:3].copy(), e0=d[:, 3:6].copy(), e1=d[:, 6:9].copy(), n=d[:, 9:12].copy(), area2=d[:, 12].copy(), q=q, light=light)
+        return tab, [int(x) for x in tot[:getattr(self, "_n_area", 0)]]
+
+    def _batch(self, fn, what, x, cols_in, cols_out):
+        a = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, cols_in)
+        out = np.zeros((a.shape[0], cols_out), dtype=np.float64)
+        self._chk(fn(self.h, a.shape[0], a.ctypes.data_as(c_double_p), out.ctypes.data_as(c_double_p)), what)
+        return out
+
+    def background(self, dirs):
+        """B(d) for directions [n, 3] -> [n, 3]"""
+        return self._batch(self.L.orc_background, "background", dirs, 3, 3)
+
+    def env_table(self):
+        """(q uint32 [H, W], total): the layout of rtamd's World.debug_env_table"""
+        w, h, tot = C.c_int(), C.c_int(), C.c_uint64()
+        self._chk(self.L.orc_env_table(self.h, C.byref(w), C.byref(h), None, C.byref(tot)), "env_table")
+        q = np.zeros((h.value, w.value), dtype=np.uint32)
+        self._chk(self.L.orc_env_table(self.h, C.byref(w), C.byref(h), q.ctypes.data_as(c_u32_p), None), "env_table")
+        return q, int(tot.value)
+
+    def env_sample(self, xi):
+        """xi [n, 4] -> [n, 4] = direction, pdf: World.debug_env_sample"""
+        return self._batch(self.L.orc_env_sample, "env_sample", xi, 4, 4)
+
+    def env_pdf(self, dirs):
+        """directions [n, 3] -> pdf [n]: World.debug_env_pdf"""
+        return self._batch(self.L.orc_env_pdf, "env_pdf", dirs, 3, 1)[:, 0]
+
+    def area_sample(self, o_xi):
+        """[n, 7] = origin, xi0 (the light), xi1..xi3 -> [n, 4] = direction, pdf summed over all area lights: World.debug_area_sample"""
+        return self._batch(self.L.orc_area_sample, "area_sample", o_xi, 7, 4)
+
+    def area_pdf(self, rays):
+        """rays [n, 6] -> pdf [n] summed over all area lights: World.debug_area_pdf"""
+        return self._batch(self.L.orc_area_pdf, "area_pdf", rays, 6, 1)[:, 0]
+
     def render_sppm(self, width, height, spp, iterations=50, photons_per_iter=500000, alpha=0.7, k_global=100, k_caustic=50,
                     max_bounces=4096, max_depth=50, t_min=1e-3, seed=1, n_workers=None):
         """SPPMIntegrator::new + capture_image (main.rs:52-54): returns (radiance [H,W,3], stats [H,W,10], (n_global, n_caustic))."""
@@ -276,8 +410,9 @@ class Scene:
         return out, stats, (int(tot[0]), int(tot[1]))
 
     def render(self, width, height, spp, max_depth=50, t_min=1e-3, seed=1, window=None, n_jobs=64, n_workers=None, integrator=0):
-        """Camera::capture_image: returns (radiance f64 [wh,ww,3], counters dict).
-        integrator 0 = sample_ray (BSDF sampling), 1 = light/cosine mixture pdf."""
+        """Camera::capture_image: returns (radiance f64 [wh,ww,3], counters dict); light_counters() then tells what the paths did.
+        integrator 0 = sample_ray (BSDF sampling), 1 = light/cosine mixture pdf over the object lights, the area lights and the
+        environment (set_lights / set_area_lights / set_env_sampling)."""
         if window is None:
             window = (0, 0, width, height)
         x0, y0, x1, y1 = window
@@ -289,6 +424,12 @@ class Scene:
                                n_jobs, n_workers, out.ctypes.data_as(c_double_p), cnt, int(integrator))
         self._chk(rc, "render")
         return out, dict(zip(COUNTER_NAMES, [int(c) for c in cnt]))
+
+    def light_counters(self):
+        """LIGHT_COUNTER_NAMES of the last render(), as a dict"""
+        lc = (C.c_uint64 * 6)()
+        self.L.orc_light_counters(self.h, lc)
+        return dict(zip(LIGHT_COUNTER_NAMES, [int(c) for c in lc]))
 
     def hit(self, orig, direction, t_min=1e-3, t_max=float("inf"), obj=-1, key=None):
         """closest hit of `obj` (default: the root).  key = (seed, pixel, sample): the RNG stream a ConstantMedium draws from;

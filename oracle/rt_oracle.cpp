@@ -268,9 +268,14 @@ struct Counters {
     uint64_t n_aabb = 0, n_sphere = 0, n_rect = 0, n_tri = 0, n_xform = 0;
     uint64_t n_segments = 0;  // World::hit calls
     uint64_t n_samples = 0;
+    // what the mixture steps and path ends of a render did (orc_light_counters): light-half picks per strategy kind, cosine halves,
+    // paths that ended in a miss after at least one bounce, paths that ended by !(wgt > 0)
+    uint64_t n_pick_object = 0, n_pick_area = 0, n_pick_env = 0, n_cosine_half = 0, n_miss_after_bounce = 0, n_wgt_end = 0;
     void add(const Counters& o) {
         n_aabb += o.n_aabb; n_sphere += o.n_sphere; n_rect += o.n_rect; n_tri += o.n_tri;
         n_xform += o.n_xform; n_segments += o.n_segments; n_samples += o.n_samples;
+        n_pick_object += o.n_pick_object; n_pick_area += o.n_pick_area; n_pick_env += o.n_pick_env;
+        n_cosine_half += o.n_cosine_half; n_miss_after_bounce += o.n_miss_after_bounce; n_wgt_end += o.n_wgt_end;
     }
 };
 // Per-thread traversal context: RNG stream of the current sample + counters.
@@ -879,6 +884,23 @@ struct BVHNode : Hitable {
 struct MeshData {
     std::vector<Vec3> positions, normals;
 };
+// Triangle::hit's barycentric test (mesh.rs:57-102) on (a, e0 = b - a, e1 = c - a): the part before the normal.  The area-light pdf
+// (rtamd.h "area lights") runs it on the stored (a, e0, e1) of its table.
+static inline bool tri_hit_edges(Vec3 pa, Vec3 e0, Vec3 e1, const Ray& ray, double t_min, double t_max, double& t, double& b1, double& b2) {
+    Vec3 s0 = v_cross(ray.dir, e1);
+    double dd = v_dot(s0, e0);
+    if (dd == 0.0) return false;
+    double div = 1.0 / dd;
+    Vec3 d = v_sub(ray.orig, pa);
+    b1 = v_dot(d, s0) * div;
+    if (b1 < 0.0 || b1 > 1.0) return false;
+    Vec3 s1 = v_cross(d, e0);
+    b2 = v_dot(ray.dir, s1) * div;
+    if (b2 < 0.0 || b1 + b2 > 1.0) return false;
+    t = v_dot(e1, s1) * div;
+    if (t < t_min || t > t_max) return false;
+    return true;
+}
 struct Triangle : Hitable {
     size_t a, b, c;
     const MeshData* md;
@@ -895,18 +917,8 @@ struct Triangle : Hitable {
         const Vec3 &pa = md->positions[a], &pb = md->positions[b], &pc = md->positions[c];
         const Vec3 &na = md->normals[a], &nb = md->normals[b], &nc = md->normals[c];
         Vec3 e0 = v_sub(pb, pa), e1 = v_sub(pc, pa);
-        Vec3 s0 = v_cross(ray.dir, e1);
-        double dd = v_dot(s0, e0);
-        if (dd == 0.0) return false;
-        double div = 1.0 / dd;
-        Vec3 d = v_sub(ray.orig, pa);
-        double b1 = v_dot(d, s0) * div;
-        if (b1 < 0.0 || b1 > 1.0) return false;
-        Vec3 s1 = v_cross(d, e0);
-        double b2 = v_dot(ray.dir, s1) * div;
-        if (b2 < 0.0 || b1 + b2 > 1.0) return false;
-        double t = v_dot(e1, s1) * div;
-        if (t < t_min || t > t_max) return false;
+        double t, b1, b2;
+        if (!tri_hit_edges(pa, e0, e1, ray, t_min, t_max, t, b1, b2)) return false;
         double b0 = 1.0 - b1 - b2;
         Vec3 n = v_unit(v_add(v_add(v_muls(na, b0), v_muls(nb, b1)), v_muls(nc, b2)));
         out = HitRecord::make(t, n, ray, material, 0.0, 0.0, id);
@@ -1011,6 +1023,153 @@ struct Camera {
 };
 
 // ----------------------------------------------------------------------------
+// Background, env sampling and area lights: no reference counterpart (a miss ends the reference's sample_ray with what it has,
+// photon_mapper.rs:335,364).  Restated from the words of include/rtamd.h ("background", "env sampling", "area lights"), operation by
+// operation, in f64 without contraction -- not from the kernels.  tests/test_oracle_lights.py holds every piece against the numpy
+// restatements (tests/env_ref.py, tests/area_ref.py) bit for bit.
+// ----------------------------------------------------------------------------
+struct Background {
+    int kind = 0;  // 0 none, 1 constant, 2 vertical gradient, 3 texture by direction
+    const Texture* tex = nullptr;
+    Vec3 c0, c1;
+    double scale = 1.;
+};
+// B(d): u = unit(d) (sqrt(sqlen) followed by a division), then the kind's formula, then scale * c per channel
+static Vec3 background_radiance(const Background& bg, Vec3 d) {
+    const Vec3 u = v_unit(d);
+    Vec3 c;
+    if (bg.kind == 1) {
+        c = bg.c0;
+    } else if (bg.kind == 2) {
+        const double t = 0.5 * (u.y + 1.0);
+        const double s = 1.0 - t;
+        c = Vec3(s * bg.c0.x + t * bg.c1.x, s * bg.c0.y + t * bg.c1.y, s * bg.c0.z + t * bg.c1.z);
+    } else {
+        HitRecord rec;
+        rec.p = u;
+        Sphere::get_uv(u, rec.u, rec.v);
+        c = bg.tex->get_color(rec);
+    }
+    return Vec3(bg.scale * c.x, bg.scale * c.y, bg.scale * c.z);
+}
+
+struct EnvTable {
+    int W = 0, H = 0;
+    std::vector<uint32_t> q;       // [H][W]
+    std::vector<uint64_t> rowcum;  // inclusive prefix sums of the row totals
+    std::vector<uint64_t> cum;     // per row, inclusive prefix sums of q
+    uint64_t total = 0;
+};
+// d of (u, v), the inverse of Sphere::get_uv: theta = PI v, phi = (2 PI) u, cos x = det_sin(x + PI / 2)
+static Vec3 env_dir(double u, double v, double& st) {
+    const double theta = PI * v, phi = (2.0 * PI) * u;
+    st = det_sin(theta);
+    const double ct = det_sin(theta + PI / 2.0);
+    const double cp = det_sin(phi + PI / 2.0), sp = det_sin(phi);
+    return Vec3(-(cp * st), -ct, sp * st);
+}
+static void env_build(const Background& bg, int W, int H, EnvTable& e) {
+    e = EnvTable();
+    e.W = W;
+    e.H = H;
+    std::vector<double> w((size_t)W * H);
+    double w_max = 0.;
+    for (int j = 0; j < H; j++)
+        for (int i = 0; i < W; i++) {
+            double st;
+            const Vec3 d = env_dir(((double)i + 0.5) / (double)W, ((double)j + 0.5) / (double)H, st);
+            const Vec3 c = background_radiance(bg, d);
+            const double wij = ((0.2126 * c.x + 0.7152 * c.y) + 0.0722 * c.z) * st;
+            w[(size_t)j * W + i] = wij;
+            if (wij > w_max) w_max = wij;
+        }
+    e.q.assign((size_t)W * H, 0u);
+    e.rowcum.assign((size_t)H, 0ull);
+    e.cum.assign((size_t)W * H, 0ull);
+    uint64_t run = 0;
+    for (int j = 0; j < H; j++) {
+        uint64_t row = 0;
+        for (int i = 0; i < W; i++) {
+            const double wij = w[(size_t)j * W + i];
+            uint32_t q = 0u;
+            if (wij > 0.) q = (uint32_t)std::fmax(1.0, std::floor((wij / w_max) * 4294967295.0));
+            e.q[(size_t)j * W + i] = q;
+            row += q;
+            e.cum[(size_t)j * W + i] = row;
+        }
+        run += row;
+        e.rowcum[(size_t)j] = run;
+    }
+    e.total = run;
+}
+// the first index of the inclusive prefix sums p[0..n) that exceeds min(last - 1, (uint64)(xi * (double)last)), last = p[n - 1]
+static size_t prefix_pick(const uint64_t* p, size_t n, double xi) {
+    const uint64_t last = p[n - 1];
+    uint64_t t = (uint64_t)(xi * (double)last);
+    if (t > last - 1) t = last - 1;
+    return (size_t)(std::upper_bound(p, p + n, t) - p);
+}
+static Vec3 env_sample(const EnvTable& e, double x1, double x2, double x3, double x4) {
+    const size_t j = prefix_pick(e.rowcum.data(), (size_t)e.H, x1);
+    const size_t i = prefix_pick(&e.cum[j * (size_t)e.W], (size_t)e.W, x2);
+    double st;
+    return env_dir(((double)i + x3) / (double)e.W, ((double)j + x4) / (double)e.H, st);
+}
+static double env_pdf(const EnvTable& e, Vec3 d) {
+    const Vec3 n = v_unit(d);
+    const double s2 = 1.0 - n.y * n.y;
+    if (!(s2 > 0.)) return 0.;  // (a NaN direction too)
+    double u, v;
+    Sphere::get_uv(n, u, v);
+    int i = (int)std::floor((double)e.W * u), j = (int)std::floor((double)e.H * v);
+    if (i > e.W - 1) i = e.W - 1;
+    if (j > e.H - 1) j = e.H - 1;
+    if (i < 0) i = 0;  // u, v lie in [0, 1]
+    if (j < 0) j = 0;
+    const uint32_t q = e.q[(size_t)j * e.W + i];
+    return ((((double)q / (double)e.total) * (double)e.W) * (double)e.H) / (((2.0 * PI) * PI) * std::sqrt(s2));
+}
+
+struct AreaTri {
+    Vec3 a, e0, e1, n;
+    double area2;
+    uint32_t q;
+    uint64_t cum;  // inclusive prefix sum of q within the light
+    int light;
+};
+struct AreaLight {
+    size_t first, count;
+    uint64_t total;
+};
+static Vec3 area_sample(const std::vector<AreaTri>& tris, const AreaLight& l, Vec3 o, double x1, double x2, double x3) {
+    uint64_t t = (uint64_t)(x1 * (double)l.total);
+    if (t > l.total - 1) t = l.total - 1;
+    size_t k = l.first;
+    while (!(tris[k].cum > t)) k++;  // the first triangle whose inclusive prefix sum exceeds t (the last one's is total > t)
+    double u = x2, v = x3;
+    if (u + v > 1.0) {
+        u = 1.0 - u;
+        v = 1.0 - v;
+    }
+    const AreaTri& T = tris[k];
+    const Vec3 p = v_add(T.a, v_add(v_muls(T.e0, u), v_muls(T.e1, v)));
+    return v_sub(p, o);
+}
+static double area_pdf(const std::vector<AreaTri>& tris, const AreaLight& l, Vec3 o, Vec3 d) {
+    double sum = 0.0;
+    for (size_t k = l.first; k < l.first + l.count; k++) {
+        const AreaTri& T = tris[k];
+        double t, b1, b2;
+        if (!tri_hit_edges(T.a, T.e0, T.e1, Ray{o, d}, 0.001, INF, t, b1, b2)) continue;
+        const double dist2 = (t * t) * v_sqlen(d);
+        const double cosine = std::fabs(v_dot(d, T.n) / (std::sqrt(v_sqlen(d)) * T.area2));
+        if (!(cosine > 0.)) continue;
+        sum = sum + (((double)T.q / (double)l.total) * dist2) / (cosine * (0.5 * T.area2));
+    }
+    return sum;
+}
+
+// ----------------------------------------------------------------------------
 // World + Integrator::sample_ray
 //   world.rs:27-29 ; integrator/photon_mapper.rs:327-365 with divergence D2.
 // ----------------------------------------------------------------------------
@@ -1019,12 +1178,21 @@ struct Scene {
     std::vector<std::unique_ptr<Material>> materials;
     std::vector<std::unique_ptr<Hitable>> objects;
     const Hitable* root = nullptr;
+    std::vector<std::unique_ptr<MeshData>> mesh_data;  // shared vertex arrays of stand-alone Triangles (mesh.rs:8-14)
     std::vector<const Hitable*> lights;  // World::new's `lights` (world.rs:18): Sphere / XZ Rect hitables
     std::vector<Vec3> light_flux;        // XZRectLight / SphereDiffuseLight `flux` (light.rs:69-72,129-132)
     std::vector<double> light_scale;     // ... and `scale` (photon power = flux * scale)
     Camera cam;
     bool cam_set = false;
     std::string err;
+    Background bg;                  // rtamd.h "background"
+    bool env_on = false;            // rtamd.h "env sampling": asked for; the strategy exists where env.total != 0
+    int env_w = 0, env_h = 0;       // as set (0, 0 = automatic)
+    EnvTable env;
+    std::vector<AreaLight> area_lights;  // rtamd.h "area lights"
+    std::vector<AreaTri> area_tris;
+    Counters last;                  // the counters of the last orc_render
+    bool env_strategy() const { return env_on && env.total != 0; }
 };
 
 static Vec3 sample_ray(const Scene& sc, Ray ray, int max_depth, double t_min, Ctx& cx) {
@@ -1032,11 +1200,16 @@ static Vec3 sample_ray(const Scene& sc, Ray ray, int max_depth, double t_min, Ct
     Vec3 radiance(0, 0, 0);
     Ray curr = ray;
     int depth = max_depth;
+    int bounce = 0;  // scatters so far
     HitRecord rec;
     for (;;) {
         cx.cnt.n_segments++;
-        if (!sc.root->hit(curr, t_min, INF, rec, cx)) break;  // miss => black background
-        if (depth <= 0) break;                                // Q12: test after the hit
+        if (!sc.root->hit(curr, t_min, INF, rec, cx)) {  // miss => the background (kind 0: black), then the path ends
+            if (sc.bg.kind != 0) radiance = v_add(radiance, v_elemul(throughput, background_radiance(sc.bg, curr.dir)));
+            if (bounce > 0) cx.cnt.n_miss_after_bounce++;
+            break;
+        }
+        if (depth <= 0) break;  // Q12: test after the hit; no background for a path that ends on a surface
         depth -= 1;
         radiance = v_add(radiance, v_elemul(throughput, rec.mat->emitted(rec)));  // Le, no face test
         ScatterResult sr = rec.mat->scatter(curr, rec, cx);
@@ -1046,6 +1219,7 @@ static Vec3 sample_ray(const Scene& sc, Ray ray, int max_depth, double t_min, Ct
             const double time = curr.time;  // D9: scattered = ray(rec.p, direction, r_in.time())
             curr = sr.ray;
             curr.time = time;
+            bounce++;
         } else {
             break;  // Absorb
         }
@@ -1113,16 +1287,27 @@ static Vec3 light_random(const Hitable* l, Vec3 o, Rng& rng) {
     return v_add(v_add(v_muls(uu, x), v_muls(vv, y)), v_muls(w, z));
 }
 
+// n = L + M + E strategies in the light half (rtamd.h "area lights", mixture): [0, L) the object lights, [L, L + M) the area lights,
+// L + M the environment (E = 1 where the scene samples its background and the table's total is not 0).  The draws of a Diffuse
+// interaction, in order: scatter()'s own, the coin, and in the light half the strategy index and the strategy's draws (object light:
+// light_random's; area light: three gen_f64; environment: four gen_f64).  The pdf sums the n strategies in index order and divides by n.
 static Vec3 sample_ray_mixture(const Scene& sc, Ray ray, int max_depth, double t_min, Ctx& cx) {
     Vec3 throughput(1, 1, 1);
     Vec3 radiance(0, 0, 0);
     Ray curr = ray;
     int depth = max_depth;
+    int bounce = 0;
     HitRecord rec;
-    const size_t n_lights = sc.lights.size();
+    const size_t n_lights = sc.lights.size(), n_area = sc.area_lights.size();
+    const bool env = sc.env_strategy();
+    const size_t n = n_lights + n_area + (env ? 1 : 0);
     for (;;) {
         cx.cnt.n_segments++;
-        if (!sc.root->hit(curr, t_min, INF, rec, cx)) break;
+        if (!sc.root->hit(curr, t_min, INF, rec, cx)) {
+            if (sc.bg.kind != 0) radiance = v_add(radiance, v_elemul(throughput, background_radiance(sc.bg, curr.dir)));
+            if (bounce > 0) cx.cnt.n_miss_after_bounce++;
+            break;
+        }
         if (depth <= 0) break;
         depth -= 1;
         radiance = v_add(radiance, v_elemul(throughput, rec.mat->emitted(rec)));
@@ -1131,17 +1316,40 @@ static Vec3 sample_ray_mixture(const Scene& sc, Ray ray, int max_depth, double t
         if (sr.kind == Diffuse) {
             Vec3 dir = sr.ray.dir;  // the cosine-distributed sample the reference's scatter drew
             if (cx.rng.gen_f64() < 0.5) {
-                size_t li = (size_t)(cx.rng.gen_f64() * (double)n_lights);
-                if (li >= n_lights) li = n_lights - 1;
-                dir = light_random(sc.lights[li], rec.p, cx.rng);
+                size_t li = (size_t)(uint32_t)(cx.rng.gen_f64() * (double)n);
+                if (li > n - 1) li = n - 1;
+                if (li < n_lights) {
+                    cx.cnt.n_pick_object++;
+                    dir = light_random(sc.lights[li], rec.p, cx.rng);
+                } else if (li < n_lights + n_area) {
+                    cx.cnt.n_pick_area++;
+                    const double x1 = cx.rng.gen_f64();
+                    const double x2 = cx.rng.gen_f64();
+                    const double x3 = cx.rng.gen_f64();
+                    dir = area_sample(sc.area_tris, sc.area_lights[li - n_lights], rec.p, x1, x2, x3);
+                } else {
+                    cx.cnt.n_pick_env++;
+                    const double x1 = cx.rng.gen_f64();
+                    const double x2 = cx.rng.gen_f64();
+                    const double x3 = cx.rng.gen_f64();
+                    const double x4 = cx.rng.gen_f64();
+                    dir = env_sample(sc.env, x1, x2, x3, x4);
+                }
+            } else {
+                cx.cnt.n_cosine_half++;
             }
             double cosine = v_dot(rec.normal, v_unit(dir));
             double scattering_pdf = (cosine < 0.) ? 0. : cosine / PI;
             double lp = 0.;
             for (size_t i = 0; i < n_lights; i++) lp = lp + light_pdf_value(sc.lights[i], rec.p, dir, cx);
-            double pdf_val = 0.5 * (lp / (double)n_lights) + 0.5 * scattering_pdf;
+            for (size_t i = 0; i < n_area; i++) lp = lp + area_pdf(sc.area_tris, sc.area_lights[i], rec.p, dir);
+            if (env) lp = lp + env_pdf(sc.env, dir);
+            double pdf_val = 0.5 * (lp / (double)n) + 0.5 * scattering_pdf;
             double wgt = scattering_pdf / pdf_val;
-            if (!(wgt > 0.)) break;  // direction below the surface (or a NaN): the path carries nothing further
+            if (!(wgt > 0.)) {  // direction below the surface (or a NaN): the path carries nothing further
+                cx.cnt.n_wgt_end++;
+                break;
+            }
             throughput = v_muls(v_elemul(throughput, sr.att), wgt);
             curr = Ray{rec.p, dir, curr.time};
         } else {
@@ -1150,6 +1358,7 @@ static Vec3 sample_ray_mixture(const Scene& sc, Ray ray, int max_depth, double t
             curr = sr.ray;
             curr.time = time;
         }
+        bounce++;
     }
     return radiance;
 }
@@ -1483,7 +1692,7 @@ struct RenderArgs {
 // (sum / spp) f64 RGB, row-major, y down, window-local indexing.
 static int render(const Scene& sc, const RenderArgs& a, int n_jobs, int n_workers, double* out_rgb, Counters* total) {
     if (!sc.root || !sc.cam_set) return -1;
-    if (a.integrator == 1 && sc.lights.empty()) return -1;
+    if (a.integrator == 1 && sc.lights.size() + sc.area_lights.size() + (sc.env_strategy() ? 1 : 0) == 0) return -1;  // nothing to sample
     if (a.integrator == 2 && !a.sppm) return -1;
     const int wh = a.y1 - a.y0, ww = a.x1 - a.x0;
     if (n_jobs < 1) n_jobs = 1;
@@ -1821,6 +2030,48 @@ int orc_mesh(void* s, int n_vert, const double* pos, const double* nrm, int n_tr
     }
     return push_obj(sc, std::move(me));
 }
+// Triangle::new on shared vertex arrays (mesh.rs:8-53): orc_mesh_data registers the arrays (returns a mesh id), orc_triangle one triangle
+int orc_mesh_data(void* s, int n_vert, const double* pos, const double* nrm) {
+    Scene& sc = *(Scene*)s;
+    if (n_vert <= 0 || !pos || !nrm) return ORC_ERR_ARG;
+    auto md = std::make_unique<MeshData>();
+    for (int i = 0; i < n_vert; i++) {
+        md->positions.emplace_back(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]);
+        md->normals.emplace_back(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]);
+    }
+    sc.mesh_data.push_back(std::move(md));
+    return (int)sc.mesh_data.size() - 1;
+}
+int orc_triangle(void* s, int mesh, uint32_t a, uint32_t b, uint32_t c, int m) {
+    Scene& sc = *(Scene*)s;
+    if (mesh < 0 || mesh >= (int)sc.mesh_data.size() || !mat(sc, m)) return ORC_ERR_ARG;
+    const MeshData* md = sc.mesh_data[(size_t)mesh].get();
+    if (a >= md->positions.size() || b >= md->positions.size() || c >= md->positions.size()) return ORC_ERR_ARG;
+    auto t = std::make_unique<Triangle>();
+    t->a = a; t->b = b; t->c = c;
+    t->md = md;
+    t->material = mat(sc, m);
+    t->init_box();
+    return push_obj(sc, std::move(t));
+}
+// {left, right} of a BVHNode (bvh.rs:47-58), as BVHNode::new really built it
+int orc_bvh_children(void* s, int o, int* out2) {
+    Scene& sc = *(Scene*)s;
+    const BVHNode* n = dynamic_cast<const BVHNode*>(obj(sc, o));
+    if (!n) return ORC_ERR_ARG;
+    out2[0] = n->left->id;
+    out2[1] = n->right->id;
+    return ORC_OK;
+}
+// the stored `trans` of a Transform, row-major 4x4
+int orc_get_transform(void* s, int o, double* out16) {
+    Scene& sc = *(Scene*)s;
+    const Transform* t = dynamic_cast<const Transform*>(obj(sc, o));
+    if (!t) return ORC_ERR_ARG;
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) out16[4 * i + j] = t->trans.m[i][j];
+    return ORC_OK;
+}
 // Transform::new -- transform.rs:17-148 : M = T * S * Rx * Ry * Rz
 int orc_transform(void* s, const double* rot_deg, const double* scale, const double* translate, int o) {
     Scene& sc = *(Scene*)s;
@@ -1903,6 +2154,201 @@ int orc_set_lights(void* s, int n, const int* ids, const double* flux3, const do
     sc.lights = v;
     return ORC_OK;
 }
+// ---- background / env sampling / area lights (rtamd.h) ----
+static int env_rebuild(Scene& sc) {  // the table follows the background and the size, whichever was set last
+    sc.env = EnvTable();
+    if (!sc.env_on || sc.bg.kind == 0) return ORC_OK;
+    int W = sc.env_w, H = sc.env_h;
+    if (W == 0) {  // automatic: an image map gets one cell per texel, both axes halved (never below 1) until at most 4096 x 2048; else 256 x 128
+        W = 256;
+        H = 128;
+        if (const ImageTexture* im = (sc.bg.kind == 3) ? dynamic_cast<const ImageTexture*>(sc.bg.tex) : nullptr) {
+            W = im->w;
+            H = im->h;
+            while (W > 4096 || H > 2048) {
+                W = std::max(1, W / 2);
+                H = std::max(1, H / 2);
+            }
+        }
+    }
+    try {
+        env_build(sc.bg, W, H, sc.env);
+    } catch (const UnitZero&) {
+        return ORC_ERR_UNIT_ZERO;
+    }
+    return ORC_OK;
+}
+// rt_scene_set_background: kind 0..3; color0 / color1 / scale finite and >= 0; texture: one of this scene's for kind 3
+int orc_set_background(void* s, int kind, const double* color0, const double* color1, int texture, double scale) {
+    Scene& sc = *(Scene*)s;
+    if (kind < 0 || kind > 3 || !color0 || !color1) return ORC_ERR_ARG;
+    if (!(scale >= 0.) || !std::isfinite(scale)) return ORC_ERR_ARG;
+    for (int i = 0; i < 3; i++)
+        if (!(color0[i] >= 0.) || !std::isfinite(color0[i]) || !(color1[i] >= 0.) || !std::isfinite(color1[i])) return ORC_ERR_ARG;
+    if (kind == 3 && !tex(sc, texture)) return ORC_ERR_ARG;
+    sc.bg.kind = kind;
+    sc.bg.tex = kind == 3 ? tex(sc, texture) : nullptr;
+    sc.bg.c0 = Vec3(color0[0], color0[1], color0[2]);
+    sc.bg.c1 = Vec3(color1[0], color1[1], color1[2]);
+    sc.bg.scale = scale;
+    return env_rebuild(sc);
+}
+// rt_scene_set_env_sampling: needs a background of kind != 0 (the product refuses that at commit)
+int orc_set_env_sampling(void* s, int enabled, int width, int height) {
+    Scene& sc = *(Scene*)s;
+    if (enabled < 0 || enabled > 1 || width < 0 || height < 0 || (width == 0) != (height == 0) || width > 8192 || height > 8192) return ORC_ERR_ARG;
+    if (enabled && sc.bg.kind == 0) return ORC_ERR_ARG;
+    sc.env_on = enabled != 0;
+    sc.env_w = width;
+    sc.env_h = height;
+    return env_rebuild(sc);
+}
+// rt_scene_set_area_lights after the lowering: light l has n_tris[l] triangles, verts = 9 doubles (a, b, c) per triangle, in table order
+int orc_set_area_lights(void* s, int n_lights, const int* n_tris, const double* verts) {
+    Scene& sc = *(Scene*)s;
+    std::vector<AreaLight> lights;
+    std::vector<AreaTri> tris;
+    const double* v = verts;
+    for (int l = 0; l < n_lights; l++) {
+        AreaLight L{tris.size(), 0, 0};
+        double area2_max = 0.;
+        for (int k = 0; k < n_tris[l]; k++, v += 9) {
+            AreaTri T;
+            const Vec3 a(v[0], v[1], v[2]), b(v[3], v[4], v[5]), c(v[6], v[7], v[8]);
+            T.a = a;
+            T.e0 = v_sub(b, a);
+            T.e1 = v_sub(c, a);
+            T.n = v_cross(T.e0, T.e1);
+            T.area2 = std::sqrt(v_sqlen(T.n));
+            T.q = 0;
+            T.cum = 0;
+            T.light = l;
+            if (T.area2 == 0. || !std::isfinite(T.area2)) continue;  // degenerate: dropped
+            if (T.area2 > area2_max) area2_max = T.area2;
+            tris.push_back(T);
+        }
+        L.count = tris.size() - L.first;
+        if (L.count == 0) return ORC_ERR_ARG;  // no triangle of non-zero area
+        uint64_t run = 0;
+        for (size_t k = L.first; k < L.first + L.count; k++) {
+            tris[k].q = (uint32_t)std::fmax(1.0, std::floor(tris[k].area2 / area2_max * 4294967295.0));
+            run += tris[k].q;
+            tris[k].cum = run;
+        }
+        L.total = run;
+        lights.push_back(L);
+    }
+    if (tris.size() > 1024) return ORC_ERR_ARG;
+    sc.area_lights = lights;
+    sc.area_tris = tris;
+    return ORC_OK;
+}
+// the table: returns N; writes min(capacity, N) rows of {a, e0, e1, n, area2} (13 doubles), q, light, and the n_lights totals
+int orc_area_tris(void* s, int capacity, double* out13, uint32_t* q, int* light, uint64_t* totals) {
+    Scene& sc = *(Scene*)s;
+    for (size_t k = 0; k < sc.area_tris.size() && (int)k < capacity; k++) {
+        const AreaTri& T = sc.area_tris[k];
+        const Vec3 f[4] = {T.a, T.e0, T.e1, T.n};
+        for (int i = 0; i < 4; i++) {
+            out13[13 * k + 3 * i] = f[i].x; out13[13 * k + 3 * i + 1] = f[i].y; out13[13 * k + 3 * i + 2] = f[i].z;
+        }
+        out13[13 * k + 12] = T.area2;
+        q[k] = T.q;
+        light[k] = T.light;
+    }
+    if (totals)
+        for (size_t l = 0; l < sc.area_lights.size(); l++) totals[l] = sc.area_lights[l].total;
+    return (int)sc.area_tris.size();
+}
+// B(d) of n directions
+int orc_background(void* s, int64_t n, const double* dirs, double* out) {
+    Scene& sc = *(Scene*)s;
+    if (sc.bg.kind == 0) return ORC_ERR_ARG;
+    try {
+        for (int64_t k = 0; k < n; k++) {
+            const Vec3 c = background_radiance(sc.bg, Vec3(dirs[3 * k], dirs[3 * k + 1], dirs[3 * k + 2]));
+            out[3 * k] = c.x; out[3 * k + 1] = c.y; out[3 * k + 2] = c.z;
+        }
+    } catch (const UnitZero&) {
+        return ORC_ERR_UNIT_ZERO;
+    }
+    return ORC_OK;
+}
+// the layouts of rt_debug_env_table_device / rt_debug_env_sample_device / rt_debug_env_pdf_device; a table whose total is 0 answers zeros
+int orc_env_table(void* s, int* w, int* h, uint32_t* q, uint64_t* total) {
+    Scene& sc = *(Scene*)s;
+    if (!sc.env_on) return ORC_ERR_ARG;
+    *w = sc.env.W;
+    *h = sc.env.H;
+    if (total) *total = sc.env.total;
+    if (q) std::memcpy(q, sc.env.q.data(), sc.env.q.size() * sizeof(uint32_t));
+    return ORC_OK;
+}
+int orc_env_sample(void* s, int64_t n, const double* xi4, double* out4) {
+    Scene& sc = *(Scene*)s;
+    if (!sc.env_on) return ORC_ERR_ARG;
+    try {
+        for (int64_t k = 0; k < n; k++) {
+            Vec3 d;
+            double p = 0.;
+            if (sc.env.total != 0) {
+                d = env_sample(sc.env, xi4[4 * k], xi4[4 * k + 1], xi4[4 * k + 2], xi4[4 * k + 3]);
+                p = env_pdf(sc.env, d);
+            }
+            out4[4 * k] = d.x; out4[4 * k + 1] = d.y; out4[4 * k + 2] = d.z; out4[4 * k + 3] = p;
+        }
+    } catch (const UnitZero&) {
+        return ORC_ERR_UNIT_ZERO;
+    }
+    return ORC_OK;
+}
+int orc_env_pdf(void* s, int64_t n, const double* dirs, double* out) {
+    Scene& sc = *(Scene*)s;
+    if (!sc.env_on) return ORC_ERR_ARG;
+    try {
+        for (int64_t k = 0; k < n; k++) out[k] = sc.env.total != 0 ? env_pdf(sc.env, Vec3(dirs[3 * k], dirs[3 * k + 1], dirs[3 * k + 2])) : 0.;
+    } catch (const UnitZero&) {
+        return ORC_ERR_UNIT_ZERO;
+    }
+    return ORC_OK;
+}
+// the layouts of rt_debug_area_sample_device (in = n x {o, xi0..xi3}, xi0 picks the light; out = n x {dir, the pdf summed over all area
+// lights}) and rt_debug_area_pdf_device (in = n x {o, d})
+static double area_pdf_all(const Scene& sc, Vec3 o, Vec3 d) {
+    double p = 0.;
+    for (size_t i = 0; i < sc.area_lights.size(); i++) p = p + area_pdf(sc.area_tris, sc.area_lights[i], o, d);
+    return p;
+}
+int orc_area_sample(void* s, int64_t n, const double* in7, double* out4) {
+    Scene& sc = *(Scene*)s;
+    const size_t M = sc.area_lights.size();
+    if (M == 0) return ORC_ERR_ARG;
+    for (int64_t k = 0; k < n; k++) {
+        const double* x = in7 + 7 * k;
+        const Vec3 o(x[0], x[1], x[2]);
+        size_t li = (size_t)(uint32_t)(x[3] * (double)M);
+        if (li > M - 1) li = M - 1;
+        const Vec3 d = area_sample(sc.area_tris, sc.area_lights[li], o, x[4], x[5], x[6]);
+        out4[4 * k] = d.x; out4[4 * k + 1] = d.y; out4[4 * k + 2] = d.z; out4[4 * k + 3] = area_pdf_all(sc, o, d);
+    }
+    return ORC_OK;
+}
+int orc_area_pdf(void* s, int64_t n, const double* rays6, double* out) {
+    Scene& sc = *(Scene*)s;
+    if (sc.area_lights.empty()) return ORC_ERR_ARG;
+    for (int64_t k = 0; k < n; k++) {
+        const double* x = rays6 + 6 * k;
+        out[k] = area_pdf_all(sc, Vec3(x[0], x[1], x[2]), Vec3(x[3], x[4], x[5]));
+    }
+    return ORC_OK;
+}
+// the last orc_render's: {object picks, area picks, environment picks, cosine halves, misses at bounce >= 1, ends by !(wgt > 0)}
+int orc_light_counters(void* s, uint64_t* out6) {
+    const Counters& c = ((Scene*)s)->last;
+    out6[0] = c.n_pick_object; out6[1] = c.n_pick_area; out6[2] = c.n_pick_env;
+    out6[3] = c.n_cosine_half; out6[4] = c.n_miss_after_bounce; out6[5] = c.n_wgt_end;
+    return ORC_OK;
+}
 int orc_bounding_box(void* s, int o, double* out6) {
     Scene& sc = *(Scene*)s;
     AABB b;
@@ -1921,6 +2367,7 @@ int orc_render(void* s, int width, int height, int spp, int max_depth, double t_
     if (integrator == 2) return ORC_ERR_ARG;  // use orc_render_sppm
     Counters c;
     int rc = render(sc, a, n_jobs, n_workers, out_rgb, &c);
+    sc.last = c;
     if (counters7) {
         counters7[0] = c.n_aabb; counters7[1] = c.n_sphere; counters7[2] = c.n_rect; counters7[3] = c.n_tri;
         counters7[4] = c.n_xform; counters7[5] = c.n_segments; counters7[6] = c.n_samples;

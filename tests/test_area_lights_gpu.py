@@ -25,15 +25,12 @@ def _camera():
     return rtamd.Camera((CAM["look_from"], CAM["look_at"]), CAM["vup"], CAM["vfov"], CAM["aspect"], CAM["aperture"], CAM["focus"])
 
 
-def scene(window=True, tetra=True, area=True, bg=None, env=False, nested=False, object_light=False):
-    """The issue's scene: a floor, a diffuse ball, a glass ball, an emissive YZ window and an emissive tetrahedron under a Transform
-    (nested: under two), no object lights unless asked for.  Returns the committed World."""
-    import rtamd
-
-    class Deferred(rtamd.World):  # new() leaves the scene a builder: the background and env sampling are set before the commit
-        def commit(self):
-            return self
-    w = Deferred()
+def build_scene(B, window=True, tetra=True, nested=False, object_light=False):
+    """The scene's objects on either builder (rtamd.World or oracle.Scene): a floor, a diffuse ball, a glass ball, an emissive YZ window
+    and an emissive tetrahedron under a Transform (nested: under two), no object lights unless asked for.  Returns (items, object
+    lights, area lights)."""
+    from nested_scenes import bvh
+    w = B
     white = w.Lambertian(w.ConstantTexture((0.8, 0.8, 0.8)))
     red = w.Lambertian(w.ConstantTexture((0.8, 0.3, 0.3)))
     items = [w.XZRectangle((-20.0, -20.0), (20.0, 20.0), 0.0, white), w.Sphere((0.0, 1.0, 0.0), 1.0, red),
@@ -44,7 +41,7 @@ def scene(window=True, tetra=True, area=True, bg=None, env=False, nested=False, 
     if tetra:
         em = w.DiffuseLight(w.ConstantTexture((15.0, 15.0, 15.0)))
         md = w.MeshData(TETRA_POS, np.tile([0.0, 1.0, 0.0], (4, 1)))
-        t = w.BVHNode_new([w.Triangle(md, a, b, c, em) for a, b, c in TETRA_IDX], bvh_seed=5)
+        t = bvh(w, [w.Triangle(md, a, b, c, em) for a, b, c in TETRA_IDX], 5)
         if nested:
             t = w.Transform((0.0, 0.0, 0.0), (1.0, 1.0, 1.0), (0.0, 0.0, 0.0), t)
         lights.append(w.Transform(TETRA_XF["rot"], TETRA_XF["scale"], TETRA_XF["translate"], t))
@@ -53,6 +50,18 @@ def scene(window=True, tetra=True, area=True, bg=None, env=False, nested=False, 
     if object_light:
         olights.append(w.XZRectangle((1.0, -2.0), (2.0, -1.0), 5.0, w.DiffuseLight(w.ConstantTexture((20.0, 20.0, 20.0)))))
         items += olights
+    return items, olights, lights
+
+
+def scene(window=True, tetra=True, area=True, bg=None, env=False, nested=False, object_light=False):
+    """The issue's scene (build_scene) as a committed World."""
+    import rtamd
+
+    class Deferred(rtamd.World):  # new() leaves the scene a builder: the background and env sampling are set before the commit
+        def commit(self):
+            return self
+    w = Deferred()
+    items, olights, lights = build_scene(w, window=window, tetra=tetra, nested=nested, object_light=object_light)
     w.new(items, lights=olights, area_lights=lights if area else ())
     if bg is not None:
         w.set_background(**bg)
@@ -86,13 +95,19 @@ def _origins(rng, n):
     return np.stack([rng.uniform(-6.0, 4.0, n), rng.uniform(0.0, 7.0, n), rng.uniform(-4.0, 5.0, n)], axis=-1)
 
 
-def test_sample_equals_the_restatement(world):
-    tab = area_ref.table_of(world.area_light_tris())
-    assert len(tab["q"]) == 6 and set(tab["light"]) == {0, 1}
+def sample_inputs():
+    """origins and draws [4096, 7] for the sample diagnostic: random ones, and the clamps and the fold of u + v"""
     rng = np.random.default_rng(11)
     x = np.concatenate([_origins(rng, 4096), rng.random((4096, 4))], axis=1)
     x[:8, 3:] = [[0.0, 0.0, 0.0, 0.0], [1.0, 1.0, 1.0, 1.0], [0.5, 0.0, 0.5, 0.5], [0.5, 1.0, 0.25, 0.75], [0.999999, 0.5, 1.0, 0.0],
                  [0.0, 0.5, 0.0, 1.0], [0.49999999, 0.99999999, 0.7, 0.7], [0.5, 0.5, 0.5, 0.50000001]]  # clamps, the fold of u + v
+    return x
+
+
+def test_sample_equals_the_restatement(world):
+    tab = area_ref.table_of(world.area_light_tris())
+    assert len(tab["q"]) == 6 and set(tab["light"]) == {0, 1}
+    x = sample_inputs()
     got = world.debug_area_sample(x)
     exp = area_ref.sample(tab, x)
     assert got[:, :3].tobytes() == exp.tobytes()
@@ -104,8 +119,9 @@ def test_sample_equals_the_restatement(world):
     assert (np.abs(p[:, 0] - WINDOW["x"]) < 1e-12).mean() == pytest.approx(0.5, abs=0.05)
 
 
-def test_pdf_equals_the_restatement(world):
-    tab = area_ref.table_of(world.area_light_tris())
+def pdf_inputs(tab):
+    """rays [4096, 6] for the pdf diagnostic of the table `tab`: any length, aimed at the lights and past their rims, through the edge the
+    window's triangles share, in the window's plane, parallel to a face of the tetrahedron"""
     rng = np.random.default_rng(12)
     o = _origins(rng, 4096)
     d = rng.normal(size=(4096, 3)) * rng.uniform(0.1, 5.0, (4096, 1))                       # any length
@@ -124,7 +140,12 @@ def test_pdf_equals_the_restatement(world):
     d[96:128, 0] = 0.0
     # parallel to a face of the tetrahedron
     d[128:160] = tab["e0"][2] * rng.uniform(-2.0, 2.0, (32, 1)) + tab["e1"][2] * rng.uniform(-2.0, 2.0, (32, 1))
-    rays = np.concatenate([o, d], axis=1)
+    return np.concatenate([o, d], axis=1)
+
+
+def test_pdf_equals_the_restatement(world):
+    tab = area_ref.table_of(world.area_light_tris())
+    rays = pdf_inputs(tab)
     got = world.debug_area_pdf(rays)
     exp = area_ref.pdf(tab, rays)
     assert got.tobytes() == exp.tobytes()

@@ -8,6 +8,7 @@ import pytest
 
 import nested_scenes as ns
 from conftest import scene_path
+from env_ref import _background, _checker, _sphere_uv, _texel, _unit  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -33,56 +34,6 @@ def _commit(w, bg):
         w.set_background(**bg)
     rtamd.World.commit(w)
     return w
-
-
-# ---- B(d) restated ------------------------------------------------------------------------------------------------------------------
-def _unit(d):
-    ln = np.sqrt(d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2])
-    return np.stack([d[..., 0] / ln, d[..., 1] / ln, d[..., 2] / ln], axis=-1)
-
-
-def _sphere_uv(u):
-    import oracle
-    flat = u.reshape(-1, 3)
-    uu = np.empty(len(flat))
-    vv = np.empty(len(flat))
-    for i, (x, y, z) in enumerate(flat):
-        theta = oracle.det_acos(-y)
-        phi = oracle.det_atan2(-z, x) + PI
-        uu[i] = phi * FRAC_1_PI * 0.5
-        vv[i] = theta * FRAC_1_PI
-    return uu.reshape(u.shape[:-1]), vv.reshape(u.shape[:-1])
-
-
-def _texel(img, u, v):  # ImageTexture: nearest texel, v flipped, clamped (Q11)
-    h, w, _ = img.shape
-    u = np.minimum(np.maximum(u, 0.0), 1.0)
-    v = 1.0 - np.minimum(np.maximum(v, 0.0), 1.0)
-    x = np.minimum(np.floor(w * u).astype(np.int64), w - 1)
-    y = np.minimum(np.floor(h * v).astype(np.int64), h - 1)
-    return img[y, x].astype(np.float64) / 255.0
-
-
-def _checker(c0, c1, p):  # CheckerTexture: .0 when sin(10x) sin(10y) sin(10z) < 0
-    s = np.sin(10.0 * p[..., 0]) * np.sin(10.0 * p[..., 1]) * np.sin(10.0 * p[..., 2])
-    return np.where((s < 0.0)[..., None], np.asarray(c0, dtype=np.float64), np.asarray(c1, dtype=np.float64))
-
-
-def _background(spec, d):
-    """B(d) in the order rtamd.h pins, for directions d [..., 3]"""
-    kind, scale = spec["kind"], spec.get("scale", 1.0)
-    u = _unit(d)
-    if kind == 1:
-        c = np.broadcast_to(np.asarray(spec["color"], dtype=np.float64), u.shape)
-    elif kind == 2:
-        t = 0.5 * (u[..., 1] + 1.0)
-        c0, c1 = (np.asarray(x, dtype=np.float64) for x in spec["gradient"])
-        c = (1.0 - t)[..., None] * c0 + t[..., None] * c1
-    elif spec["tex"] == "image":
-        c = _texel(spec["image"], *_sphere_uv(u))
-    else:
-        c = _checker(spec["c0"], spec["c1"], u)
-    return scale * c
 
 
 # ---- 1. miss pixels bit for bit -----------------------------------------------------------------------------------------------------

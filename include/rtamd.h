@@ -567,6 +567,37 @@ void rt_default_adaptive_config(rt_adaptive_config* c);
 int rt_render_adaptive(const rt_scene* s, const rt_camera* cam, const rt_params* p, const rt_adaptive_config* cfg, double* out_rgb,
                        int32_t* out_tile_spp, rt_stats* stats);
 
+/* ---- pixel regions of a frame (no reference counterpart: capture_image renders whole frames) ------------------------- */
+/* A region is the pixel rectangle [x0, x1) x [y0, y1) of the p->width x p->height frame, y down.  rt_region_render traces all p->spp
+ * samples of every pixel of every region and writes each region's linear radiance -- the running sum divided by spp exactly as rt_render
+ * divides -- packed: region i is [y1 - y0][x1 - x0][3] f64, row-major, and starts behind regions 0 .. i-1; rt_region_doubles gives the
+ * total, 3 x the sum of the areas.  Every value equals the same pixel of rt_render's frame for the same scene, camera and params, bit for bit
+ * (the RNG is keyed by (seed, pixel, sample), the samples of a pixel are added in index order whatever else the launch renders).  Regions
+ * may overlap, repeat, share tiles and come in any order: each gets its own copy of its pixels.
+ *   cost      whole 8x8 tiles are traced: a call costs the tiles its regions touch (each once, however many regions touch it), in ONE launch
+ *             over the sorted, unique list of those tiles (rt_region_tiles), so the launch depends on the SET of pixels asked for, not on
+ *             how the caller cut it.  A pixel-exact lane mask is out of scope: a one-pixel region traces its tile's 64 pixels.
+ *   supports  what rt_render_accumulate_device supports: kernels 0 / 1 / 2 / 5 and integrators 0 / 1, with rt_render's kernel choice, refusals
+ *             and messages for media, the book-2 kinds, backgrounds, env sampling, area lights and nested Transforms; kernel 6 and
+ *             integrator 2 are RT_ERR_UNSUPPORTED.
+ *   errors    RT_ERR_ARG, before anything else: a null argument, params that rt_render refuses (size, spp, depth, kernel / integrator id,
+ *             shutter), p->world != 1 or p->rank != 0, n_regions outside 1..65536, a region that breaks 0 <= x0 < x1 <= width or
+ *             0 <= y0 < y1 <= height.  Then RT_ERR_UNSUPPORTED (kernel 6, integrator 2), RT_ERR_NOT_COMMITTED, RT_ERR_NO_DEVICE.
+ *   stats     seconds = wall time of the call; samples = in-image pixels of the touched tiles x spp (what was really traced); kernel_ms,
+ *             launches, kernel_used, scene_in_lds and the rest as rt_render reports them for its launch.
+ * rt_region_doubles and rt_region_tiles are host only (no device needed) and check p and the regions as above; a bad argument returns a
+ * negative rt_status.  rt_region_tiles lowers the regions to the launch's tile list -- image tiles ty * tiles_x + tx, ascending, unique --
+ * writes min(capacity, N) ids and returns N; out_tiles may be NULL when capacity is 0.
+ * rt_region_render writes HOST memory; rt_region_render_device DEVICE memory of the call's device (p->device, -1 = current), with the work
+ * queued on `hip_stream` (hipStream_t as void*, NULL = default stream), and returns after it has completed there. */
+typedef struct rt_region { int32_t x0, y0, x1, y1; } rt_region;
+int64_t rt_region_doubles(const rt_params* p, int n_regions, const rt_region* regions);
+int64_t rt_region_tiles(const rt_params* p, int n_regions, const rt_region* regions, int64_t capacity, int32_t* out_tiles);
+int rt_region_render(const rt_scene* s, const rt_camera* cam, const rt_params* p, int n_regions, const rt_region* regions,
+                     double* out_rgb, rt_stats* stats);
+int rt_region_render_device(const rt_scene* s, const rt_camera* cam, const rt_params* p, int n_regions, const rt_region* regions,
+                            double* d_out_rgb, void* hip_stream, rt_stats* stats);
+
 /* From<Vec3> for Rgb<u8> (vec3.rs:223-231): floor(clamp(sqrt(c),0,1)*255), NaN -> 0.  Host buffers. */
 int rt_tonemap_u8(const double* rgb, size_t n_channels, uint8_t* out);
 /* RgbImage::save("output/test.png") (main.rs:55): 8-bit RGB PNG */

@@ -660,6 +660,47 @@ int rt_render_adaptive(const rt_scene* s, const rt_camera* cam, const rt_params*
     });
 }
 
+// ---- pixel regions of a frame (the driver: host/frame.cpp render_regions, the crop: device/region.inc) ----
+int64_t rt_region_doubles(const rt_params* p, int n_regions, const rt_region* regions) {
+    int64_t n = 0;
+    const int rc = guard([&] {
+        check_regions(p, n_regions, regions);
+        n = 3 * region_pixels(n_regions, regions);
+        return (int)RT_OK;
+    });
+    return rc < 0 ? rc : n;
+}
+int64_t rt_region_tiles(const rt_params* p, int n_regions, const rt_region* regions, int64_t capacity, int32_t* out_tiles) {
+    int64_t n = 0;
+    const int rc = guard([&] {
+        const RenderPlan full = check_regions(p, n_regions, regions);
+        REQUIRE(capacity >= 0 && (out_tiles || capacity == 0), "out_tiles may be null only with capacity 0 (capacity must be >= 0)");
+        const std::vector<int32_t> tiles = region_tile_list(full, n_regions, regions);
+        n = (int64_t)tiles.size();
+        if (std::min(capacity, n) > 0) std::memcpy(out_tiles, tiles.data(), (size_t)std::min(capacity, n) * sizeof(int32_t));
+        return (int)RT_OK;
+    });
+    return rc < 0 ? rc : n;
+}
+int rt_region_render(const rt_scene* s, const rt_camera* cam, const rt_params* p, int n_regions, const rt_region* regions, double* out_rgb,
+                     rt_stats* stats) {
+    return guard([&] {
+        REQUIRE(s && cam && p && regions && out_rgb, "null argument");
+        check_regions(p, n_regions, regions);
+        render_regions(*s, *cam, *p, n_regions, regions, out_rgb, false, nullptr, stats);
+        return (int)RT_OK;
+    });
+}
+int rt_region_render_device(const rt_scene* s, const rt_camera* cam, const rt_params* p, int n_regions, const rt_region* regions,
+                            double* d_out_rgb, void* hip_stream, rt_stats* stats) {
+    return guard([&] {
+        REQUIRE(s && cam && p && regions && d_out_rgb, "null argument");
+        check_regions(p, n_regions, regions);
+        render_regions(*s, *cam, *p, n_regions, regions, d_out_rgb, true, hip_stream, stats);
+        return (int)RT_OK;
+    });
+}
+
 int rt_render_sppm_tiles_device(const rt_scene* s, const rt_camera* cam, const rt_params* p, const rt_sppm_config* cfg, double* d_tiles,
                                 void* hip_stream, rt_stats* stats) {
     return guard([&] {

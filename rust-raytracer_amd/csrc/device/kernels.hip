@@ -5256,3 +5256,5 @@ void debug_hit_device(const rt_scene& s, int kernel, size_t n, const double* ray
 // rt_render_aov: the first-hit guide buffers of the denoiser
 #include "aov.inc"
 #include "adaptive.inc"
+// rt_region_render: the crop behind a region call's one render_tiles launch
+#include "region.inc"

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "device/adaptive.h"
+#include "device/region.h"
 
 namespace rtamd {
 
@@ -303,6 +304,83 @@ void render_adaptive(const rt_scene& s, const rt_camera& cam, const rt_params& p
     stitch_to_host(full, compact.f64(), T, frame.f64(), out_rgb);
     if (out_tile_spp) std::memcpy(out_tile_spp, n_t.data(), (size_t)T * sizeof(int32_t));
     clock.finish(stats, sum, samples);
+}
+
+// ---- pixel regions of a frame ----
+RenderPlan check_regions(const rt_params* p, int n_regions, const rt_region* regions) {
+    REQUIRE(p && regions, "null argument");
+    const RenderPlan full = make_plan(p);
+    REQUIRE(p->world == 1 && p->rank == 0, "rt_region_* cuts regions out of a whole frame: world must be 1 and rank 0");
+    REQUIRE(full.tiles_total <= 0x7FFFFFFF, "frame too large: more than 2^31 - 1 tiles");
+    REQUIRE(n_regions >= 1 && n_regions <= 65536, "n_regions must be 1..65536");
+    for (int i = 0; i < n_regions; i++) {
+        const rt_region& r = regions[i];
+        if (!(0 <= r.x0 && r.x0 < r.x1 && r.x1 <= p->width && 0 <= r.y0 && r.y0 < r.y1 && r.y1 <= p->height))
+            throw RtError(RT_ERR_ARG, "region " + std::to_string(i) + " = (" + std::to_string(r.x0) + ", " + std::to_string(r.y0) + ", " + std::to_string(r.x1) +
+                                          ", " + std::to_string(r.y1) + ") must satisfy 0 <= x0 < x1 <= width = " + std::to_string(p->width) +
+                                          " and 0 <= y0 < y1 <= height = " + std::to_string(p->height));
+    }
+    return full;
+}
+int64_t region_pixels(int n_regions, const rt_region* regions) {
+    const int64_t limit = INT64_MAX / (3 * (int64_t)sizeof(double));  // the packed output's size in bytes stays an int64
+    int64_t px = 0;
+    for (int i = 0; i < n_regions; i++) {
+        const int64_t area = (int64_t)(regions[i].x1 - regions[i].x0) * (regions[i].y1 - regions[i].y0);
+        if (area > limit - px) throw RtError(RT_ERR_UNSUPPORTED, "regions too large: the packed output exceeds 2^63 bytes");
+        px += area;
+    }
+    return px;
+}
+std::vector<int32_t> region_tile_list(const RenderPlan& full, int n_regions, const rt_region* regions) {
+    std::vector<bool> touched((size_t)full.tiles_total, false);
+    for (int i = 0; i < n_regions; i++) {
+        const rt_region& r = regions[i];
+        for (int ty = r.y0 / TILE_H; ty <= (r.y1 - 1) / TILE_H; ty++)
+            for (int tx = r.x0 / TILE_W; tx <= (r.x1 - 1) / TILE_W; tx++) touched[(size_t)ty * full.tiles_x + tx] = true;
+    }
+    std::vector<int32_t> list;
+    for (int64_t t = 0; t < full.tiles_total; t++)
+        if (touched[(size_t)t]) list.push_back((int32_t)t);
+    return list;
+}
+void render_regions(const rt_scene& s, const rt_camera& cam, const rt_params& p, int n_regions, const rt_region* regions, double* out,
+                    bool out_on_device, void* stream, rt_stats* stats) {
+    if (p.kernel == 6 || p.integrator == 2) throw RtError(RT_ERR_UNSUPPORTED, "rt_region_render runs with kernels 0 / 1 / 2 / 5 and integrators 0 / 1");
+    require_committed(s);
+    require_device(region_crop != nullptr);
+    const CallClock clock;
+    DeviceScope dev_scope(p.device);  // (a device output and the stream must belong to it)
+    const RenderPlan full = make_plan(&p);
+    const CameraDev cd = make_camera(cam);
+    const std::vector<int32_t> tiles = region_tile_list(full, n_regions, regions);
+    const int64_t n_tiles = (int64_t)tiles.size();
+    std::vector<RegionDev> table((size_t)n_regions);
+    int64_t first = 0;
+    for (int i = 0; i < n_regions; i++) {
+        const rt_region& r = regions[i];
+        table[(size_t)i] = RegionDev{r.x0, r.y0, r.x1 - r.x0, r.y1 - r.y0, first};
+        first += (int64_t)(r.x1 - r.x0) * (r.y1 - r.y0);
+    }
+    const int64_t n_values = 3 * region_pixels(n_regions, regions);
+    uint64_t traced = 0;
+    for (int32_t t : tiles) traced += tile_pixels(full, t);
+    // the tile list, the regions, the compact accumulator [n_tiles][64][3] of the one launch and, for a host caller, the packed output
+    DevBuf list((size_t)n_tiles * sizeof(int32_t)), regs(table.size() * sizeof(RegionDev)), compact((size_t)n_tiles * TILE_PIX * 3 * sizeof(double)),
+        packed(out_on_device ? 16 : (size_t)n_values * sizeof(double));
+    dev_copy_to_device(list.p, tiles.data(), (size_t)n_tiles * sizeof(int32_t));
+    dev_copy_to_device(regs.p, table.data(), table.size() * sizeof(RegionDev));
+    RenderPlan pl = make_plan(&p, n_tiles);
+    pl.s_first = 0;
+    pl.s_last = full.spp;
+    pl.ext_accum = compact.f64();
+    pl.tile_list = list.i32();
+    rt_stats st{};
+    render_tiles(s, cd, pl, nullptr, stream, &st);
+    double* d_out = out_on_device ? out : packed.f64();
+    region_crop(compact.f64(), list.i32(), n_tiles, (const RegionDev*)regs.p, n_regions, n_values, full.tiles_x, full.spp, d_out, stream);
+    if (!out_on_device) dev_copy_to_host(out, packed.p, (size_t)n_values * sizeof(double));
+    clock.finish(stats, st, traced * (uint64_t)full.spp);
 }
 
 // ---- the frame across the GPUs of one node (camera.rs:74-126 has the fan-out and the stitch inside capture_image) ----

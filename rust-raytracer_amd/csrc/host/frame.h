@@ -1,7 +1,7 @@
 // The frame-level host driver: what a render call does around the kernels -- the plan of a launch, the tile arithmetic of a partition,
 // the device buffers of a frame and the stitch into the caller's memory, and the drivers themselves (one frame on one GPU, resumable
-// rendering with host-held state, the pass loop of tile-adaptive sampling, the fan-out over the GPUs of a node, the SPPM frame).
-// Plain C++17: the device is reached through device/device.h, device/adaptive.h and device/denoise.h only.  Everything throws RtError;
+// rendering with host-held state, the pass loop of tile-adaptive sampling, pixel regions, the fan-out over the GPUs of a node, the SPPM
+// frame).  Plain C++17: the device is reached through device/device.h, device/adaptive.h, device/region.h and device/denoise.h only.  Everything throws RtError;
 // the extern "C" boundary (abi.cpp) checks its arguments, calls in here and turns exceptions into status codes.
 #pragma once
 #include <chrono>
@@ -101,6 +101,16 @@ void finalize_host(const rt_params& p, const double* accum_state, double* out_rg
 // rt_render_adaptive: the passes over the active tiles and the stopping tests between them
 void render_adaptive(const rt_scene& s, const rt_camera& cam, const rt_params& p, const rt_adaptive_config& cfg, double* out_rgb,
                      int32_t* out_tile_spp, rt_stats* stats);
+// rt_region_*: pixel regions of a frame.  check_regions is the argument check all four entry points share (RT_ERR_ARG for
+// a null pointer, whatever make_plan refuses, a partition, n_regions outside 1..65536, a region that is empty or leaves the frame) and
+// returns the whole frame's plan; region_pixels = the pixels of the packed output (regions counted one by one); region_tile_list = the
+// image tiles any region touches, ascending and unique; render_regions = one render_tiles over that list, then the crop, into
+// out (HOST, or DEVICE memory of the call's device when out_on_device) -- its checks begin at RT_ERR_UNSUPPORTED
+RenderPlan check_regions(const rt_params* p, int n_regions, const rt_region* regions);
+int64_t region_pixels(int n_regions, const rt_region* regions);
+std::vector<int32_t> region_tile_list(const RenderPlan& full, int n_regions, const rt_region* regions);
+void render_regions(const rt_scene& s, const rt_camera& cam, const rt_params& p, int n_regions, const rt_region* regions, double* out,
+                    bool out_on_device, void* stream, rt_stats* stats);
 // rt_render_multi*, rt_render_sppm_multi (cfg: its configuration, null for the path tracer): one host thread per rank, the gather on
 // device_ids[0], the stitch
 void render_fanout(const rt_scene& s, const CameraDev& cd, const rt_sppm_config* cfg, const rt_params* p, int n_devices, const int* device_ids,

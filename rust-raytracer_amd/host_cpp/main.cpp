@@ -3,13 +3,16 @@
 // and the same "Total / RT" timing print.  Also renders the reference's scene files.
 //   rtamd_render [--scene cornell|FILE.json|FILE.yaml] [--cube data/mesh/cube.obj] [-w W] [-h H] [--spp N]
 //                [--depth D] [--seed S] [--aspect A] [--integrator 0|1] [--sppm ITERATIONS PHOTONS_PER_ITER]
-//                [--gpus N | --devices 0,1,...] [--background r,g,b | --sky] [--env-sampling] [-o out.png] [--describe] [--vec3-selftest]
+//                [--gpus N | --devices 0,1,...] [--background r,g,b | --sky] [--env-sampling] [--region x0,y0,x1,y1] [-o out.png]
+//                [--describe] [--vec3-selftest]
 // --gpus N spreads the frame over N GPUs of this node inside ONE capture_image call (rt_render_multi: tiles dealt round-robin, RCCL
 // gather; 0 = all visible); --devices names the HIP ordinal of every rank (an ordinal may repeat).
 // `rtamd_render --cube data/mesh/cube.obj --sppm 50 500000` is the reference binary: SPPM pre-pass + 256 spp, output/test.png
 // --background r,g,b gives rays that leave the scene a constant colour, --sky book 1's sky gradient (rt_scene_set_background; the
 // reference has neither: its misses are black); --env-sampling makes that background one more light of --integrator 1
 // (rt_scene_set_env_sampling, automatic table size)
+// --region x0,y0,x1,y1 renders only the pixels [x0, x1) x [y0, y1) of the W x H frame (rt_region_render: the frame's own pixels, at the
+// cost of the 8x8 tiles they touch) and writes the cropped PNG
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -54,6 +57,8 @@ int main(int argc, char** argv) {
     int run_samples = 64;
     rt_background bg{};  // kind 0: none
     bool env_sampling = false;
+    rt_region region{0, 0, 0, 0};
+    bool crop = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -81,6 +86,10 @@ int main(int argc, char** argv) {
             double c[3];
             if (std::sscanf(next(), "%lf,%lf,%lf", &c[0], &c[1], &c[2]) != 3) { std::fprintf(stderr, "--background wants r,g,b\n"); return 2; }
             bg = World::background_color(c[0], c[1], c[2]);
+        }
+        else if (a == "--region") {
+            if (std::sscanf(next(), "%d,%d,%d,%d", &region.x0, &region.y0, &region.x1, &region.y1) != 4) { std::fprintf(stderr, "--region wants x0,y0,x1,y1\n"); return 2; }
+            crop = true;
         }
         else if (a == "-o") out = next();
         else if (a == "--checkpoint") { checkpoint = next(); }
@@ -115,6 +124,18 @@ int main(int argc, char** argv) {
         }
         auto rt_start = std::chrono::steady_clock::now();
         rt_stats st{};
+        if (crop) {
+            const std::vector<double> rad = world->render_regions(cfg, {region}, 0, &st)[0];
+            RgbImage img;
+            img.width = region.x1 - region.x0;
+            img.height = region.y1 - region.y0;
+            img.data.resize(rad.size());
+            check(rt_tonemap_u8(rad.data(), rad.size(), img.data.data()));
+            img.save(out);
+            std::printf("region (%d, %d, %d, %d): %llu samples traced, kernel %.1f ms, %.3fs\n", region.x0, region.y0, region.x1, region.y1,
+                        (unsigned long long)st.samples, st.kernel_ms, std::chrono::duration<double>(std::chrono::steady_clock::now() - rt_start).count());
+            return 0;
+        }
         std::vector<rt_stats> ranks;
         RgbImage result = world->capture_image(cfg, &st, nullptr, &ranks);
         result.save(out);

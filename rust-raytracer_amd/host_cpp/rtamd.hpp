@@ -554,6 +554,28 @@ class World {
         return rad;
     }
 
+    // Pixel regions of the frame capture_image would render (rt_region_render): each region [x0, x1) x [y0, y1) as linear
+    // radiance [y1 - y0][x1 - x0][3], bit for bit the frame's pixels, at the cost of the 8x8 tiles the regions touch (one launch).
+    std::vector<std::vector<double>> render_regions(const Config& cfg, const std::vector<rt_region>& regions, int kernel = 0,
+                                                    rt_stats* stats = nullptr) const {
+        rt_params p;
+        rt_default_params(&p);
+        p.width = cfg.width; p.height = cfg.height; p.spp = cfg.sample_per_pixel; p.max_depth = cfg.max_depth;
+        p.t_min = cfg.t_min; p.seed = cfg.seed; p.integrator = cfg.integrator; p.kernel = kernel;
+        const int64_t n = rt_region_doubles(&p, (int)regions.size(), regions.data());
+        if (n < 0) check((int)n);
+        std::vector<double> packed((size_t)n);
+        check(rt_region_render(s_, &cam.c, &p, (int)regions.size(), regions.data(), packed.data(), stats));
+        std::vector<std::vector<double>> out;
+        size_t at = 0;
+        for (const rt_region& r : regions) {
+            const size_t len = (size_t)(r.x1 - r.x0) * (size_t)(r.y1 - r.y0) * 3;
+            out.emplace_back(packed.begin() + (ptrdiff_t)at, packed.begin() + (ptrdiff_t)(at + len));
+            at += len;
+        }
+        return out;
+    }
+
    private:
     rt_scene* s_ = nullptr;
 };

@@ -73,6 +73,10 @@ class rt_adaptive_config(C.Structure):
     _fields_ = [("min_spp", C.c_int32), ("reserved", C.c_int32), ("threshold", C.c_double)]
 
 
+class rt_region(C.Structure):
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32)]
+
+
 class rt_background(C.Structure):
     _fields_ = [("kind", C.c_int32), ("texture", C.c_int32), ("color0", C.c_double * 3), ("color1", C.c_double * 3), ("scale", C.c_double)]
 
@@ -194,6 +198,12 @@ _SIGS = [
     ("rt_default_adaptive_config", None, [C.POINTER(rt_adaptive_config)]),
     ("rt_render_adaptive", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_adaptive_config), _dp,
                                      C.POINTER(C.c_int32), C.POINTER(rt_stats)]),
+    ("rt_region_doubles", C.c_int64, [C.POINTER(rt_params), C.c_int, C.POINTER(rt_region)]),
+    ("rt_region_tiles", C.c_int64, [C.POINTER(rt_params), C.c_int, C.POINTER(rt_region), C.c_int64, C.POINTER(C.c_int32)]),
+    ("rt_region_render", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.c_int, C.POINTER(rt_region), _dp,
+                                   C.POINTER(rt_stats)]),
+    ("rt_region_render_device", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.c_int, C.POINTER(rt_region), C.c_void_p,
+                                          C.c_void_p, C.POINTER(rt_stats)]),
     ("rt_render_tiles_device", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.c_void_p, C.c_void_p,
                                          C.POINTER(rt_stats)]),
     ("rt_render_sppm_tiles_device", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_sppm_config), C.c_void_p,
@@ -647,6 +657,38 @@ class World:
         d["prepass_seconds"] = st.reserved[0] * 1e-6
         return out, stats, (int(tot[0]), int(tot[1])), d
 
+    def render_regions(self, camera, regions, width=800, height=800, spp=256, max_depth=50, t_min=1e-3, seed=1, rank=0, world=1, spp_chunk=0,
+                       kernel=0, device=-1, integrator=0, shutter=(0.0, 0.0)):
+        """rt_region_render: the pixel rectangles regions = [(x0, y0, x1, y1), ...] ([x0, x1) x [y0, y1), y down) of the width x height frame
+        render() would return, bit for bit, at the cost of the 8x8 tiles they touch.  Returns ([radiance f64
+        [y1 - y0, x1 - x0, 3] per region], stats dict)."""
+        p = default_params(width=width, height=height, spp=spp, max_depth=max_depth, t_min=t_min, seed=seed, rank=rank, world=world,
+                           spp_chunk=spp_chunk, kernel=kernel, device=device, integrator=integrator, time0=float(shutter[0]), time1=float(shutter[1]))
+        arr, n = _regions(regions)
+        out = np.zeros(_chk(self.L.rt_region_doubles(C.byref(p), n, arr)), dtype=np.float64)
+        st = rt_stats()
+        _chk(self.L.rt_region_render(self.h, C.byref(camera.c), C.byref(p), n, arr, out.ctypes.data_as(_dp), C.byref(st)))
+        views, at = [], 0
+        for r in arr[:n]:
+            h, w = r.y1 - r.y0, r.x1 - r.x0
+            views.append(out[at:at + h * w * 3].reshape(h, w, 3))
+            at += h * w * 3
+        return views, st.as_dict()
+
+    def render_region(self, camera, region, **kw):
+        """render_regions for one region (x0, y0, x1, y1): returns (radiance [y1 - y0, x1 - x0, 3], stats dict)"""
+        views, st = self.render_regions(camera, [region], **kw)
+        return views[0], st
+
+    def render_regions_device(self, camera, params, regions, d_out_ptr, stream_ptr=None):
+        """rt_region_render_device: the packed regions (region_doubles(params, regions) f64) into a raw device pointer (e.g. torch tensor
+        .data_ptr()), queued on stream_ptr; returns the stats dict after the work has completed on that stream."""
+        arr, n = _regions(regions)
+        st = rt_stats()
+        _chk(self.L.rt_region_render_device(self.h, C.byref(camera.c), C.byref(params), n, arr, C.c_void_p(d_out_ptr),
+                                            C.c_void_p(stream_ptr or 0), C.byref(st)))
+        return st.as_dict()
+
     def render_tiles_device(self, camera, params, d_tiles_ptr, stream_ptr=None):
         """rt_render_tiles_device: d_tiles_ptr is a raw device pointer (e.g. torch tensor .data_ptr())."""
         st = rt_stats()
@@ -823,6 +865,28 @@ def debug_schedule(tiles_owned, n_waves, s_begin, s_end, sub_spp=8, job_units=2)
     rows = [tuple(out[5 * i:5 * i + 5]) for i in range(5)]
     n = next(i for i, r in enumerate(rows) if r[3] == 0)
     return rounds, rows[:n + 1]
+
+
+def _regions(regions):
+    """[(x0, y0, x1, y1), ...] -> (rt_region array, count); an empty list still has an address, so the library answers n_regions == 0 itself"""
+    regions = [rt_region(*[int(v) for v in r]) for r in regions]
+    return (rt_region * max(1, len(regions)))(*regions), len(regions)
+
+
+def region_doubles(params, regions):
+    """rt_region_doubles: the f64 count of the packed output of World.render_regions_device"""
+    arr, n = _regions(regions)
+    return int(_chk(lib().rt_region_doubles(C.byref(params), n, arr)))
+
+
+def region_tiles(width, height, regions):
+    """rt_region_tiles: the image tiles (ty * tiles_x + tx, ascending, unique; int32 array) a region call of a width x height frame traces.
+    Host only."""
+    p = default_params(width=width, height=height)
+    arr, n = _regions(regions)
+    out = np.zeros(_chk(lib().rt_region_tiles(C.byref(p), n, arr, 0, None)), dtype=np.int32)
+    _chk(lib().rt_region_tiles(C.byref(p), n, arr, out.size, out.ctypes.data_as(C.POINTER(C.c_int32))))
+    return out
 
 
 def tiles_owned(params):

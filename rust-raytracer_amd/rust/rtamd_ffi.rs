@@ -182,6 +182,16 @@ pub struct rt_adaptive_config {
     pub threshold: c_double,
 }
 
+/// include/rtamd.h rt_region: pixels [x0, x1) x [y0, y1) of the frame, y down
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct rt_region {
+    pub x0: i32,
+    pub y0: i32,
+    pub x1: i32,
+    pub y1: i32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct rt_tuning {
@@ -317,6 +327,10 @@ extern "C" {
     pub fn rt_denoise(cfg: *const rt_denoise_config, width: i32, height: i32, rgb: *const c_double, variance: *const c_double, aov: *const c_double, out_rgb: *mut c_double, out_variance: *mut c_double) -> c_int;
     pub fn rt_denoise_device(cfg: *const rt_denoise_config, width: i32, height: i32, d_rgb: *const c_double, d_variance: *const c_double, d_aov: *const c_double, d_out_rgb: *mut c_double, d_out_variance: *mut c_double, hip_stream: *mut c_void) -> c_int;
     pub fn rt_render_sppm(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, cfg: *const rt_sppm_config, out_rgb: *mut c_double, stats_out: *mut c_double, photons_stored: *mut u64, stats: *mut rt_stats) -> c_int;
+    pub fn rt_region_doubles(p: *const rt_params, n_regions: c_int, regions: *const rt_region) -> i64;
+    pub fn rt_region_tiles(p: *const rt_params, n_regions: c_int, regions: *const rt_region, capacity: i64, out_tiles: *mut i32) -> i64;
+    pub fn rt_region_render(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, n_regions: c_int, regions: *const rt_region, out_rgb: *mut c_double, stats: *mut rt_stats) -> c_int;
+    pub fn rt_region_render_device(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, n_regions: c_int, regions: *const rt_region, d_out_rgb: *mut c_double, hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
     pub fn rt_default_adaptive_config(c: *mut rt_adaptive_config);
     pub fn rt_render_adaptive(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, cfg: *const rt_adaptive_config, out_rgb: *mut c_double, out_tile_spp: *mut i32, stats: *mut rt_stats) -> c_int;
     pub fn rt_render_tiles_device(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, d_tiles: *mut c_double, hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
@@ -660,6 +674,25 @@ impl Scene {
         let mut st = rt_stats::default();
         check(unsafe { rt_render_adaptive(self.raw, cam, p, &c, out.as_mut_ptr(), tile_spp.as_mut_ptr(), &mut st) })?;
         Ok((out, tile_spp, st))
+    }
+    /// Pixel regions of the frame `render` would return: every region's pixels, bit for bit, at the cost of the 8x8 tiles
+    /// the regions touch, in one launch.  Returns one `Vec` per region, `[y1 - y0][x1 - x0][3]` row-major, and the statistics.
+    pub fn render_regions(&self, cam: &rt_camera, p: &rt_params, regions: &[rt_region]) -> Result<(Vec<Vec<f64>>, rt_stats), RtError> {
+        let n64 = unsafe { rt_region_doubles(p, regions.len() as c_int, regions.as_ptr()) };
+        if n64 < 0 {
+            check(n64 as c_int)?;
+        }
+        let mut packed = vec![0.0f64; n64 as usize];
+        let mut st = rt_stats::default();
+        check(unsafe { rt_region_render(self.raw, cam, p, regions.len() as c_int, regions.as_ptr(), packed.as_mut_ptr(), &mut st) })?;
+        let mut out = Vec::with_capacity(regions.len());
+        let mut at = 0usize;
+        for r in regions {
+            let n = ((r.x1 - r.x0) as usize) * ((r.y1 - r.y0) as usize) * 3;
+            out.push(packed[at..at + n].to_vec());
+            at += n;
+        }
+        Ok((out, st))
     }
     pub fn finish_accumulated(p: &rt_params, state: &[f64]) -> Result<Vec<f64>, RtError> {
         let mut out = vec![0.0f64; (p.width as usize) * (p.height as usize) * 3];

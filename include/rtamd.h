@@ -617,7 +617,9 @@ int rt_debug_math_device(int op, size_t n, const double* a_host, const double* b
 /* closest hit of explicit world-space rays through device traversal `kernel` (1, 2, or 3 = kernel 2's LDS node table "NodeW" with
  * its own box test, which pt_kernel uses when the scene is LDS-resident; 5 / 6 = the walks of the instance service in one lane: the
  * world-space walk with the large instances deferred, then their object-space walks over the Node2 / item records (5: the in-lane
- * fallback of kernel 5) or over the compact NodeQ / Tri32 copies (6: what the serving waves of kernels 5 / 6 walk), with the exact-tie rule): rays n*6 (orig,dir);
+ * fallback of kernel 5) or over the compact NodeQ / Tri32 copies (6: what the serving waves of kernels 5 / 6 walk), with the exact-tie rule;
+ * 7 = 3 with the table's boxes tightened as a render tightens them, for the origin bound 2 * max(scene extent, largest |origin coordinate| of
+ * this batch); a scene with instances keeps the stored boxes, as in a render): rays n*6 (orig,dir);
  * out n*12 = {hit, t, p[3], normal[3], front_face, u, v, leaf index in the reference-order program} */
 int rt_debug_hit_device(const rt_scene* s, int kernel, size_t n, const double* rays_host, double t_min, double t_max, double* out_host);
 /* the per-tile job sequence of one launch over samples [s_begin, s_end) for a rank that owns `tiles_owned` tiles on a GPU with `n_waves`

@@ -35,6 +35,7 @@
 #include "../common/detuv.h"
 #include "../common/rng.h"
 #include "../common/schedule.h"
+#include "../common/tighten.h"
 #include "device.h"
 
 namespace rtamd {
@@ -269,6 +270,7 @@ struct RenderK {
     double time0, time1;     // D9: the camera's shutter; time1 > time0: every sample draws its time after the lens sample
     int time_slots;          // D9: 1 = the scene has moving spheres: 8 bytes of LDS per lane (behind the launch constants) hold the paths' times
     const int* tile_list;    // null, or the image tiles of this launch (rt_render_adaptive's active tiles): job tile j renders tile_list[j]
+    float box_shrink;        // kernel 2 with the scene in LDS: the NodeW rows' planes move inward by this much while staging (common/tighten.h); 0: as stored
 };
 
 // ------------------------------------------------------ intersection ------
@@ -790,6 +792,32 @@ DEV void ray32_wide_addr(Ray32& r, uint32_t n2w_lds) {
 DEV uint32_t wide_ref(uint32_t ref) {
     return (ref >> REF_TAG_SHIFT) == 0u ? (ref / NODEW_CHUNK) * (3u * NODEW_FAR) + (ref % NODEW_CHUNK) * 32u : ref;
 }
+// The workgroup expands the blob's Node2 array into the NodeW rows at `n2w` (LDS).  shrink > 0: every child box is tightened to the
+// render's own origin bound on the way (common/tighten.h; the host hands 0 wherever the stored pads must stay: scenes with instances,
+// hit_kernel's mode 3).  The caller synchronises.
+DEV void stage_nodew(const FlatView& sv, char* n2w, float shrink) {
+    for (uint32_t i = threadIdx.x; i < sv.n_nodes2; i += blockDim.x) {
+        const uint4* nd = (const uint4*)(sv.base + sv.off_n2) + (size_t)i * NODE2_F4;
+        uint4 a = nd[0], b = nd[1], c = nd[2];  // (lox0,lox1,loy0,loy1) (loz0,loz1,hix0,hix1) (hiy0,hiy1,hiz0,hiz1) (c0,c1,-,-)
+        const uint4 d = nd[3];
+        if (shrink > 0.f) {
+            float lo0[3] = {__uint_as_float(a.x), __uint_as_float(a.z), __uint_as_float(b.x)}, hi0[3] = {__uint_as_float(b.z), __uint_as_float(c.x), __uint_as_float(c.z)};
+            float lo1[3] = {__uint_as_float(a.y), __uint_as_float(a.w), __uint_as_float(b.y)}, hi1[3] = {__uint_as_float(b.w), __uint_as_float(c.y), __uint_as_float(c.w)};
+            tighten_box(lo0, hi0, shrink);
+            tighten_box(lo1, hi1, shrink);
+            a = make_uint4(__float_as_uint(lo0[0]), __float_as_uint(lo1[0]), __float_as_uint(lo0[1]), __float_as_uint(lo1[1]));
+            b = make_uint4(__float_as_uint(lo0[2]), __float_as_uint(lo1[2]), __float_as_uint(hi0[0]), __float_as_uint(hi1[0]));
+            c = make_uint4(__float_as_uint(hi0[1]), __float_as_uint(hi1[1]), __float_as_uint(hi0[2]), __float_as_uint(hi1[2]));
+        }
+        const uint32_t c0 = wide_ref(d.x), c1 = wide_ref(d.y);
+        char* w = n2w + wide_ref(i);
+        const uint4 lo0 = make_uint4(a.x, a.y, a.z, a.w), lo1 = make_uint4(b.x, b.y, c0, c1);
+        const uint4 hi0 = make_uint4(b.z, b.w, c.x, c.y), hi1 = make_uint4(c.z, c.w, c0, c1);
+        ((uint4*)w)[0] = lo0; ((uint4*)w)[1] = lo1;
+        ((uint4*)(w + NODEW_FAR))[0] = hi0; ((uint4*)(w + NODEW_FAR))[1] = hi1;
+        ((uint4*)(w + 2 * NODEW_FAR))[0] = lo0; ((uint4*)(w + 2 * NODEW_FAR))[1] = lo1;
+    }
+}
 // one child of a NodeW: near / far planes already selected
 DEV bool box32w(float nx, float ny, float nz, float fx, float fy, float fz, const Ray32& r, float& entry) {
     const float px = __builtin_fmaf(nx, r.ix, -r.cx), qx = __builtin_fmaf(fx, r.ix, -r.cx);
@@ -797,9 +825,11 @@ DEV bool box32w(float nx, float ny, float nz, float fx, float fy, float fz, cons
     const float pz = __builtin_fmaf(nz, r.iz, -r.cz), qz = __builtin_fmaf(fz, r.iz, -r.cz);
     // No widening factor W here (box32 multiplies tf by 1 + 2^-20): the pad is 12 e |o|max since round 3 (flatten.cpp), of which
     // 2.001 e |o|max cover lo' - lo as in the proof above box32, leaving a margin m >= 9.99 e |o|max between [lo', hi'] and the
-    // exact box B on every side.  For a real t >= 0 with o + t d in B, on every axis: nu <= t - m/|d| and phi >= t + m/|d|, and
+    // exact box B on every side.  |o|max is the bound the table in LDS was padded for: origin_limit2 as the blob stores it, or the
+    // render's own O_r = 2 max(ew, camera bound) when stage_nodew tightened the rows (common/tighten.h: the planes it writes are
+    // never inside B -+ 12 e O_r, and every origin of that render is within O_r).  For a real t >= 0 with o + t d in B, on every axis: nu <= t - m/|d| and phi >= t + m/|d|, and
     // t |d| = the distance travelled along the axis <= 2 |o|max (|o|max bounds origins AND item coordinates: flatten.cpp's
-    // origin_limit / oo), so nu (1 + th) <= t - m/|d| + 4.1 e t <= t and phi (1 + th') >= (t + m/|d|)(1 - 4.1 e) >= t because
+    // origin_limit / oo; a render's O_r >= ew by its max), so nu (1 + th) <= t - m/|d| + 4.1 e t <= t and phi (1 + th') >= (t + m/|d|)(1 - 4.1 e) >= t because
     // 4.1 e * 2 |o|max (1 + 4.1 e) < m.  Hence tn <= t <= tf, tn <= best <= r.best, r.tmin <= t_min <= t <= tf: the test passes.
     // (non-positive nu, clamped iv, NaN: as for box32.)
     const float tn = fmaxf(fmaxf(px, py), pz);
@@ -918,6 +948,10 @@ DEV double track_bound(const MediaTrack& K, double best) {
 // hence the same hit.  (On the LDS-resident scenes the rounds' tail is short -- 3.5 rounds against 1.5 on the headline scene -- and the
 // slicing only costs registers: measured -1.4 % there, -21 % on the Cornell box; the switch RT_SLICE_TH compiles it into the MEDIA variants
 // alone, and it is OFF in the product: no gain there either, see RT_SLICE_TH.)
+// (Round 7 measured an EARLY EXIT from the node loop of the WIDE form -- the wave leaves it once lanes at a leaf >= 7/8 of the lanes still
+// walking, the others re-enter with cur and their stack untouched; two ballots' bit counts and a scalar compare per node step -- and
+// rejected it: headline 2 564-2 566 Msamples/s against the parent's 2 877-2 879, -10.9 %, where tools/walk_model.cpp had priced the
+// saved wave-steps at +1..2 %.  DESIGN.md s5-r7, profiles/r07/README.md.  It is not in the tree.)
 struct WalkState {
     uint32_t cur;  // node / leaf to continue at; REF_DONE: no walk in progress
     uint32_t sp;   // stack offset in words (WIDE: the LDS byte address)
@@ -2265,6 +2299,10 @@ __device__ __attribute__((noinline)) UnitInfo next_unit(uint32_t* wst_, uint32_t
 #ifndef RT_SLICE_TH
 #define RT_SLICE_TH 0
 #endif
+// A/B switch, ON in the product (round 7): 0 leaves the NodeW rows of kernel 2 with the blob's pads (box_shrink = 0 in every launch)
+#ifndef RT_TIGHTEN_BOXES
+#define RT_TIGHTEN_BOXES 1
+#endif
 // INTEG & INTEG_BG: the background variants of integrator INTEG & 3 -- a value of the INTEG axis rather than a template
 // parameter of its own, so that every kernel without a background keeps its name (and its code)
 static constexpr int INTEG_BG = 4;
@@ -2296,17 +2334,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
             for (uint32_t i = threadIdx.x; i < lo_bytes / 16; i += blockDim.x) dst[i] = src[i];
         }
         char* n2w = smem + lo_bytes;
-        for (uint32_t i = threadIdx.x; i < sv.n_nodes2; i += blockDim.x) {
-            const uint4* nd = (const uint4*)(sv.base + sv.off_n2) + (size_t)i * NODE2_F4;
-            const uint4 a = nd[0], b = nd[1], c = nd[2], d = nd[3];  // (lox0,lox1,loy0,loy1) (loz0,loz1,hix0,hix1) (hiy0,hiy1,hiz0,hiz1) (c0,c1,-,-)
-            const uint32_t c0 = wide_ref(d.x), c1 = wide_ref(d.y);
-            char* w = n2w + wide_ref(i);
-            const uint4 lo0 = make_uint4(a.x, a.y, a.z, a.w), lo1 = make_uint4(b.x, b.y, c0, c1);
-            const uint4 hi0 = make_uint4(b.z, b.w, c.x, c.y), hi1 = make_uint4(c.z, c.w, c0, c1);
-            ((uint4*)w)[0] = lo0; ((uint4*)w)[1] = lo1;
-            ((uint4*)(w + NODEW_FAR))[0] = hi0; ((uint4*)(w + NODEW_FAR))[1] = hi1;
-            ((uint4*)(w + 2 * NODEW_FAR))[0] = lo0; ((uint4*)(w + 2 * NODEW_FAR))[1] = lo1;
-        }
+        stage_nodew(sv, n2w, rk.box_shrink);
         staged = lo_bytes + nodew_bytes(sv.n_nodes2);
         __syncthreads();
         A = make_acc(smem - st_begin, sv.base, sv);
@@ -3705,23 +3733,13 @@ DEV void hit_row(double* q, const Hit& h, const Rec& rec) {
     q[9] = rec.u; q[10] = rec.v;
     q[11] = (double)h.node;
 }
-__global__ void hit_kernel(FlatView sv, int accel, size_t n, const double* rays, double t_min, double t_max, double* out, int* err) {
+__global__ void hit_kernel(FlatView sv, int accel, float box_shrink, size_t n, const double* rays, double t_min, double t_max, double* out, int* err) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     Acc A = make_acc(sv.base, sv.base, sv);
     uint32_t stack_at = 0;
-    if (accel == 3) {  // the NodeW table of pt_kernel's LDS variants (box32w), expanded here as that kernel expands it; tables stay global
-        for (uint32_t k = threadIdx.x; k < sv.n_nodes2; k += blockDim.x) {
-            const uint4* nd = (const uint4*)(sv.base + sv.off_n2) + (size_t)k * NODE2_F4;
-            const uint4 a = nd[0], b = nd[1], c = nd[2], d4 = nd[3];
-            const uint32_t c0 = wide_ref(d4.x), c1 = wide_ref(d4.y);
-            char* w = smem + wide_ref(k);
-            const uint4 lo0 = make_uint4(a.x, a.y, a.z, a.w), lo1 = make_uint4(b.x, b.y, c0, c1);
-            const uint4 hi0 = make_uint4(b.z, b.w, c.x, c.y), hi1 = make_uint4(c.z, c.w, c0, c1);
-            ((uint4*)w)[0] = lo0; ((uint4*)w)[1] = lo1;
-            ((uint4*)(w + NODEW_FAR))[0] = hi0; ((uint4*)(w + NODEW_FAR))[1] = hi1;
-            ((uint4*)(w + 2 * NODEW_FAR))[0] = lo0; ((uint4*)(w + 2 * NODEW_FAR))[1] = lo1;
-        }
+    if (accel == 3) {  // the NodeW table of pt_kernel's LDS variants (box32w), expanded here as that kernel expands it (box_shrink: the host's mode 7); tables stay global
+        stage_nodew(sv, smem, box_shrink);
         __syncthreads();
         A.n2w_lds = (uint32_t)(uintptr_t)(AS_L char*)smem;
         stack_at = nodew_bytes(sv.n_nodes2);
@@ -3787,23 +3805,13 @@ __global__ void hit_kernel(FlatView sv, int accel, size_t n, const double* rays,
     hit_row(q, h, rec);
 }
 // hit_kernel's kernels 1, 2 and 3 for scenes with nested Transforms (the chain walk, GENERAL == 3)
-__global__ void hit_kernel_nest(FlatView sv, int accel, size_t n, const double* rays, double t_min, double t_max, double* out, int* err) {
+__global__ void hit_kernel_nest(FlatView sv, int accel, float box_shrink, size_t n, const double* rays, double t_min, double t_max, double* out, int* err) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     Acc A = make_acc(sv.base, sv.base, sv);
     uint32_t stack_at = 0;
     if (accel == 3) {  // the NodeW table, expanded as hit_kernel expands it
-        for (uint32_t k = threadIdx.x; k < sv.n_nodes2; k += blockDim.x) {
-            const uint4* nd = (const uint4*)(sv.base + sv.off_n2) + (size_t)k * NODE2_F4;
-            const uint4 a = nd[0], b = nd[1], c = nd[2], d4 = nd[3];
-            const uint32_t c0 = wide_ref(d4.x), c1 = wide_ref(d4.y);
-            char* w = smem + wide_ref(k);
-            const uint4 lo0 = make_uint4(a.x, a.y, a.z, a.w), lo1 = make_uint4(b.x, b.y, c0, c1);
-            const uint4 hi0 = make_uint4(b.z, b.w, c.x, c.y), hi1 = make_uint4(c.z, c.w, c0, c1);
-            ((uint4*)w)[0] = lo0; ((uint4*)w)[1] = lo1;
-            ((uint4*)(w + NODEW_FAR))[0] = hi0; ((uint4*)(w + NODEW_FAR))[1] = hi1;
-            ((uint4*)(w + 2 * NODEW_FAR))[0] = lo0; ((uint4*)(w + 2 * NODEW_FAR))[1] = lo1;
-        }
+        stage_nodew(sv, smem, box_shrink);
         __syncthreads();
         A.n2w_lds = (uint32_t)(uintptr_t)(AS_L char*)smem;
         stack_at = nodew_bytes(sv.n_nodes2);
@@ -4439,6 +4447,12 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
         if (smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     }
 
+    // The LDS node table of kernel 2 is padded for THIS render's ray origins (common/tighten.h): the lens (cam_abs, the
+    // quantity camera_ok was tested with: |lens offset| <= lens_radius on every axis) and points on the scene's items or inside its
+    // media (their extent is part of origin_limit2 / 64: build_bvhs starts ew from media_extent).  A scene with any instance keeps the
+    // stored pads: the table then holds object-space BVHs too, whose pads come from the instances' own origin bounds.  Regions, adaptive
+    // passes, resumable ranges and the ranks of rt_render_multi all launch from here, with the camera of their frame.
+    const float node_shrink = (RT_TIGHTEN_BOXES && kernel == 2 && lds) ? box_shrink(view.origin_limit2, render_origin_bound(view.origin_limit2, cam_abs), view.n_inst2 == 0u) : 0.f;
     const int64_t n_pix = plan.tiles_owned * TILE_PIX;
     // workspace: RING_UNITS unit buffers (12 KB) per resident wave -- independent of the image -- plus accumulator and tickets
     const size_t ring_bytes = (size_t)grid * (PT_BLOCK / 64) * RING_UNITS * UNIT_DOUBLES * sizeof(double);
@@ -4487,6 +4501,7 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
         rk.time1 = plan.time1;
         rk.time_slots = moving ? 1 : 0;
         rk.tile_list = plan.tile_list;
+        rk.box_shrink = node_shrink;
         rk.n_top = n_top;
         rk.n_topq = n_topq;
         rk.coop_stack = (int)stack5;
@@ -4535,6 +4550,9 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
         st->scene_bytes = s.flat.blob.size();
         st->reserved[1] = (uint64_t)(ring_bytes + (size_t)n_pix * 3 * sizeof(double) + (size_t)plan.tiles_owned * sizeof(unsigned int) +
                                      ((kernel == 5) ? (size_t)grid * COOP_POOL * COOP_REC * sizeof(uint64_t) : 0));  // workspace bytes
+        uint32_t shrink_bits;
+        std::memcpy(&shrink_bits, &node_shrink, 4);
+        st->reserved[3] = shrink_bits;  // (rt_render_multi overwrites entry 0's with its own count afterwards)
     }
 #ifdef RTAMD_COOP_STATS
     if (kernel == 5) {
@@ -5223,7 +5241,18 @@ void debug_hit_device(const rt_scene& s, int kernel, size_t n, const double* ray
     err.alloc(4);
     HIP_CHECK(hipMemset(err.p, 0, 4));
     HIP_CHECK(hipMemcpy(dr.p, rays, n * 48, hipMemcpyHostToDevice));
-    if (kernel < 1 || kernel > 6 || kernel == 4) throw RtError(RT_ERR_ARG, "rt_debug_hit_device: kernel 1, 2, 3, 5 or 6");
+    if (kernel < 1 || kernel > 7 || kernel == 4) throw RtError(RT_ERR_ARG, "rt_debug_hit_device: kernel 1, 2, 3, 5, 6 or 7");
+    // 7: mode 3's table with the pads of a render whose origins are these rays' (common/tighten.h): O_r = 2 max(ew, largest |origin coordinate|
+    // of the batch); as in a render, a scene with instances keeps the stored pads, and so does a batch that reaches origin_limit2
+    float shrink = 0.f;
+    if (kernel == 7) {
+        double o_abs = 0.;
+        for (size_t i = 0; i < n; i++)
+            for (int k = 0; k < 3; k++) o_abs = std::fmax(o_abs, std::fabs(rays[6 * i + k]));
+        if (!std::isfinite(o_abs)) o_abs = view.origin_limit2;  // (fmax drops a NaN coordinate: such a ray passes every box anyway)
+        shrink = box_shrink(view.origin_limit2, render_origin_bound(view.origin_limit2, o_abs), view.n_inst2 == 0u);
+        kernel = 3;
+    }
     if (kernel != 1 && !view.accel_ok) throw RtError(RT_ERR_UNSUPPORTED, "no accel for this scene");
     if (kernel != 1 && !(t_min >= 0.)) throw RtError(RT_ERR_UNSUPPORTED, "kernel 2 needs t_min >= 0 (box32)");
     if ((kernel == 5 || kernel == 6) && (view.coop_data_ok == 0 || view.n_inst2 < 1 || view.n_inst2 > (uint32_t)COOP_MAX_INST))
@@ -5239,14 +5268,14 @@ void debug_hit_device(const rt_scene& s, int kernel, size_t n, const double* ray
     }
     if (s.flat.xf_nest != 0u) {  // nested Transforms: the chain walk (kernels 5 / 6 were refused above: nested scenes have no compact data)
         if (smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)hit_kernel_nest, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        hipLaunchKernelGGL(hit_kernel_nest, dim3((unsigned)((n + 63) / 64)), dim3(64), smem, 0, view, kernel, n, (const double*)dr.p, t_min, t_max,
+        hipLaunchKernelGGL(hit_kernel_nest, dim3((unsigned)((n + 63) / 64)), dim3(64), smem, 0, view, kernel, shrink, n, (const double*)dr.p, t_min, t_max,
                            (double*)dout.p, (int*)err.p);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpy(out, dout.p, n * 96, hipMemcpyDeviceToHost));
         return;
     }
     hipLaunchKernelGGL(hit_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), smem, 0, view,
-                       kernel, n, (const double*)dr.p, t_min, t_max, (double*)dout.p, (int*)err.p);
+                       kernel, shrink, n, (const double*)dr.p, t_min, t_max, (double*)dout.p, (int*)err.p);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpy(out, dout.p, n * 96, hipMemcpyDeviceToHost));
 }

@@ -56,6 +56,9 @@ class rt_stats(C.Structure):
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
         d["workspace_bytes"] = int(self.reserved[1])
+        # rt_render on one device: how far kernel 2 moved the planes of its LDS node table inward for this render's ray origins (the f32's
+        # bits; 0: the stored boxes).  rt_render_multi's entry 0 keeps its row count in the same word: read that as rows_through_rccl.
+        d["box_shrink"] = float(np.uint32(self.reserved[3] & 0xFFFFFFFF).view(np.float32))
         return d
 
 

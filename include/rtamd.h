@@ -172,7 +172,9 @@ int rt_texture_checker(rt_scene* s, int t0, int t1);
 int rt_texture_image(rt_scene* s, int width, int height, const uint8_t* rgb);
 /* Book-2 extension, no reference counterpart (BASELINE config C5 names it): noise_texture(scale), the marble texture
  * 0.5 (1 + sin(scale p.z + 10 turb(p))) over Perlin noise with 7 octaves of turbulence; the 256 gradient vectors and the three
- * permutations come from the RNG stream (seed, "perlin" key, 0); sin is the deterministic rtamd-sin-1 (csrc/common/detsin.h) */
+ * permutations come from the RNG stream (seed, "perlin" key, 0); sin is the deterministic rtamd-sin-1 (csrc/common/detsin.h).
+ * The lattice index of an octave's coordinate x is floor(x) mod 256 of the mathematical integer (0..255) for every finite x -- so 0 for
+ * every |x| >= 2^60 -- and 0 for a non-finite x: defined at every coordinate a scene can hold (see "diagnostics", Noise). */
 int rt_texture_noise(rt_scene* s, double scale, uint64_t seed);
 /* material.rs:88-212  Lambertian::new / Metal::new / Dielectric::new / DiffuseLight::new */
 int rt_material_lambertian(rt_scene* s, int albedo_tex);
@@ -641,6 +643,29 @@ int rt_debug_env_pdf_device(const rt_scene* s, int device, size_t n, const doubl
  * pdfs of all M area lights, in list order from 0.0 (not divided by M). */
 int rt_debug_area_sample_device(const rt_scene* s, int device, size_t n, const double* in_host, double* out_host);
 int rt_debug_area_pdf_device(const rt_scene* s, int device, size_t n, const double* rays_host, double* pdf_host);
+/* shading and object-light diagnostics on HIP device `device`: what a path does after its hit, on explicit inputs, through the very
+ * functions the render kernels call.  The arguments are checked on the host first -- RT_ERR_ARG (a null pointer, n == 0, a material or
+ * light index that is not an integer of the scene's range), RT_ERR_NOT_COMMITTED -- then RT_ERR_NO_DEVICE without a GPU.  Every row has
+ * its own random stream, keys_host n*3 = {seed, pixel, sample} as uint64, and its own unit-zero status (1.0: some unit() met a vector of
+ * length 0; the row's other outputs are then what the arithmetic gave).  "next draw" = the two 32-bit halves {upper, lower} of the
+ * stream's next u64 after the call, as exact doubles: its index in rt_debug_rng_host's stream is the number of draws the call consumed.
+ * shade: emitted + scatter of material `mat` at an explicit hit record, texture lookup included (the noise-texture form where the scene
+ *   has a noise texture, as a render chooses).  in_host n*17 = {mat, mix, ray origin[3], ray direction[3], p[3], normal[3], front_face, u, v}
+ *   (the ray origin is carried for the oracle's Ray and not read); out_host n*22 = {scattered (0: Absorb), diffuse, out_dir[3], att[3],
+ *   emitted[3], mixed, continued, beta[3], dir[3], unit-zero status, next draw[2]}.  Where mix != 0 and the interaction is Diffuse, the
+ *   plain mixture step of integrator 1 follows (mixed = 1): continued = its weight is > 0, beta = the weight times att started from
+ *   (1, 1, 1) (left at that where not continued), dir = the direction it settled on; elsewhere mixed = continued = 0, beta = (1, 1, 1),
+ *   dir = out_dir.  out_dir is (0, 0, 0) on Absorb.  mix needs object lights and a scene without env sampling and area lights (RT_ERR_ARG).
+ * light sample: light_random of object light `light` (index into rt_scene_set_lights' list) seen from o: in_host n*4 = {o[3], light};
+ *   out_host n*6 = {dir[3], unit-zero status, next draw[2]}.
+ * light pdf: rays_host n*6 = {o[3], d[3]} -> pdf_host n*L: the pdf of EACH of the scene's L object lights for the ray, in list order
+ *   (the mixture adds them in that order from 0.0 and divides by L).
+ * Noise: the lattice index of a Perlin octave is floor(x) mod 256 of the mathematical integer, 0..255, for every finite coordinate x
+ * (computed as fx - 256 floor(fx / 256), exact in f64: no conversion leaves the range of int; every |x| >= 2^60 has index 0); a
+ * non-finite coordinate has index 0 (and the texture's value is then 0.5, through rtamd-sin-1 of a NaN). */
+int rt_debug_shade_device(const rt_scene* s, int device, size_t n, const double* in_host, const uint64_t* keys_host, double* out_host);
+int rt_debug_light_sample_device(const rt_scene* s, int device, size_t n, const double* in_host, const uint64_t* keys_host, double* out_host);
+int rt_debug_light_pdf_device(const rt_scene* s, int device, size_t n, const double* rays_host, double* pdf_host);
 
 #ifdef __cplusplus
 }

@@ -112,6 +112,10 @@ def lib():
     L.orc_area_sample.argtypes = [C.c_void_p, C.c_int64, c_double_p, c_double_p]
     L.orc_area_pdf.argtypes = [C.c_void_p, C.c_int64, c_double_p, c_double_p]
     L.orc_light_counters.argtypes = [C.c_void_p, c_u64_p]
+    c_i64_p = C.POINTER(C.c_int64)
+    L.orc_shade.argtypes = [C.c_void_p, C.c_int64, c_double_p, c_u64_p, c_double_p, c_i64_p]
+    L.orc_light_sample.argtypes = [C.c_void_p, C.c_int64, c_double_p, c_u64_p, c_double_p, c_i64_p]
+    L.orc_light_pdf.argtypes = [C.c_void_p, C.c_int64, c_double_p, c_double_p]
     _LIB = L
     return L
 
@@ -332,6 +336,7 @@ class Scene:
         fl = np.ascontiguousarray(flux if flux is not None else np.ones((len(ids), 3)), dtype=np.float64).reshape(-1)
         sc = np.ascontiguousarray(scale if scale is not None else np.ones(len(ids)), dtype=np.float64).reshape(-1)
         self._chk(self.L.orc_set_lights(self.h, len(ids), arr, fl.ctypes.data_as(c_double_p), sc.ctypes.data_as(c_double_p)), "set_lights")
+        self._n_lights = len(ids)
 
     # background / env sampling / area lights (include/rtamd.h; no reference counterpart)
     def set_background(self, kind, color0=(0.0, 0.0, 0.0), color1=(0.0, 0.0, 0.0), texture=-1, scale=1.0):
@@ -395,6 +400,28 @@ class Scene:
     def area_pdf(self, rays):
         """rays [n, 6] -> pdf [n] summed over all area lights: World.debug_area_pdf"""
         return self._batch(self.L.orc_area_pdf, "area_pdf", rays, 6, 1)[:, 0]
+
+    def _keyed(self, fn, what, x, keys, cols_in, cols_out):
+        a = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, cols_in)
+        k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(a.shape[0], 3)
+        out = np.zeros((a.shape[0], cols_out), dtype=np.float64)
+        draws = np.zeros(a.shape[0], dtype=np.int64)
+        self._chk(fn(self.h, a.shape[0], a.ctypes.data_as(c_double_p), k.ctypes.data_as(c_u64_p), out.ctypes.data_as(c_double_p),
+                     draws.ctypes.data_as(C.POINTER(C.c_int64))), what)
+        return out, draws
+
+    def shade(self, rows, keys):
+        """rows [n, 17], keys uint64 [n, 3] -> ([n, 22], draws [n]): World.debug_shade's layout (include/rtamd.h) and the random numbers
+        each row consumed; a row whose unit() threw has status 1 and zeros elsewhere"""
+        return self._keyed(self.L.orc_shade, "shade", rows, keys, 17, 22)
+
+    def light_sample(self, o_light, keys):
+        """[n, 4] = origin, object light index; keys uint64 [n, 3] -> ([n, 6], draws [n]): World.debug_light_sample"""
+        return self._keyed(self.L.orc_light_sample, "light_sample", o_light, keys, 4, 6)
+
+    def light_pdf(self, rays):
+        """rays [n, 6] -> [n, L], light_pdf_value of every object light in list order: World.debug_light_pdf"""
+        return self._batch(self.L.orc_light_pdf, "light_pdf", rays, 6, max(1, getattr(self, "_n_lights", 0)))
 
     def render_sppm(self, width, height, spp, iterations=50, photons_per_iter=500000, alpha=0.7, k_global=100, k_caustic=50,
                     max_bounces=4096, max_depth=50, t_min=1e-3, seed=1, n_workers=None):

@@ -418,10 +418,16 @@ struct NoiseTexture : Texture {
             }
         }
     }
+    // the lattice index of a coordinate with floor fx: floor(x) mod 256 of the mathematical integer, 0..255 (fx - 256 floor(fx / 256) is
+    // exact in f64 for every finite fx, so the conversion below is always in range); 0 for a non-finite coordinate
+    static int cell(double fx) {
+        const double m = fx - 256. * std::floor(fx / 256.);
+        return (m >= 0. && m < 256.) ? (int)m : 0;
+    }
     double noise(Vec3 p) const {
         const double fx = std::floor(p.x), fy = std::floor(p.y), fz = std::floor(p.z);
         const double u = p.x - fx, v = p.y - fy, w = p.z - fz;
-        const int i = (int)fx, j = (int)fy, k = (int)fz;
+        const int i = cell(fx), j = cell(fy), k = cell(fz);
         const double uu = u * u * (3. - 2. * u), vv = v * v * (3. - 2. * v), ww = w * w * (3. - 2. * w);
         double accum = 0.;
         for (int di = 0; di < 2; di++)
@@ -1250,7 +1256,15 @@ static double light_pdf_value(const Hitable* l, Vec3 o, Vec3 v, Ctx& cx) {
     HitRecord rec;
     Ctx scratch;  // the pdf's own hit test is not part of the traversal counters
     (void)cx;
-    if (!l->hit(Ray{o, v}, 0.001, INF, rec, scratch)) return 0.;
+    bool hit;
+    try {
+        hit = l->hit(Ray{o, v}, 0.001, INF, rec, scratch);
+    } catch (const UnitZero&) {
+        // a sphere light seen from so far away that the hit point rounds onto its centre: the record's normal has no length, but the ray
+        // did hit and the pdf reads no normal (the device's light_pdf_value builds no record).  A rectangle's normal is a constant.
+        hit = true;
+    }
+    if (!hit) return 0.;
     if (const Rect* r = dynamic_cast<const Rect*>(l)) {
         double area = (r->a1 - r->a0) * (r->b1 - r->b0);
         double distance_squared = rec.t * rec.t * v_sqlen(v);
@@ -1291,6 +1305,51 @@ static Vec3 light_random(const Hitable* l, Vec3 o, Rng& rng) {
 // L + M the environment (E = 1 where the scene samples its background and the table's total is not 0).  The draws of a Diffuse
 // interaction, in order: scatter()'s own, the coin, and in the light half the strategy index and the strategy's draws (object light:
 // light_random's; area light: three gen_f64; environment: four gen_f64).  The pdf sums the n strategies in index order and divides by n.
+// One Diffuse interaction of the mixture: scatter() has drawn `dir`; the coin, the strategy, the pdfs and the weight follow.  Returns false
+// when the path ends (weight not > 0: a direction below the surface, or a NaN); otherwise `throughput` has taken att times the weight.
+// `dir` is the direction the step settled on either way.  The renderer and orc_shade call this one function.
+static bool mixture_diffuse_step(const Scene& sc, const HitRecord& rec, Vec3 att, Vec3& throughput, Vec3& dir, Ctx& cx) {
+    const size_t n_lights = sc.lights.size(), n_area = sc.area_lights.size();
+    const bool env = sc.env_strategy();
+    const size_t n = n_lights + n_area + (env ? 1 : 0);
+    if (cx.rng.gen_f64() < 0.5) {
+        size_t li = (size_t)(uint32_t)(cx.rng.gen_f64() * (double)n);
+        if (li > n - 1) li = n - 1;
+        if (li < n_lights) {
+            cx.cnt.n_pick_object++;
+            dir = light_random(sc.lights[li], rec.p, cx.rng);
+        } else if (li < n_lights + n_area) {
+            cx.cnt.n_pick_area++;
+            const double x1 = cx.rng.gen_f64();
+            const double x2 = cx.rng.gen_f64();
+            const double x3 = cx.rng.gen_f64();
+            dir = area_sample(sc.area_tris, sc.area_lights[li - n_lights], rec.p, x1, x2, x3);
+        } else {
+            cx.cnt.n_pick_env++;
+            const double x1 = cx.rng.gen_f64();
+            const double x2 = cx.rng.gen_f64();
+            const double x3 = cx.rng.gen_f64();
+            const double x4 = cx.rng.gen_f64();
+            dir = env_sample(sc.env, x1, x2, x3, x4);
+        }
+    } else {
+        cx.cnt.n_cosine_half++;
+    }
+    double cosine = v_dot(rec.normal, v_unit(dir));
+    double scattering_pdf = (cosine < 0.) ? 0. : cosine / PI;
+    double lp = 0.;
+    for (size_t i = 0; i < n_lights; i++) lp = lp + light_pdf_value(sc.lights[i], rec.p, dir, cx);
+    for (size_t i = 0; i < n_area; i++) lp = lp + area_pdf(sc.area_tris, sc.area_lights[i], rec.p, dir);
+    if (env) lp = lp + env_pdf(sc.env, dir);
+    double pdf_val = 0.5 * (lp / (double)n) + 0.5 * scattering_pdf;
+    double wgt = scattering_pdf / pdf_val;
+    if (!(wgt > 0.)) {  // direction below the surface (or a NaN): the path carries nothing further
+        cx.cnt.n_wgt_end++;
+        return false;
+    }
+    throughput = v_muls(v_elemul(throughput, att), wgt);
+    return true;
+}
 static Vec3 sample_ray_mixture(const Scene& sc, Ray ray, int max_depth, double t_min, Ctx& cx) {
     Vec3 throughput(1, 1, 1);
     Vec3 radiance(0, 0, 0);
@@ -1298,9 +1357,6 @@ static Vec3 sample_ray_mixture(const Scene& sc, Ray ray, int max_depth, double t
     int depth = max_depth;
     int bounce = 0;
     HitRecord rec;
-    const size_t n_lights = sc.lights.size(), n_area = sc.area_lights.size();
-    const bool env = sc.env_strategy();
-    const size_t n = n_lights + n_area + (env ? 1 : 0);
     for (;;) {
         cx.cnt.n_segments++;
         if (!sc.root->hit(curr, t_min, INF, rec, cx)) {
@@ -1315,42 +1371,7 @@ static Vec3 sample_ray_mixture(const Scene& sc, Ray ray, int max_depth, double t
         if (!(sr.has_ray && sr.has_att)) break;
         if (sr.kind == Diffuse) {
             Vec3 dir = sr.ray.dir;  // the cosine-distributed sample the reference's scatter drew
-            if (cx.rng.gen_f64() < 0.5) {
-                size_t li = (size_t)(uint32_t)(cx.rng.gen_f64() * (double)n);
-                if (li > n - 1) li = n - 1;
-                if (li < n_lights) {
-                    cx.cnt.n_pick_object++;
-                    dir = light_random(sc.lights[li], rec.p, cx.rng);
-                } else if (li < n_lights + n_area) {
-                    cx.cnt.n_pick_area++;
-                    const double x1 = cx.rng.gen_f64();
-                    const double x2 = cx.rng.gen_f64();
-                    const double x3 = cx.rng.gen_f64();
-                    dir = area_sample(sc.area_tris, sc.area_lights[li - n_lights], rec.p, x1, x2, x3);
-                } else {
-                    cx.cnt.n_pick_env++;
-                    const double x1 = cx.rng.gen_f64();
-                    const double x2 = cx.rng.gen_f64();
-                    const double x3 = cx.rng.gen_f64();
-                    const double x4 = cx.rng.gen_f64();
-                    dir = env_sample(sc.env, x1, x2, x3, x4);
-                }
-            } else {
-                cx.cnt.n_cosine_half++;
-            }
-            double cosine = v_dot(rec.normal, v_unit(dir));
-            double scattering_pdf = (cosine < 0.) ? 0. : cosine / PI;
-            double lp = 0.;
-            for (size_t i = 0; i < n_lights; i++) lp = lp + light_pdf_value(sc.lights[i], rec.p, dir, cx);
-            for (size_t i = 0; i < n_area; i++) lp = lp + area_pdf(sc.area_tris, sc.area_lights[i], rec.p, dir);
-            if (env) lp = lp + env_pdf(sc.env, dir);
-            double pdf_val = 0.5 * (lp / (double)n) + 0.5 * scattering_pdf;
-            double wgt = scattering_pdf / pdf_val;
-            if (!(wgt > 0.)) {  // direction below the surface (or a NaN): the path carries nothing further
-                cx.cnt.n_wgt_end++;
-                break;
-            }
-            throughput = v_muls(v_elemul(throughput, sr.att), wgt);
+            if (!mixture_diffuse_step(sc, rec, sr.att, throughput, dir, cx)) break;
             curr = Ray{rec.p, dir, curr.time};
         } else {
             throughput = v_elemul(throughput, sr.att);
@@ -2339,6 +2360,105 @@ int orc_area_pdf(void* s, int64_t n, const double* rays6, double* out) {
     for (int64_t k = 0; k < n; k++) {
         const double* x = rays6 + 6 * k;
         out[k] = area_pdf_all(sc, Vec3(x[0], x[1], x[2]), Vec3(x[3], x[4], x[5]));
+    }
+    return ORC_OK;
+}
+// the layouts of rt_debug_shade_device (in = n x {mat, mix, ray o, ray d, p, normal, front_face, u, v}, keys = n x {seed, pixel, sample};
+// out = n x {scattered, diffuse, out_dir, att, emitted, mixed, continued, beta, dir, unit-zero status, the next draw's two halves}),
+// rt_debug_light_sample_device (in = n x {o, light}; out = n x {dir, status, next draw}) and rt_debug_light_pdf_device (in = n x {o, d};
+// out = n x L, one pdf per object light).  draws[k] = the random numbers row k consumed.  A row whose unit() threw has status 1, and its
+// other outputs are zero: the device goes on computing there, so only the status is comparable.
+static void next_draw(Rng rng, double* out2) {
+    const uint64_t x = rng.next_u64();
+    out2[0] = (double)(uint32_t)(x >> 32);
+    out2[1] = (double)(uint32_t)x;
+}
+int orc_shade(void* s, int64_t n, const double* in17, const uint64_t* keys3, double* out22, int64_t* draws) {
+    Scene& sc = *(Scene*)s;
+    for (int64_t k = 0; k < n; k++) {
+        const double* x = in17 + 17 * k;
+        if (!(x[0] >= 0. && x[0] < (double)sc.materials.size() && x[0] == std::floor(x[0]))) return ORC_ERR_ARG;
+        if (x[1] != 0. && (sc.lights.empty() || !sc.area_lights.empty() || sc.env_on)) return ORC_ERR_ARG;
+    }
+    for (int64_t k = 0; k < n; k++) {
+        const double* x = in17 + 17 * k;
+        double* y = out22 + 22 * k;
+        for (int i = 0; i < 22; i++) y[i] = 0.;
+        Ctx cx;
+        cx.rng = Rng(keys3[3 * k], keys3[3 * k + 1], keys3[3 * k + 2]);
+        HitRecord rec;
+        rec.p = Vec3(x[8], x[9], x[10]);
+        rec.normal = Vec3(x[11], x[12], x[13]);
+        rec.front_face = x[14] != 0.;
+        rec.u = x[15];
+        rec.v = x[16];
+        rec.mat = mat(sc, (int)x[0]);
+        const Ray r{Vec3(x[2], x[3], x[4]), Vec3(x[5], x[6], x[7])};
+        try {
+            const Vec3 e = rec.mat->emitted(rec);
+            const ScatterResult sr = rec.mat->scatter(r, rec, cx);
+            const bool scattered = sr.has_ray && sr.has_att;
+            Vec3 beta(1, 1, 1), dir = scattered ? sr.ray.dir : Vec3(0, 0, 0);
+            bool mixed = false, cont = false;
+            if (scattered && sr.kind == Diffuse && x[1] != 0.) {
+                mixed = true;
+                cont = mixture_diffuse_step(sc, rec, sr.att, beta, dir, cx);
+            }
+            y[0] = scattered ? 1. : 0.;
+            y[1] = (scattered && sr.kind == Diffuse) ? 1. : 0.;
+            if (scattered) {
+                y[2] = sr.ray.dir.x; y[3] = sr.ray.dir.y; y[4] = sr.ray.dir.z;
+                y[5] = sr.att.x; y[6] = sr.att.y; y[7] = sr.att.z;
+            }
+            y[8] = e.x; y[9] = e.y; y[10] = e.z;
+            y[11] = mixed ? 1. : 0.;
+            y[12] = cont ? 1. : 0.;
+            y[13] = beta.x; y[14] = beta.y; y[15] = beta.z;
+            y[16] = dir.x; y[17] = dir.y; y[18] = dir.z;
+            next_draw(cx.rng, y + 20);
+        } catch (const UnitZero&) {
+            for (int i = 0; i < 22; i++) y[i] = 0.;
+            y[19] = 1.;
+        }
+        draws[k] = (int64_t)cx.rng.draws;
+    }
+    return ORC_OK;
+}
+int orc_light_sample(void* s, int64_t n, const double* in4, const uint64_t* keys3, double* out6, int64_t* draws) {
+    Scene& sc = *(Scene*)s;
+    if (sc.lights.empty()) return ORC_ERR_ARG;
+    for (int64_t k = 0; k < n; k++) {
+        const double li = in4[4 * k + 3];
+        if (!(li >= 0. && li < (double)sc.lights.size() && li == std::floor(li))) return ORC_ERR_ARG;
+    }
+    for (int64_t k = 0; k < n; k++) {
+        const double* x = in4 + 4 * k;
+        double* y = out6 + 6 * k;
+        for (int i = 0; i < 6; i++) y[i] = 0.;
+        Rng rng(keys3[3 * k], keys3[3 * k + 1], keys3[3 * k + 2]);
+        try {
+            const Vec3 d = light_random(sc.lights[(size_t)x[3]], Vec3(x[0], x[1], x[2]), rng);
+            y[0] = d.x; y[1] = d.y; y[2] = d.z;
+            next_draw(rng, y + 4);
+        } catch (const UnitZero&) {
+            y[3] = 1.;
+        }
+        draws[k] = (int64_t)rng.draws;
+    }
+    return ORC_OK;
+}
+int orc_light_pdf(void* s, int64_t n, const double* rays6, double* out) {
+    Scene& sc = *(Scene*)s;
+    const size_t L = sc.lights.size();
+    if (L == 0) return ORC_ERR_ARG;
+    Ctx cx;
+    try {
+        for (int64_t k = 0; k < n; k++) {
+            const double* x = rays6 + 6 * k;
+            for (size_t i = 0; i < L; i++) out[(size_t)k * L + i] = light_pdf_value(sc.lights[i], Vec3(x[0], x[1], x[2]), Vec3(x[3], x[4], x[5]), cx);
+        }
+    } catch (const UnitZero&) {  // (the hit record of a light's own hit test: the device's pdf builds none)
+        return ORC_ERR_UNIT_ZERO;
     }
     return ORC_OK;
 }

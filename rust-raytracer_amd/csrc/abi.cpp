@@ -68,6 +68,8 @@ void debug_env_eval_device(const rt_scene& s, int mode, size_t n, const double* 
 }  // namespace rtamd
 namespace rtamd {
 void debug_area_eval_device(const rt_scene& s, int mode, size_t n, const double* in, double* out) __attribute__((weak));  // (likewise)
+void debug_shade_device(const rt_scene& s, size_t n, const double* in, const uint64_t* keys, double* out) __attribute__((weak));
+void debug_light_eval_device(const rt_scene& s, int mode, size_t n, const double* in, const uint64_t* keys, double* out) __attribute__((weak));
 }  // namespace rtamd
 static bool env_debug_linked() { return &rtamd::debug_env_table_device != nullptr && &rtamd::debug_env_eval_device != nullptr; }
 
@@ -992,6 +994,55 @@ int rt_debug_area_pdf_device(const rt_scene* s, int device, size_t n, const doub
         if (&rtamd::debug_area_eval_device == nullptr) throw RtError(RT_ERR_NO_DEVICE, "no HIP device");
         debug_area_eval_device(*s, 1, n, rays_host, pdf_host);
     });
+}
+// the shading and object-light diagnostics check their arguments on the host, before they ask for a device
+static void index_column(const double* in, size_t n, size_t stride, size_t col, size_t count, const char* what) {
+    for (size_t k = 0; k < n; k++) {
+        const double v = in[stride * k + col];
+        if (!(v >= 0. && v < (double)count && v == std::floor(v))) throw RtError(RT_ERR_ARG, what);
+    }
+}
+static int shade_debug(const rt_scene* s, int device, bool linked, const std::function<void()>& check, const std::function<void()>& f) {
+    return guard([&] {
+        REQUIRE(s, "null scene");
+        check();
+        const int n_dev = device_count();
+        if (n_dev < 1 || !linked) throw RtError(RT_ERR_NO_DEVICE, "no HIP device");
+        REQUIRE(device >= 0 && device < n_dev, "no such device");
+        DeviceScope dev_scope(device);
+        f();
+        return (int)RT_OK;
+    });
+}
+static void object_lights_only(const rt_scene& s) {
+    if (!s.committed) throw RtError(RT_ERR_NOT_COMMITTED, "scene not committed");
+    if (s.flat.view.n_lights == 0u) throw RtError(RT_ERR_ARG, "the scene has no object lights (rt_scene_set_lights)");
+}
+int rt_debug_shade_device(const rt_scene* s, int device, size_t n, const double* in_host, const uint64_t* keys_host, double* out_host) {
+    return shade_debug(s, device, &rtamd::debug_shade_device != nullptr, [&] {
+        REQUIRE(n > 0 && in_host && keys_host && out_host, "bad argument");
+        if (!s->committed) throw RtError(RT_ERR_NOT_COMMITTED, "scene not committed");
+        index_column(in_host, n, 17, 0, s->materials.size(), "rt_debug_shade_device: no such material");
+        bool mix = false;
+        for (size_t k = 0; k < n; k++) mix |= in_host[17 * k + 1] != 0.;
+        if (!mix) return;
+        object_lights_only(*s);
+        if (s->flat.view.off_env != 0u || s->flat.view.off_area != 0u)
+            throw RtError(RT_ERR_ARG, "rt_debug_shade_device takes the plain mixture step: object lights only, no env sampling, no area lights");
+    }, [&] { debug_shade_device(*s, n, in_host, keys_host, out_host); });
+}
+int rt_debug_light_sample_device(const rt_scene* s, int device, size_t n, const double* in_host, const uint64_t* keys_host, double* out_host) {
+    return shade_debug(s, device, &rtamd::debug_light_eval_device != nullptr, [&] {
+        REQUIRE(n > 0 && in_host && keys_host && out_host, "bad argument");
+        object_lights_only(*s);
+        index_column(in_host, n, 4, 3, s->flat.view.n_lights, "rt_debug_light_sample_device: no such light");
+    }, [&] { debug_light_eval_device(*s, 0, n, in_host, keys_host, out_host); });
+}
+int rt_debug_light_pdf_device(const rt_scene* s, int device, size_t n, const double* rays_host, double* pdf_host) {
+    return shade_debug(s, device, &rtamd::debug_light_eval_device != nullptr, [&] {
+        REQUIRE(n > 0 && rays_host && pdf_host, "bad argument");
+        object_lights_only(*s);
+    }, [&] { debug_light_eval_device(*s, 1, n, rays_host, nullptr, pdf_host); });
 }
 int rt_debug_schedule(int64_t tiles_owned, int n_waves, int s_begin, int s_end, int sub_spp, int job_units, int* out25) {
     int rounds = 0;

@@ -52,6 +52,10 @@ void debug_env_eval_device(const rt_scene& s, int mode, size_t n, const double* 
 // area light diagnostics on the current device: mode 0: n draws (in n*7 {o, xi0..xi3} -> out n*4 {dir, pdf}),
 // mode 1: n pdfs (in n*6 {o, d} -> out n)
 void debug_area_eval_device(const rt_scene& s, int mode, size_t n, const double* in, double* out);
+// shading and object-light diagnostics on the current device (the scene, the material and light indices were checked by the caller):
+// shade: in n*17, keys n*3, out n*22; light eval mode 0: n draws (in n*4 {o, light}, keys n*3 -> out n*6), mode 1: n*6 {o, d} -> out n * n_lights
+void debug_shade_device(const rt_scene& s, size_t n, const double* in, const uint64_t* keys, double* out);
+void debug_light_eval_device(const rt_scene& s, int mode, size_t n, const double* in, const uint64_t* keys, double* out);
 int device_count();
 // thin HIP wrappers so abi.cpp stays free of HIP headers
 void* dev_alloc(size_t n);

@@ -377,15 +377,30 @@ __device__ __attribute__((noinline)) bool msphere_hit(const double* q, double ti
     return true;
 }
 // perlin::noise / turb and noise_texture::value of the book over the texture's tables (768 f64 gradient vectors, 768 permutation bytes)
+// The lattice index of a coordinate x is floor(x) mod 256 of the mathematical integer (rtamd.h "noise"): fx - 256 floor(fx / 256) is exact
+// in f64 for every finite fx, so no conversion leaves the range of int; a non-finite x has index 0.
+DEV int perlin_cell(double fx) {
+    const double m = fx - 256. * floor(fx * 0.00390625);
+    return (m >= 0. && m < 256.) ? (int)m : 0;
+}
 __device__ __attribute__((noinline)) double noise_marble(const uint8_t* tab, double scale, double px, double py, double pz) {
     const double* ranvec = (const double*)tab;
     const uint8_t* perm = tab + 768 * sizeof(double);
     double accum_t = 0., weight = 1.;
     double x = px, y = py, z = pz;
+    // |p| < 2^25 on every axis (a NaN is not): the seven octaves stay below 2^31, each floor converts to int exactly and its low eight
+    // bits ARE floor(x) mod 256, so the common case keeps the one conversion; only a far point pays for the f64 form
+    const double NEAR = 33554432.;
+    const bool near = (fabs(px) < NEAR) && (fabs(py) < NEAR) && (fabs(pz) < NEAR);
     for (int oct = 0; oct < 7; oct++) {
         const double fx = floor(x), fy = floor(y), fz = floor(z);
         const double u = x - fx, v = y - fy, w = z - fz;
-        const int i = (int)fx, j = (int)fy, k = (int)fz;
+        int i, j, k;
+        if (near) {
+            i = (int)fx; j = (int)fy; k = (int)fz;
+        } else {
+            i = perlin_cell(fx); j = perlin_cell(fy); k = perlin_cell(fz);
+        }
         const double uu = u * u * (3. - 2. * u), vv = v * v * (3. - 2. * v), ww = w * w * (3. - 2. * w);
         double accum = 0.;
         for (int di = 0; di < 2; di++)
@@ -5287,3 +5302,5 @@ void debug_hit_device(const rt_scene& s, int kernel, size_t n, const double* ray
 #include "adaptive.inc"
 // rt_region_render: the crop behind a region call's one render_tiles launch
 #include "region.inc"
+// rt_debug_shade_device, rt_debug_light_sample_device, rt_debug_light_pdf_device: shading and object lights on explicit inputs
+#include "shade_debug.inc"

@@ -233,6 +233,9 @@ _SIGS = [
     ("rt_debug_env_pdf_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, _dp]),
     ("rt_debug_area_sample_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, _dp]),
     ("rt_debug_area_pdf_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, _dp]),
+    ("rt_debug_shade_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, C.POINTER(C.c_uint64), _dp]),
+    ("rt_debug_light_sample_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, C.POINTER(C.c_uint64), _dp]),
+    ("rt_debug_light_pdf_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, _dp]),
 ]
 ABI_SYMBOLS = [s[0] for s in _SIGS]
 
@@ -506,6 +509,7 @@ class World:
     def set_lights(self, lights):
         arr = (C.c_int * len(lights))(*lights)
         _chk(self.L.rt_scene_set_lights(self.h, len(lights), arr))
+        self.n_lights = len(lights)
 
     def set_background(self, color=None, gradient=None, texture=None, scale=1.0):
         """rt_scene_set_background (before commit): at most one of color=(r, g, b) (kind 1), gradient=((down), (up)) (kind 2) or
@@ -815,6 +819,37 @@ class World:
         r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
         out = np.zeros(r.shape[0], dtype=np.float64)
         _chk(self.L.rt_debug_area_pdf_device(self.h, int(device), r.shape[0], r.ctypes.data_as(_dp), out.ctypes.data_as(_dp)))
+        return out
+
+    def debug_shade(self, rows, keys, device=0):
+        """rt_debug_shade_device: rows [n, 17] = mat, mix, ray origin, ray direction, p, normal, front_face, u, v; keys uint64 [n, 3] =
+        seed, pixel, sample -> [n, 22] = scattered, diffuse, out_dir, att, emitted, mixed, continued, beta, dir, unit-zero status, the
+        next draw's two 32-bit halves"""
+        x = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, 17)
+        k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(x.shape[0], 3)
+        out = np.zeros((x.shape[0], 22), dtype=np.float64)
+        _chk(self.L.rt_debug_shade_device(self.h, int(device), x.shape[0], x.ctypes.data_as(_dp), k.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                          out.ctypes.data_as(_dp)))
+        return out
+
+    def debug_light_sample(self, o_light, keys, device=0):
+        """rt_debug_light_sample_device: [n, 4] = origin, object light index; keys uint64 [n, 3] -> [n, 6] = direction, unit-zero status,
+        the next draw's two 32-bit halves"""
+        x = np.ascontiguousarray(o_light, dtype=np.float64).reshape(-1, 4)
+        k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(x.shape[0], 3)
+        out = np.zeros((x.shape[0], 6), dtype=np.float64)
+        _chk(self.L.rt_debug_light_sample_device(self.h, int(device), x.shape[0], x.ctypes.data_as(_dp), k.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                 out.ctypes.data_as(_dp)))
+        return out
+
+    def debug_light_pdf(self, rays, device=0, n_lights=None):
+        """rt_debug_light_pdf_device: rays [n, 6] = origin, direction -> [n, L]: the pdf of each of the L object lights, in list order"""
+        r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        n_lights = getattr(self, "n_lights", None) if n_lights is None else int(n_lights)
+        if n_lights is None:  # (a scene from a file: the caller knows its light list)
+            raise ValueError("debug_light_pdf: pass n_lights, the length of the scene's object light list")
+        out = np.zeros((r.shape[0], max(1, n_lights)), dtype=np.float64)  # (a scene without lights is refused)
+        _chk(self.L.rt_debug_light_pdf_device(self.h, int(device), r.shape[0], r.ctypes.data_as(_dp), out.ctypes.data_as(_dp)))
         return out
 
 

@@ -357,6 +357,9 @@ extern "C" {
     pub fn rt_debug_env_pdf_device(s: *const rt_scene, device: c_int, n: usize, dirs_host: *const c_double, pdf_host: *mut c_double) -> c_int;
     pub fn rt_debug_area_sample_device(s: *const rt_scene, device: c_int, n: usize, in_host: *const c_double, out_host: *mut c_double) -> c_int;
     pub fn rt_debug_area_pdf_device(s: *const rt_scene, device: c_int, n: usize, rays_host: *const c_double, pdf_host: *mut c_double) -> c_int;
+    pub fn rt_debug_shade_device(s: *const rt_scene, device: c_int, n: usize, in_host: *const c_double, keys_host: *const u64, out_host: *mut c_double) -> c_int;
+    pub fn rt_debug_light_sample_device(s: *const rt_scene, device: c_int, n: usize, in_host: *const c_double, keys_host: *const u64, out_host: *mut c_double) -> c_int;
+    pub fn rt_debug_light_pdf_device(s: *const rt_scene, device: c_int, n: usize, rays_host: *const c_double, pdf_host: *mut c_double) -> c_int;
 }
 
 // ------------------------------------------------------------------ errors ----

@@ -666,6 +666,57 @@ int rt_debug_area_pdf_device(const rt_scene* s, int device, size_t n, const doub
 int rt_debug_shade_device(const rt_scene* s, int device, size_t n, const double* in_host, const uint64_t* keys_host, double* out_host);
 int rt_debug_light_sample_device(const rt_scene* s, int device, size_t n, const double* in_host, const uint64_t* keys_host, double* out_host);
 int rt_debug_light_pdf_device(const rt_scene* s, int device, size_t n, const double* rays_host, double* pdf_host);
+/* SPPM photon gather diagnostics: ONE iteration of the render's own gather on explicit inputs (host buffers throughout) -- the grid
+ * build and the sort of both photon maps, gather_kernel (four waves per block, one gather point per wave, caustic map first, then
+ * global) and estimate_kernel, launched as rt_render_sppm launches them.  No scene is involved.
+ *   global / caustic: the two photon maps, n * 9 doubles {position[3], power[3], norm[3]} each; either n may be 0 (its pointer is then
+ *     not read).  At most 2^30 photons per map.
+ *   points: m * 7 doubles {valid, p[3], bsdf[3]}; a row with valid == 0 is skipped and its statistics stay as they came.
+ *   stats: m * 10 doubles {global[5], caustic[5]}, each map {flux[3], radius2, photons} -- IN: the state before this iteration (all zeros
+ *     before the first), OUT: the state after it.  The caller carries it from call to call, each with that iteration's photon maps.
+ *   k_global, k_caustic, alpha: as in rt_sppm_config.  shift: the S of the 2^-S fixed-point flux accumulators, 0..60.  CONTRACT: every
+ *     photon's term bsdf * power * (1 - disk factor) has |term| * 2^S < 2^52 per channel (rt_render_sppm chooses S from the lights'
+ *     power so that this holds), and the int64 sum of one query's terms does not overflow.  term * 2^S is rounded to the nearest
+ *     integer, ties to even.
+ *   n_emitted: the N of flux / (pi * radius2 * N).  estimates: OUT m * 6 doubles {caustic[3], global[3]} for EVERY row (0 / 0 = NaN where
+ *     radius2 == 0).
+ *   grid_global, grid_caustic: OUT what the grid over each map came out as.  Where cell_start / index are not NULL they receive the
+ *     dim[0] * dim[1] * dim[2] + 1 cell offsets (cell c = (z * dim[1] + y) * dim[0] + x holds index[cell_start[c] .. cell_start[c + 1]))
+ *     and the n photon indices grouped by cell; *_capacity are the entries the buffers hold (RT_ERR_ARG where that is too few:
+ *     rt_debug_grid_shape gives the number of cells beforehand).  A map with n == 0 has no grid: lo = 0, cell = 1, dim = 1, no buffer written.
+ * Honours rt_tuning.sppm_knn_candidates as rt_render_sppm does.  The arguments are checked on the host first -- RT_ERR_ARG for a null
+ * pointer, m == 0, k < 1, !(alpha > 0), S outside 0..60 -- then RT_ERR_NO_DEVICE without a GPU.  A photon position that is not finite
+ * is RT_ERR_UNSUPPORTED.  Returns RT_ERR_UNIT_ZERO where some gather point lies exactly on a photon it visits (as rt_render_sppm does);
+ * every output is then still written, with what the arithmetic gave. */
+typedef struct rt_debug_grid {
+    double lo[3];               /* the grid's origin: the least photon coordinate per axis */
+    double cell;                /* the edge of a cell */
+    int32_t dim[3];             /* cells per axis, 1..161 */
+    int32_t reserved;
+    uint32_t* cell_start;       /* NULL, or cell_start_capacity entries */
+    uint32_t* index;            /* NULL, or index_capacity entries */
+    uint64_t cell_start_capacity, index_capacity;
+} rt_debug_grid;
+typedef struct rt_debug_sppm_gather {
+    uint64_t n_global, n_caustic, m;
+    const double* global;
+    const double* caustic;
+    const double* points;
+    double* stats;
+    double* estimates;
+    int32_t k_global, k_caustic;
+    double alpha;
+    int32_t shift;                 /* S */
+    int32_t reserved;
+    double n_emitted;
+    rt_debug_grid grid_global, grid_caustic;
+} rt_debug_sppm_gather;
+int rt_debug_sppm_gather_device(int device, rt_debug_sppm_gather* io);
+/* the shape build_grid gives the uniform grid over n photons whose bounding box is [lo3, hi3] (host logic only, no device needed):
+ * cell = 2 * sqrt(area / n) of the box's surface area, not below longest extent / 160; dim = floor(extent / cell) + 1 per axis, 1..161.
+ * Fallbacks: a box without area (a line or a point) takes cell = its longest extent, a point cell = 1; n == 0 gives cell = 1, dim = 1.
+ * RT_ERR_UNSUPPORTED where an extent is negative or not finite. */
+int rt_debug_grid_shape(const double* lo3, const double* hi3, uint64_t n, double* cell, int32_t* dim3);
 
 #ifdef __cplusplus
 }

@@ -116,6 +116,10 @@ def lib():
     L.orc_shade.argtypes = [C.c_void_p, C.c_int64, c_double_p, c_u64_p, c_double_p, c_i64_p]
     L.orc_light_sample.argtypes = [C.c_void_p, C.c_int64, c_double_p, c_u64_p, c_double_p, c_i64_p]
     L.orc_light_pdf.argtypes = [C.c_void_p, C.c_int64, c_double_p, c_double_p]
+    L.orc_sppm_gather.argtypes = [C.c_int64, c_double_p, C.c_int64, c_double_p, C.c_int64, c_double_p, c_double_p, C.c_int, C.c_int, C.c_double,
+                                  C.c_int, C.c_double, c_double_p]
+    L.orc_sppm_iteration.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, c_int_p, C.c_int, C.c_int64, c_double_p, c_double_p, c_i64_p,
+                                     c_double_p, c_int_p]
     _LIB = L
     return L
 
@@ -126,6 +130,23 @@ def _d3(v):
 
 class OracleError(RuntimeError):
     pass
+
+
+def sppm_gather(global_photons, caustic_photons, points, stats, k_global, k_caustic, alpha, S, n_emitted):
+    """One iteration of the SPPM gather by brute force, in rtamd.debug_sppm_gather's layouts (include/rtamd.h): photon maps [n, 9] =
+    {position, power, norm}, points [m, 7] = {valid, p, bsdf}, stats [m, 10] = the state before -> (stats [m, 10] after, estimates [m, 6],
+    unit_zero: some unit() met a zero vector; such a point keeps what the updates before the throw left)."""
+    g, c = (np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 9) for a in (global_photons, caustic_photons))
+    pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 7)
+    st = np.array(stats, dtype=np.float64).reshape(-1, 10)
+    assert len(st) == len(pts)
+    est = np.zeros((len(pts), 6))
+    rc = lib().orc_sppm_gather(len(g), g.ctypes.data_as(c_double_p), len(c), c.ctypes.data_as(c_double_p), len(pts), pts.ctypes.data_as(c_double_p),
+                               st.ctypes.data_as(c_double_p), int(k_global), int(k_caustic), float(alpha), int(S), float(n_emitted),
+                               est.ctypes.data_as(c_double_p))
+    if rc not in (0, -2):
+        raise OracleError("sppm_gather failed (%d)" % rc)
+    return st, est, rc == -2
 
 
 COUNTER_NAMES = ("n_aabb", "n_sphere", "n_rect", "n_tri", "n_xform", "n_segments", "n_samples")
@@ -435,6 +456,19 @@ class Scene:
         self._chk(self.L.orc_render_sppm(self.h, width, height, spp, max_depth, float(t_min), int(seed), cfg, float(alpha), n_workers,
                                          out.ctypes.data_as(c_double_p), stats.ctypes.data_as(c_double_p), tot), "render_sppm")
         return out, stats, (int(tot[0]), int(tot[1]))
+
+    def sppm_iteration(self, width, height, it, photons_per_iter, k_global=100, k_caustic=50, max_bounces=4096, seed=1):
+        """the photon maps and gather points of iteration `it` of render_sppm's pre-pass: (global [n, 9], caustic [n, 9], points [W*H, 7], S)
+        in sppm_gather's layouts; S = the fixed-point shift the pre-pass takes from the scene's lights"""
+        cfg = (C.c_int * 5)(it + 1, int(photons_per_iter), int(k_global), int(k_caustic), int(max_bounces))
+        cap = 64 * int(photons_per_iter) + 1024
+        g, c = np.zeros((cap, 9)), np.zeros((cap, 9))
+        gp = np.zeros((width * height, 7))
+        counts = (C.c_int64 * 2)()
+        S = C.c_int()
+        self._chk(self.L.orc_sppm_iteration(self.h, width, height, int(seed), cfg, int(it), cap, g.ctypes.data_as(c_double_p),
+                                            c.ctypes.data_as(c_double_p), counts, gp.ctypes.data_as(c_double_p), C.byref(S)), "sppm_iteration")
+        return g[:counts[0]].copy(), c[:counts[1]].copy(), gp, S.value
 
     def render(self, width, height, spp, max_depth=50, t_min=1e-3, seed=1, window=None, n_jobs=64, n_workers=None, integrator=0):
         """Camera::capture_image: returns (radiance f64 [wh,ww,3], counters dict); light_counters() then tells what the paths did.

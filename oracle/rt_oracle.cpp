@@ -2657,6 +2657,102 @@ int orc_render_sppm(void* s, int width, int height, int spp, int max_depth, doub
     return render(sc, a, 64, n_workers, out_rgb, nullptr);
 }
 
+// One iteration of the SPPM gather on explicit inputs, in the layouts of rt_debug_sppm_gather_device (include/rtamd.h): photon maps
+// n x 9 {position, power, norm}, gp7 = m x {valid, p, bsdf}, stats10 = m x {global[5], caustic[5]} in and out, est6 = m x {caustic[3],
+// global[3]} out.  Per valid point: sppm_update of the caustic map, then of the global map (photon_mapper.rs:284-285), by brute force;
+// then adjust_flux's division for every row.  A point whose unit() threw keeps what the updates before the throw left, and the call
+// returns ORC_ERR_UNIT_ZERO after it has gone through every point.
+int orc_sppm_gather(int64_t n_global, const double* glo9, int64_t n_caustic, const double* cau9, int64_t m, const double* gp7, double* stats10,
+                    int k_global, int k_caustic, double alpha, int S, double n_emitted, double* est6) {
+    if (n_global < 0 || n_caustic < 0 || m < 1 || !gp7 || !stats10 || !est6 || (n_global && !glo9) || (n_caustic && !cau9)) return ORC_ERR_ARG;
+    if (k_global < 1 || k_caustic < 1 || !(alpha > 0.) || S < 0 || S > 60) return ORC_ERR_ARG;
+    auto photons = [](int64_t n, const double* x) {
+        std::vector<Photon> pm((size_t)n);
+        for (int64_t i = 0; i < n; i++, x += 9)
+            pm[(size_t)i] = Photon{Vec3(x[0], x[1], x[2]), Vec3(x[3], x[4], x[5]), Vec3(0., 0., 0.), Vec3(x[6], x[7], x[8])};
+        return pm;
+    };
+    const std::vector<Photon> all = photons(n_global, glo9), cau = photons(n_caustic, cau9);
+    int rc = ORC_OK;
+    for (int64_t i = 0; i < m; i++) {
+        const double* g = gp7 + 7 * i;
+        double* st = stats10 + 10 * i;
+        SPPM two[2];  // global, caustic
+        for (int k = 0; k < 2; k++) {
+            two[k].flux = Vec3(st[5 * k], st[5 * k + 1], st[5 * k + 2]);
+            two[k].radius2 = st[5 * k + 3];
+            two[k].photons = (uint64_t)st[5 * k + 4];
+        }
+        if (g[0] != 0.) {
+            GatherPoint gp;
+            gp.valid = true;
+            gp.p = Vec3(g[1], g[2], g[3]);
+            gp.bsdf = Vec3(g[4], g[5], g[6]);
+            try {
+                sppm_update(two[1], gp, cau, (size_t)k_caustic, alpha, S);  // caustic first (:284)
+                sppm_update(two[0], gp, all, (size_t)k_global, alpha, S);
+            } catch (const UnitZero&) {
+                rc = ORC_ERR_UNIT_ZERO;
+            }
+            for (int k = 0; k < 2; k++) {
+                st[5 * k] = two[k].flux.x; st[5 * k + 1] = two[k].flux.y; st[5 * k + 2] = two[k].flux.z;
+                st[5 * k + 3] = two[k].radius2; st[5 * k + 4] = (double)two[k].photons;
+            }
+        }
+        const Vec3 ec = sppm_estimate(two[1], n_emitted), eg = sppm_estimate(two[0], n_emitted);
+        double* e = est6 + 6 * i;
+        e[0] = ec.x; e[1] = ec.y; e[2] = ec.z;
+        e[3] = eg.x; e[4] = eg.y; e[5] = eg.z;
+    }
+    return rc;
+}
+// The photon maps and the gather points of iteration `it` of orc_render_sppm's pre-pass (cfg5 as there): both maps n x 9 {position,
+// power, norm} up to `capacity` photons each, gp7 = width * height x {valid, p, bsdf}; counts2 = {global, caustic} photons of the
+// iteration (ORC_ERR_ARG where one exceeds capacity; the counts are still reported), *S_out = the fixed-point shift of the scene's lights.
+int orc_sppm_iteration(void* s, int width, int height, uint64_t seed, const int* cfg5, int it, int64_t capacity, double* glo9, double* cau9,
+                       int64_t* counts2, double* gp7, int* S_out) {
+    Scene& sc = *(Scene*)s;
+    if (width <= 1 || height <= 1 || !cfg5 || it < 0 || !counts2 || !gp7 || !S_out || !sc.root || !sc.cam_set || sc.lights.empty()) return ORC_ERR_ARG;
+    SppmConfig cfg;
+    cfg.iterations = cfg5[0]; cfg.photons_per_iter = cfg5[1]; cfg.k_global = cfg5[2]; cfg.k_caustic = cfg5[3]; cfg.max_bounces = cfg5[4];
+    *S_out = sppm_fixed_shift(sc);
+    try {
+        std::vector<Photon> all, cau;
+        const uint64_t P = (uint64_t)cfg.photons_per_iter;
+        trace_photons(sc, cfg, seed, (uint64_t)it * P, (uint64_t)(it + 1) * P, all, cau);
+        counts2[0] = (int64_t)all.size();
+        counts2[1] = (int64_t)cau.size();
+        if (counts2[0] > capacity || counts2[1] > capacity || (counts2[0] && !glo9) || (counts2[1] && !cau9)) return ORC_ERR_ARG;
+        const std::vector<Photon>* maps[2] = {&all, &cau};
+        double* outs[2] = {glo9, cau9};
+        for (int k = 0; k < 2; k++)
+            for (size_t i = 0; i < maps[k]->size(); i++) {
+                const Photon& ph = (*maps[k])[i];
+                double* o = outs[k] + 9 * i;
+                o[0] = ph.position.x; o[1] = ph.position.y; o[2] = ph.position.z;
+                o[3] = ph.power.x; o[4] = ph.power.y; o[5] = ph.power.z;
+                o[6] = ph.norm.x; o[7] = ph.norm.y; o[8] = ph.norm.z;
+            }
+        Ctx cx;
+        for (int y = 0; y < height; y++)
+            for (int x = 0; x < width; x++) {  // the eye pass of sppm_prepass
+                const uint64_t pix = (uint64_t)y * width + x;
+                cx.rng = Rng(seed ^ SALT_EYE, pix, (uint64_t)it);
+                double u = ((double)x + cx.rng.gen_f64()) / (double)(width - 1);
+                double v = ((double)y + cx.rng.gen_f64()) / (double)(height - 1);
+                Ray r = sc.cam.get_ray(u, 1.0 - v, cx.rng);
+                GatherPoint gp = eye_gather_point(sc, r, cfg, cx);
+                double* o = gp7 + 7 * pix;
+                o[0] = gp.valid ? 1. : 0.;
+                o[1] = gp.p.x; o[2] = gp.p.y; o[3] = gp.p.z;
+                o[4] = gp.bsdf.x; o[5] = gp.bsdf.y; o[6] = gp.bsdf.z;
+            }
+    } catch (const UnitZero&) {
+        return ORC_ERR_UNIT_ZERO;
+    }
+    return ORC_OK;
+}
+
 void orc_tonemap_u8(const double* rgb, size_t n_channels, uint8_t* out) {
     for (size_t i = 0; i < n_channels; i++) out[i] = tonemap_channel(rgb[i]);
 }

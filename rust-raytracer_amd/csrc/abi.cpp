@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "common/grid_shape.h"
 #include "common/rng.h"
 #include "common/schedule.h"
 #include "device/adaptive.h"
@@ -70,6 +71,7 @@ namespace rtamd {
 void debug_area_eval_device(const rt_scene& s, int mode, size_t n, const double* in, double* out) __attribute__((weak));  // (likewise)
 void debug_shade_device(const rt_scene& s, size_t n, const double* in, const uint64_t* keys, double* out) __attribute__((weak));
 void debug_light_eval_device(const rt_scene& s, int mode, size_t n, const double* in, const uint64_t* keys, double* out) __attribute__((weak));
+bool debug_sppm_gather_device(rt_debug_sppm_gather& io) __attribute__((weak));
 }  // namespace rtamd
 static bool env_debug_linked() { return &rtamd::debug_env_table_device != nullptr && &rtamd::debug_env_eval_device != nullptr; }
 
@@ -1043,6 +1045,39 @@ int rt_debug_light_pdf_device(const rt_scene* s, int device, size_t n, const dou
         REQUIRE(n > 0 && rays_host && pdf_host, "bad argument");
         object_lights_only(*s);
     }, [&] { debug_light_eval_device(*s, 1, n, rays_host, nullptr, pdf_host); });
+}
+// the SPPM gather diagnostic checks its arguments on the host, before it asks for a device (as shade_debug does)
+int rt_debug_sppm_gather_device(int device, rt_debug_sppm_gather* io) {
+    bool unit_zero = false;
+    const int rc = guard([&] {
+        REQUIRE(io, "null argument");
+        REQUIRE(io->points && io->stats && io->estimates && (io->global || io->n_global == 0) && (io->caustic || io->n_caustic == 0), "null pointer");
+        REQUIRE(io->m > 0 && io->m <= 0x7FFFFFFFull, "m must be 1 .. 2^31 - 1");
+        REQUIRE(io->n_global <= 0x40000000ull && io->n_caustic <= 0x40000000ull, "photon map too large");
+        REQUIRE(io->k_global >= 1 && io->k_caustic >= 1, "k must be >= 1");
+        REQUIRE(io->alpha > 0., "alpha must be > 0");
+        REQUIRE(io->shift >= 0 && io->shift <= 60, "S must be 0 .. 60");
+        const int n_dev = device_count();
+        if (n_dev < 1 || &rtamd::debug_sppm_gather_device == nullptr) throw RtError(RT_ERR_NO_DEVICE, "no HIP device");
+        REQUIRE(device >= 0 && device < n_dev, "no such device");
+        DeviceScope dev_scope(device);
+        unit_zero = debug_sppm_gather_device(*io);
+        return (int)RT_OK;
+    });
+    if (rc == RT_OK && unit_zero) {
+        g_err = "unitizing zero vector (device, SPPM gather)";
+        return RT_ERR_UNIT_ZERO;
+    }
+    return rc;
+}
+int rt_debug_grid_shape(const double* lo3, const double* hi3, uint64_t n, double* cell, int32_t* dim3) {
+    return guard([&] {
+        REQUIRE(lo3 && hi3 && cell && dim3, "null argument");
+        int dim[3];
+        if (!grid_shape(lo3, hi3, (size_t)n, cell, dim)) throw RtError(RT_ERR_UNSUPPORTED, "the bounding box is not finite");
+        for (int a = 0; a < 3; a++) dim3[a] = dim[a];
+        return (int)RT_OK;
+    });
 }
 int rt_debug_schedule(int64_t tiles_owned, int n_waves, int s_begin, int s_end, int sub_spp, int job_units, int* out25) {
     int rounds = 0;

@@ -56,6 +56,9 @@ void debug_area_eval_device(const rt_scene& s, int mode, size_t n, const double*
 // shade: in n*17, keys n*3, out n*22; light eval mode 0: n draws (in n*4 {o, light}, keys n*3 -> out n*6), mode 1: n*6 {o, d} -> out n * n_lights
 void debug_shade_device(const rt_scene& s, size_t n, const double* in, const uint64_t* keys, double* out);
 void debug_light_eval_device(const rt_scene& s, int mode, size_t n, const double* in, const uint64_t* keys, double* out);
+// SPPM gather diagnostics on the current device (device/sppm_debug.inc; the arguments were checked by the caller): one iteration of
+// render_sppm's grid build, sort, gather and estimate on the caller's photon maps and gather points.  true: a unit() met a zero vector
+bool debug_sppm_gather_device(rt_debug_sppm_gather& io);
 int device_count();
 // thin HIP wrappers so abi.cpp stays free of HIP headers
 void* dev_alloc(size_t n);

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../common/flat.h"
+#include "../common/grid_shape.h"
 #include "../common/detlog.h"
 #include "../common/detsin.h"
 #include "../common/detuv.h"
@@ -4853,29 +4854,16 @@ void build_grid(Grid& g, const PhotonBuf& pb, unsigned int n, hipStream_t stream
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(keys, g.mnmx.p, sizeof(keys), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
-    double lo[3], hi[3], ext[3];
+    double lo[3], hi[3], cell = 1.;
     for (int a = 0; a < 3; a++) {
         lo[a] = f64_unkey(keys[a]);
         hi[a] = f64_unkey(keys[3 + a]);
-        ext[a] = hi[a] - lo[a];
-        if (!(ext[a] >= 0.) || !std::isfinite(ext[a])) throw RtError(RT_ERR_UNSUPPORTED, "photon positions are not finite");
     }
-    // photons lie on surfaces: aim at ~4 per occupied cell  ->  cell ~ 2 * sqrt(area / n)
-    double area = 2. * (ext[0] * ext[1] + ext[1] * ext[2] + ext[2] * ext[0]);
-    double longest = std::fmax(ext[0], std::fmax(ext[1], ext[2]));
-    double cell = 2. * std::sqrt(area / (double)n);
-    if (!(cell > 0.)) cell = longest > 0. ? longest : 1.;
-    const double min_cell = longest / 160.;  // at most 160 cells per axis
-    if (cell < min_cell) cell = min_cell;
-    if (!(cell > 0.)) cell = 1.;
+    if (!grid_shape(lo, hi, n, &cell, g.k.dim)) throw RtError(RT_ERR_UNSUPPORTED, "photon positions are not finite");  // (common/grid_shape.h)
     size_t cells = 1;
     for (int a = 0; a < 3; a++) {
-        int d = (int)std::floor(ext[a] / cell) + 1;
-        if (d < 1) d = 1;
-        if (d > 161) d = 161;
-        g.k.dim[a] = d;
         g.k.lo[a] = lo[a];
-        cells *= (size_t)d;
+        cells *= (size_t)g.k.dim[a];
     }
     g.k.cell = cell;
     g.k.inv_cell = 1. / cell;
@@ -5304,3 +5292,5 @@ void debug_hit_device(const rt_scene& s, int kernel, size_t n, const double* ray
 #include "region.inc"
 // rt_debug_shade_device, rt_debug_light_sample_device, rt_debug_light_pdf_device: shading and object lights on explicit inputs
 #include "shade_debug.inc"
+// rt_debug_sppm_gather_device: one iteration of the SPPM gather on explicit photons and gather points
+#include "sppm_debug.inc"

@@ -67,6 +67,20 @@ class rt_sppm_config(C.Structure):
                 ("max_bounces", C.c_int32), ("reserved", C.c_int32), ("alpha", C.c_double)]
 
 
+class rt_debug_grid(C.Structure):
+    _fields_ = [("lo", C.c_double * 3), ("cell", C.c_double), ("dim", C.c_int32 * 3), ("reserved", C.c_int32),
+                ("cell_start", C.POINTER(C.c_uint32)), ("index", C.POINTER(C.c_uint32)), ("cell_start_capacity", C.c_uint64),
+                ("index_capacity", C.c_uint64)]
+
+
+class rt_debug_sppm_gather(C.Structure):
+    _fields_ = [("n_global", C.c_uint64), ("n_caustic", C.c_uint64), ("m", C.c_uint64), ("global_", C.POINTER(C.c_double)),
+                ("caustic", C.POINTER(C.c_double)), ("points", C.POINTER(C.c_double)), ("stats", C.POINTER(C.c_double)),
+                ("estimates", C.POINTER(C.c_double)), ("k_global", C.c_int32), ("k_caustic", C.c_int32), ("alpha", C.c_double),
+                ("shift", C.c_int32), ("reserved", C.c_int32), ("n_emitted", C.c_double), ("grid_global", rt_debug_grid),
+                ("grid_caustic", rt_debug_grid)]
+
+
 class rt_denoise_config(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("normal_power_log2", C.c_int32), ("sigma_depth", C.c_double), ("sigma_albedo", C.c_double),
                 ("sigma_luma", C.c_double), ("eps", C.c_double), ("guides", C.c_int32), ("reserved", C.c_int32 * 5)]
@@ -236,6 +250,8 @@ _SIGS = [
     ("rt_debug_shade_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, C.POINTER(C.c_uint64), _dp]),
     ("rt_debug_light_sample_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, C.POINTER(C.c_uint64), _dp]),
     ("rt_debug_light_pdf_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, _dp]),
+    ("rt_debug_sppm_gather_device", C.c_int, [C.c_int, C.POINTER(rt_debug_sppm_gather)]),
+    ("rt_debug_grid_shape", C.c_int, [_dp, _dp, C.c_uint64, _dp, C.POINTER(C.c_int32)]),
 ]
 ABI_SYMBOLS = [s[0] for s in _SIGS]
 
@@ -903,6 +919,51 @@ def debug_schedule(tiles_owned, n_waves, s_begin, s_end, sub_spp=8, job_units=2)
     rows = [tuple(out[5 * i:5 * i + 5]) for i in range(5)]
     n = next(i for i, r in enumerate(rows) if r[3] == 0)
     return rounds, rows[:n + 1]
+
+
+def debug_grid_shape(lo, hi, n):
+    """rt_debug_grid_shape: (cell, (dim0, dim1, dim2)) of the uniform grid build_grid lays over n photons with the bounding box [lo, hi].
+    Host logic only."""
+    cell = C.c_double()
+    dim = (C.c_int32 * 3)()
+    _chk(lib().rt_debug_grid_shape(_arr3(lo), _arr3(hi), int(n), C.byref(cell), dim))
+    return cell.value, tuple(dim)
+
+
+def debug_sppm_gather(global_photons, caustic_photons, points, stats, k_global, k_caustic, alpha, S, n_emitted, device=0, grids=True):
+    """rt_debug_sppm_gather_device: one iteration of the render's SPPM gather.  global_photons [n, 9], caustic_photons [n, 9] =
+    {position, power, norm} (either may be empty), points [m, 7] = {valid, p, bsdf}, stats [m, 10] = the state before the iteration ->
+    dict(stats [m, 10] after it, estimates [m, 6], unit_zero, grid_global, grid_caustic); a grid = dict(lo, cell, dim, cell_start, index),
+    the last two None for an empty map or with grids=False."""
+    maps = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 9) for a in (global_photons, caustic_photons)]
+    pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 7)
+    st = np.array(stats, dtype=np.float64).reshape(-1, 10)
+    if len(st) != len(pts):
+        raise ValueError("stats and points must have the same number of rows")
+    est = np.zeros((len(pts), 6))
+    io = rt_debug_sppm_gather()
+    io.n_global, io.n_caustic, io.m = len(maps[0]), len(maps[1]), len(pts)
+    io.global_ = maps[0].ctypes.data_as(_dp) if len(maps[0]) else None
+    io.caustic = maps[1].ctypes.data_as(_dp) if len(maps[1]) else None
+    io.points, io.stats, io.estimates = pts.ctypes.data_as(_dp), st.ctypes.data_as(_dp), est.ctypes.data_as(_dp)
+    io.k_global, io.k_caustic, io.alpha, io.shift, io.n_emitted = int(k_global), int(k_caustic), float(alpha), int(S), float(n_emitted)
+    tables = []
+    for g, ph in ((io.grid_global, maps[0]), (io.grid_caustic, maps[1])):
+        cs = ix = None
+        if grids and len(ph) and np.isfinite(ph[:, 0:3]).all():
+            _, dim = debug_grid_shape(ph[:, 0:3].min(axis=0), ph[:, 0:3].max(axis=0), len(ph))
+            cs = np.zeros(dim[0] * dim[1] * dim[2] + 1, dtype=np.uint32)
+            ix = np.zeros(len(ph), dtype=np.uint32)
+            g.cell_start, g.cell_start_capacity = cs.ctypes.data_as(C.POINTER(C.c_uint32)), len(cs)
+            g.index, g.index_capacity = ix.ctypes.data_as(C.POINTER(C.c_uint32)), len(ix)
+        tables.append((cs, ix))
+    rc = lib().rt_debug_sppm_gather_device(int(device), C.byref(io))
+    if rc != -2:  # RT_ERR_UNIT_ZERO is a result here: every output is written
+        _chk(rc)
+    out = {"stats": st, "estimates": est, "unit_zero": rc == -2}
+    for name, g, (cs, ix) in (("grid_global", io.grid_global, tables[0]), ("grid_caustic", io.grid_caustic, tables[1])):
+        out[name] = {"lo": np.array(g.lo[:]), "cell": g.cell, "dim": tuple(g.dim[:]), "cell_start": cs, "index": ix}
+    return out
 
 
 def _regions(regions):

@@ -126,6 +126,42 @@ pub struct rt_sppm_config {
     pub alpha: c_double,
 }
 
+/// include/rtamd.h rt_debug_grid: what the uniform grid over one photon map came out as (rt_debug_sppm_gather_device)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct rt_debug_grid {
+    pub lo: [c_double; 3],
+    pub cell: c_double,
+    pub dim: [i32; 3],
+    pub reserved: i32,
+    pub cell_start: *mut u32,
+    pub index: *mut u32,
+    pub cell_start_capacity: u64,
+    pub index_capacity: u64,
+}
+
+/// include/rtamd.h rt_debug_sppm_gather: inputs and outputs of one iteration of the SPPM gather on explicit photon maps
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct rt_debug_sppm_gather {
+    pub n_global: u64,
+    pub n_caustic: u64,
+    pub m: u64,
+    pub global: *const c_double,
+    pub caustic: *const c_double,
+    pub points: *const c_double,
+    pub stats: *mut c_double,
+    pub estimates: *mut c_double,
+    pub k_global: i32,
+    pub k_caustic: i32,
+    pub alpha: c_double,
+    pub shift: i32,
+    pub reserved: i32,
+    pub n_emitted: c_double,
+    pub grid_global: rt_debug_grid,
+    pub grid_caustic: rt_debug_grid,
+}
+
 /// include/rtamd.h rt_denoise_config (rt_default_denoise_config fills it)
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -360,6 +396,8 @@ extern "C" {
     pub fn rt_debug_shade_device(s: *const rt_scene, device: c_int, n: usize, in_host: *const c_double, keys_host: *const u64, out_host: *mut c_double) -> c_int;
     pub fn rt_debug_light_sample_device(s: *const rt_scene, device: c_int, n: usize, in_host: *const c_double, keys_host: *const u64, out_host: *mut c_double) -> c_int;
     pub fn rt_debug_light_pdf_device(s: *const rt_scene, device: c_int, n: usize, rays_host: *const c_double, pdf_host: *mut c_double) -> c_int;
+    pub fn rt_debug_sppm_gather_device(device: c_int, io: *mut rt_debug_sppm_gather) -> c_int;
+    pub fn rt_debug_grid_shape(lo3: *const c_double, hi3: *const c_double, n: u64, cell: *mut c_double, dim3: *mut i32) -> c_int;
 }
 
 // ------------------------------------------------------------------ errors ----

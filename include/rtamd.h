@@ -666,6 +666,27 @@ int rt_debug_area_pdf_device(const rt_scene* s, int device, size_t n, const doub
 int rt_debug_shade_device(const rt_scene* s, int device, size_t n, const double* in_host, const uint64_t* keys_host, double* out_host);
 int rt_debug_light_sample_device(const rt_scene* s, int device, size_t n, const double* in_host, const uint64_t* keys_host, double* out_host);
 int rt_debug_light_pdf_device(const rt_scene* s, int device, size_t n, const double* rays_host, double* pdf_host);
+/* closest hit of explicit rays that carry what a path's segment carries: a ray time and a random stream.  This is the closest-hit
+ * diagnostic for scenes with a ConstantMedium (whose hit draws from the path's stream) or a moving sphere (whose centre depends on the
+ * ray's time), both of which rt_debug_hit_device refuses; any other committed scene is accepted too and then draws nothing.
+ *   rays_host n*7 = {origin[3], direction[3], time}; keys_host n*3 = {seed, pixel, sample} as uint64: row i walks with a fresh stream of
+ *   its own key.  t_max is +inf, as in a render.
+ *   kernel 1: the reference-order program (traverse), 2: the accel walk over the node array in global memory, 3: the same walk over the
+ *   LDS node table "NodeW" with the stored pads (rt_debug_hit_device's mode 3).  The GENERAL / MEDIA variant of each walk is the one a
+ *   render with integrator 0 and a closed shutter launches for the scene (spheres only, general, book 2, nested chains).
+ *   out_host n*14 = rt_debug_hit_device's 12 fields {hit, t, p[3], normal[3], front_face, u, v, leaf index in the reference-order
+ *   program}, all zero on a miss, then "next draw" = the two 32-bit halves {upper, lower} of the stream's next u64 after the walk, as
+ *   exact doubles (as rt_debug_shade_device reports it): its index in rt_debug_rng_host's stream is the number of draws the walk
+ *   consumed -- at most one per ConstantMedium the ray crosses, none in a scene without media.  A medium's hit is materialised as a
+ *   render's: outward normal (1, 0, 0), u = v = 0, leaf index = the medium's closing node.
+ * Checked on the host first: RT_ERR_ARG (a null pointer, n == 0, a kernel outside 1..3, a time that is not finite, a time outside
+ * [time0, time1] of any moving sphere of the scene -- the rule of a render's shutter: their boxes are built for that range),
+ * RT_ERR_NOT_COMMITTED, RT_ERR_UNSUPPORTED (kernel 2 or 3 on a scene without an accel or with t_min < 0; stacks or a NodeW table that
+ * do not fit in LDS) -- then RT_ERR_NO_DEVICE without a GPU.  Returns RT_ERR_UNIT_ZERO where the record of some row took unit() of a vector of
+ * length 0 (as a render of that hit would); every output is then still written, with what the arithmetic gave.  The accel walks are exact for origins within the scene's origin bound, as
+ * in a render (64 times its extent). */
+int rt_debug_walk_device(const rt_scene* s, int device, int kernel, size_t n, const double* rays_host, const uint64_t* keys_host, double t_min,
+                         double* out_host);
 /* SPPM photon gather diagnostics: ONE iteration of the render's own gather on explicit inputs (host buffers throughout) -- the grid
  * build and the sort of both photon maps, gather_kernel (four waves per block, one gather point per wave, caustic map first, then
  * global) and estimate_kernel, launched as rt_render_sppm launches them.  No scene is involved.

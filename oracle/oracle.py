@@ -74,6 +74,7 @@ def lib():
                                   c_double_p, c_double_p, c_u64_p]
     L.orc_hit.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, C.c_double, C.c_double, c_double_p]
     L.orc_hit_batch.argtypes = [C.c_void_p, C.c_int64, c_double_p, C.c_double, C.c_double, C.c_int, c_double_p]
+    L.orc_walk_batch.argtypes = [C.c_void_p, C.c_int64, c_double_p, c_u64_p, C.c_double, C.c_int, c_double_p, C.POINTER(C.c_int64)]
     L.orc_camera_rays.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, c_double_p]
     L.orc_aabb_hit.argtypes = [c_double_p, c_double_p, c_double_p, C.c_double, C.c_double]
     L.orc_scatter.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, C.c_int, C.c_double, C.c_double,
@@ -518,6 +519,20 @@ class Scene:
         self._chk(self.L.orc_hit_batch(self.h, r.shape[0], r.ctypes.data_as(c_double_p), float(t_min), float(t_max), int(n_workers),
                                        out.ctypes.data_as(c_double_p)), "hit_batch")
         return out
+
+    def walk(self, rays7, keys, t_min=1e-3, n_workers=None):
+        """the root's hit for every row of rays7 [n, 7] (orig, dir, Ray.time) with a fresh stream of the row's key (keys uint64 [n, 3] =
+        seed, pixel, sample) and t_max = +inf: -> (hit_batch's records [n, 12], draws [n] = the random numbers each row's walk
+        consumed) -- what the product's World.debug_walk answers."""
+        if n_workers is None:
+            n_workers = os.cpu_count() or 1
+        r = np.ascontiguousarray(rays7, dtype=np.float64).reshape(-1, 7)
+        k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(r.shape[0], 3)
+        out = np.zeros((r.shape[0], 12), dtype=np.float64)
+        draws = np.zeros(r.shape[0], dtype=np.int64)
+        self._chk(self.L.orc_walk_batch(self.h, r.shape[0], r.ctypes.data_as(c_double_p), k.ctypes.data_as(c_u64_p), float(t_min),
+                                        int(n_workers), out.ctypes.data_as(c_double_p), draws.ctypes.data_as(C.POINTER(C.c_int64))), "walk")
+        return out, draws
 
     def scatter(self, mat, ray_o, ray_d, p, normal, front_face, uv=(0.0, 0.0), key=(1, 0, 0)):
         out = (C.c_double * 14)()

@@ -2571,6 +2571,46 @@ int orc_hit_rng(void* s, int o, const double* orig, const double* dir, double t_
     }
     return ORC_OK;
 }
+// orc_hit_rng of the root for n rays that carry their own time and stream (rays n*7 = orig, dir, Ray.time; keys n*3 = seed, pixel,
+// sample; t_max = +inf as in a render), threaded like orc_hit_batch: out n*12 = orc_hit's record per ray (all zero on a miss),
+// draws[i] = the numbers row i consumed.  What the product's rt_debug_walk_device answers (include/rtamd.h).
+int orc_walk_batch(void* s, int64_t n, const double* rays7, const uint64_t* keys3, double t_min, int n_workers, double* out, int64_t* draws) {
+    Scene& sc = *(Scene*)s;
+    if (!sc.root || n < 0) return ORC_ERR_ARG;
+    if (n_workers < 1) n_workers = 1;
+    std::atomic<int> err{ORC_OK};
+    auto worker = [&](int64_t begin, int64_t end) {
+        for (int64_t i = begin; i < end; i++) {
+            double* q = out + 12 * i;
+            for (int k = 0; k < 12; k++) q[k] = 0.;
+            const double* ro = rays7 + 7 * i;
+            Ctx cx;
+            cx.rng = Rng(keys3[3 * i], keys3[3 * i + 1], keys3[3 * i + 2]);
+            HitRecord rec;
+            Ray r{Vec3(ro[0], ro[1], ro[2]), Vec3(ro[3], ro[4], ro[5]), ro[6]};
+            bool ok;
+            try {
+                ok = sc.root->hit(r, t_min, INF, rec, cx);
+            } catch (const UnitZero&) {
+                err.store(ORC_ERR_UNIT_ZERO);
+                return;
+            }
+            draws[i] = (int64_t)cx.rng.draws;
+            if (!ok) continue;
+            q[0] = 1.;
+            q[1] = rec.t;
+            q[2] = rec.p.x; q[3] = rec.p.y; q[4] = rec.p.z;
+            q[5] = rec.normal.x; q[6] = rec.normal.y; q[7] = rec.normal.z;
+            q[8] = rec.front_face ? 1. : 0.;
+            q[9] = rec.u; q[10] = rec.v;
+            q[11] = (double)rec.prim_id;
+        }
+    };
+    std::vector<std::thread> th;
+    for (int w = 0; w < n_workers; w++) th.emplace_back(worker, n * w / n_workers, n * (w + 1) / n_workers);
+    for (auto& t : th) t.join();
+    return err.load();
+}
 // AABB::hit on an explicit box (KAT helper)
 int orc_aabb_hit(const double* box6, const double* orig, const double* dir, double t_min, double t_max) {
     AABB b{Vec3(box6[0], box6[1], box6[2]), Vec3(box6[3], box6[4], box6[5])};

@@ -72,6 +72,7 @@ void debug_area_eval_device(const rt_scene& s, int mode, size_t n, const double*
 void debug_shade_device(const rt_scene& s, size_t n, const double* in, const uint64_t* keys, double* out) __attribute__((weak));
 void debug_light_eval_device(const rt_scene& s, int mode, size_t n, const double* in, const uint64_t* keys, double* out) __attribute__((weak));
 bool debug_sppm_gather_device(rt_debug_sppm_gather& io) __attribute__((weak));
+bool debug_walk_device(const rt_scene& s, int kernel, size_t n, const double* rays, const uint64_t* keys, double t_min, double* out) __attribute__((weak));
 }  // namespace rtamd
 static bool env_debug_linked() { return &rtamd::debug_env_table_device != nullptr && &rtamd::debug_env_eval_device != nullptr; }
 
@@ -1045,6 +1046,34 @@ int rt_debug_light_pdf_device(const rt_scene* s, int device, size_t n, const dou
         REQUIRE(n > 0 && rays_host && pdf_host, "bad argument");
         object_lights_only(*s);
     }, [&] { debug_light_eval_device(*s, 1, n, rays_host, nullptr, pdf_host); });
+}
+// the walk diagnostic likewise: every refusal that needs no device comes before RT_ERR_NO_DEVICE
+int rt_debug_walk_device(const rt_scene* s, int device, int kernel, size_t n, const double* rays_host, const uint64_t* keys_host, double t_min, double* out_host) {
+    bool unit_zero = false;
+    const int rc = shade_debug(s, device, &rtamd::debug_walk_device != nullptr, [&] {
+        REQUIRE(n > 0 && rays_host && keys_host && out_host, "bad argument");
+        REQUIRE(kernel >= 1 && kernel <= 3, "rt_debug_walk_device: kernel 1, 2 or 3");
+        if (!s->committed) throw RtError(RT_ERR_NOT_COMMITTED, "scene not committed");
+        const FlatView& v = s->flat.view;
+        if (kernel != 1 && !v.accel_ok) throw RtError(RT_ERR_UNSUPPORTED, "no accel for this scene");
+        if (kernel != 1 && !(t_min >= 0.)) throw RtError(RT_ERR_UNSUPPORTED, "kernels 2 and 3 need t_min >= 0 (box32)");
+        if (debug_walk_lds_bytes(v, kernel) > DEBUG_WALK_LDS_MAX)
+            throw RtError(RT_ERR_UNSUPPORTED, kernel == 3 ? "the NodeW table of this scene does not fit in LDS" : "the walk stacks of this scene do not fit in LDS");
+        const bool moving = (v.kinds_mask & (1u << NK_MSPHERE)) != 0;
+        for (size_t k = 0; k < n; k++) {
+            const double tm = rays_host[7 * k + 6];
+            REQUIRE(std::isfinite(tm), "rt_debug_walk_device: a ray time is not finite");
+            // the shutter rule of a render: a moving sphere's box covers its positions between ITS time0 and time1 only
+            if (moving && !(tm >= s->flat.msph_t0_max && tm <= s->flat.msph_t1_min))
+                throw RtError(RT_ERR_ARG, "rt_debug_walk_device: ray time " + std::to_string(tm) + " lies outside [time0, time1] of a moving sphere ([" +
+                                              std::to_string(s->flat.msph_t0_max) + ", " + std::to_string(s->flat.msph_t1_min) + "] for this scene)");
+        }
+    }, [&] { unit_zero = debug_walk_device(*s, kernel, n, rays_host, keys_host, t_min, out_host); });
+    if (rc == RT_OK && unit_zero) {
+        g_err = "unitizing zero vector (device, walk diagnostic)";
+        return RT_ERR_UNIT_ZERO;
+    }
+    return rc;
 }
 // the SPPM gather diagnostic checks its arguments on the host, before it asks for a device (as shade_debug does)
 int rt_debug_sppm_gather_device(int device, rt_debug_sppm_gather* io) {

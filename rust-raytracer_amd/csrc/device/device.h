@@ -59,6 +59,19 @@ void debug_light_eval_device(const rt_scene& s, int mode, size_t n, const double
 // SPPM gather diagnostics on the current device (device/sppm_debug.inc; the arguments were checked by the caller): one iteration of
 // render_sppm's grid build, sort, gather and estimate on the caller's photon maps and gather points.  true: a unit() met a zero vector
 bool debug_sppm_gather_device(rt_debug_sppm_gather& io);
+// closest-hit diagnostic with a ray time and a random stream per row, on the current device (device/walk_debug.inc; the arguments, the
+// scene, the times and debug_walk_lds_bytes were checked by the caller): rays n*7, keys n*3, out n*14.  true: a unit() met a zero vector
+bool debug_walk_device(const rt_scene& s, int kernel, size_t n, const double* rays, const uint64_t* keys, double t_min, double* out);
+// dynamic LDS of debug_walk_device's launch (blocks of 64): kernel 3's NodeW table (kernels.hip: nodew_bytes), the stack columns of
+// kernels 2 / 3, and 64 ray times where the scene has moving spheres (walk_debug.inc has the map)
+static const size_t DEBUG_WALK_LDS_MAX = 160 * 1024;
+inline size_t debug_walk_lds_bytes(const FlatView& v, int kernel) {
+    size_t b = 0;
+    if (kernel == 3) b += ((size_t)v.n_nodes2 + 128) / 129 * 3 * 4128;
+    if (kernel == 2 || kernel == 3) b += (size_t)v.stack2 * 64 * sizeof(uint32_t);
+    if (v.kinds_mask & (1u << NK_MSPHERE)) b += 64 * sizeof(double) + (kernel == 1 ? 8 : 0);  // (kernel 1: the slots must not start at LDS address 0)
+    return b;
+}
 int device_count();
 // thin HIP wrappers so abi.cpp stays free of HIP headers
 void* dev_alloc(size_t n);

@@ -4283,6 +4283,26 @@ static void pick_coop(int integ, bool mixed, bool wide, pt_coop_fn& fn, pt_coop_
     }
 }
 
+// Which pt_kernel family a scene takes (host only).  moving / book2 / general / nest / media are render_tiles' own predicates: GENERAL is
+// 3 for nested Transforms, else 2 for the book-2 kinds (moving spheres, noise textures, an open shutter), else 1 for any primitive beyond
+// boxes and spheres, else 0; MEDIA where a ConstantMedium exists.  rt_debug_walk_device (walk_debug.inc) picks its walk with the same call.
+struct SceneVariant {
+    bool moving, book2, general, nest, media;
+    int g() const { return nest ? 3 : book2 ? 2 : general ? 1 : 0; }
+};
+static SceneVariant scene_variant(const rt_scene& s, bool open_shutter) {
+    const FlatView& view = s.flat.view;
+    SceneVariant v;
+    v.moving = (view.kinds_mask & (1u << NK_MSPHERE)) != 0;  // D9: the paths' times live in LDS, 8 bytes per lane
+    // D9: moving spheres, noise textures and an open shutter (every sample draws a time) live in their own kernel variants (GENERAL == 2,
+    // kernels 1 / 2, integrator 0): nothing of them is compiled into the others
+    v.book2 = v.moving || view.has_noise != 0 || open_shutter;
+    v.general = (view.kinds_mask & ~((1u << NK_BOX) | (1u << NK_SPHERE))) != 0 || v.book2;
+    v.nest = s.flat.xf_nest != 0u;  // nested Transforms: the GENERAL == 3 variants (common/flat.h "Nested Transforms")
+    v.media = (view.kinds_mask & (1u << NK_MEDIUM_BEGIN)) != 0;  // kernel 1, or kernel 2's MEDIA variant (traverse2_media)
+    return v;
+}
+
 void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& plan_in, double* d_tiles, void* stream_, rt_stats* st) {
     if (!s.committed) throw RtError(RT_ERR_NOT_COMMITTED, "scene not committed");
     const Tuning tun = tuning();  // one snapshot per call
@@ -4299,18 +4319,15 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
     if (st) st->upload_ms = upload_ms;
     // env sampling: the background is a light of integrator 1 -- unless its table sums to zero (a black background)
     const bool env = view.off_env != 0u && env_total != 0ull;
-    const bool moving = (view.kinds_mask & (1u << NK_MSPHERE)) != 0;  // D9: the paths' times live in LDS, 8 bytes per lane
-    // D9: moving spheres, noise textures and an open shutter (every sample draws a time) live in their own kernel variants (GENERAL == 2,
-    // kernels 1 / 2, integrator 0): nothing of them is compiled into the others
-    const bool book2 = moving || view.has_noise != 0 || plan.time1 > plan.time0;
+    const SceneVariant variant = scene_variant(s, plan.time1 > plan.time0);
+    const bool moving = variant.moving, book2 = variant.book2;
     if (moving) {  // a moving sphere's box covers its positions between ITS time0 and time1 only (scene.cpp: add_moving_sphere)
         const double sh0 = plan.time0, sh1 = plan.time1 > plan.time0 ? plan.time1 : plan.time0;
         if (!(sh0 >= s.flat.msph_t0_max && sh1 <= s.flat.msph_t1_min))
             throw RtError(RT_ERR_ARG, "the shutter [time0, time1] = [" + std::to_string(sh0) + ", " + std::to_string(sh1) + "] must lie inside [time0, time1] of every moving sphere ([" +
                                           std::to_string(s.flat.msph_t0_max) + ", " + std::to_string(s.flat.msph_t1_min) + "] for this scene): their boxes are built for that range");
     }
-    const bool general = (view.kinds_mask & ~((1u << NK_BOX) | (1u << NK_SPHERE))) != 0 || book2;
-    const bool nest = s.flat.xf_nest != 0u;  // nested Transforms: the GENERAL == 3 variants (common/flat.h "Nested Transforms")
+    const bool general = variant.general, nest = variant.nest;
     const size_t lds_max = di.lds_max - (moving ? (size_t)PT_BLOCK * sizeof(double) : 0);
     // The accel kernels need the camera inside the region the f32 boxes were padded for (flatten.cpp: origin_limit2) and
     // t_min >= 0 (box32's proof); otherwise kernel 1 (reference order) renders.
@@ -4319,7 +4336,7 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
     const size_t stack2_bytes = walk_stack_bytes(view.stack2, PT_BLOCK);
     const size_t hot1 = (size_t)view.stage_bytes, hot2 = (size_t)(view.stage2_end - view.stage2_begin);
     const bool accel2_usable = view.accel_ok && camera_ok && stack2_bytes <= lds_max;  // per-lane stacks live in LDS
-    const bool media = (view.kinds_mask & (1u << NK_MEDIUM_BEGIN)) != 0;               // kernel 1, or kernel 2's MEDIA variant (traverse2_media)
+    const bool media = variant.media;
     // kernel 5 = kernel 2's BVH with the cooperative instance service (pt_kernel_coop): for scenes with LARGE mesh instances
     // the two walks of kernel 5 never share a stack; the world-space walk includes the instances it enters in the lane (NK_INSTANCE_INLINE)
     const uint32_t stack5 = coop_stack_rows(view);
@@ -5294,3 +5311,5 @@ void debug_hit_device(const rt_scene& s, int kernel, size_t n, const double* ray
 #include "shade_debug.inc"
 // rt_debug_sppm_gather_device: one iteration of the SPPM gather on explicit photons and gather points
 #include "sppm_debug.inc"
+// rt_debug_walk_device: closest hits of explicit rays with a ray time and a random stream (media, moving spheres)
+#include "walk_debug.inc"

@@ -250,6 +250,7 @@ _SIGS = [
     ("rt_debug_shade_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, C.POINTER(C.c_uint64), _dp]),
     ("rt_debug_light_sample_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, C.POINTER(C.c_uint64), _dp]),
     ("rt_debug_light_pdf_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, _dp]),
+    ("rt_debug_walk_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, _dp, C.POINTER(C.c_uint64), C.c_double, _dp]),
     ("rt_debug_sppm_gather_device", C.c_int, [C.c_int, C.POINTER(rt_debug_sppm_gather)]),
     ("rt_debug_grid_shape", C.c_int, [_dp, _dp, C.c_uint64, _dp, C.POINTER(C.c_int32)]),
 ]
@@ -846,6 +847,16 @@ class World:
         out = np.zeros((x.shape[0], 22), dtype=np.float64)
         _chk(self.L.rt_debug_shade_device(self.h, int(device), x.shape[0], x.ctypes.data_as(_dp), k.ctypes.data_as(C.POINTER(C.c_uint64)),
                                           out.ctypes.data_as(_dp)))
+        return out
+
+    def debug_walk(self, rays7, keys, t_min=1e-3, kernel=1, device=0):
+        """rt_debug_walk_device: rays7 [n, 7] = origin, direction, ray time; keys uint64 [n, 3] = seed, pixel, sample -> [n, 14] =
+        debug_hit's 12 fields, then the next draw's two 32-bit halves.  The closest-hit query for scenes with media or moving spheres."""
+        r = np.ascontiguousarray(rays7, dtype=np.float64).reshape(-1, 7)
+        k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(r.shape[0], 3)
+        out = np.zeros((r.shape[0], 14), dtype=np.float64)
+        _chk(self.L.rt_debug_walk_device(self.h, int(device), int(kernel), r.shape[0], r.ctypes.data_as(_dp), k.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                         float(t_min), out.ctypes.data_as(_dp)))
         return out
 
     def debug_light_sample(self, o_light, keys, device=0):

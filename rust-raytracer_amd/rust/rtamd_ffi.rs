@@ -396,6 +396,7 @@ extern "C" {
     pub fn rt_debug_shade_device(s: *const rt_scene, device: c_int, n: usize, in_host: *const c_double, keys_host: *const u64, out_host: *mut c_double) -> c_int;
     pub fn rt_debug_light_sample_device(s: *const rt_scene, device: c_int, n: usize, in_host: *const c_double, keys_host: *const u64, out_host: *mut c_double) -> c_int;
     pub fn rt_debug_light_pdf_device(s: *const rt_scene, device: c_int, n: usize, rays_host: *const c_double, pdf_host: *mut c_double) -> c_int;
+    pub fn rt_debug_walk_device(s: *const rt_scene, device: c_int, kernel: c_int, n: usize, rays_host: *const c_double, keys_host: *const u64, t_min: c_double, out_host: *mut c_double) -> c_int;
     pub fn rt_debug_sppm_gather_device(device: c_int, io: *mut rt_debug_sppm_gather) -> c_int;
     pub fn rt_debug_grid_shape(lo3: *const c_double, hi3: *const c_double, n: u64, cell: *mut c_double, dim3: *mut i32) -> c_int;
 }

@@ -733,6 +733,50 @@ typedef struct rt_debug_sppm_gather {
     rt_debug_grid grid_global, grid_caustic;
 } rt_debug_sppm_gather;
 int rt_debug_sppm_gather_device(int device, rt_debug_sppm_gather* io);
+/* SPPM trace diagnostics: the photon pass and the eye pass of ONE iteration of rt_render_sppm's pre-pass on a committed scene, and what
+ * they wrote (host buffers throughout).  The entry goes through the code rt_render_sppm itself runs for the light table (cumulative
+ * weights, flux, scale, S), for the choice of the compiled photon / eye kernel and its launch shape, for the launches and for the
+ * grow-and-retry of the photon stores; only the two-stream overlap of iterations is the render's alone.  The gather is not run
+ * (rt_debug_sppm_gather_device takes what this entry returns).
+ *   IN   width, height (each >= 2: the eye pass divides by width - 1 and height - 1), seed (rt_params.seed), iteration >= 0 (photon i of
+ *        the pass is photon iteration * photons_per_iter + i of the run, a 64-bit index; the eye stream of a pixel is keyed by the
+ *        iteration), photons_per_iter >= 1, max_bounces >= 1 (rt_sppm_config's).
+ *        capacity_global, capacity_caustic: the photons the two DEVICE stores hold at the first launch, 0 = the render's 8 P + 1024 and
+ *        2 P + 1024; a non-zero rt_tuning.sppm_photon_capacity overrides both, as in a render.  A store that overflows is grown to
+ *        max(photons + 1024, 2 x capacity) and the pass repeated (it is deterministic).
+ *        global, caustic: NULL, or host buffers of global_rows / caustic_rows rows of 9 doubles.  The photon pass runs unless BOTH are
+ *        NULL; a map whose pointer is NULL is counted and not copied.  points: NULL (the eye pass is skipped), or width * height * 7 doubles.
+ *   OUT  the two maps as n * 9 doubles {position[3], power[3], norm[3]} (rt_debug_sppm_gather's layout) in the order the device stored
+ *        them, which is arbitrary; n_global, n_caustic: their photons -- also written where a host buffer holds fewer rows, which is
+ *        RT_ERR_ARG with neither map copied, so that a second call can be sized.
+ *        points: per pixel y * width + x {valid, p[3], bsdf[3]}; the device buffer is zeroed before the eye kernel runs, so a row with
+ *        valid == 0 is all zeros (the kernel writes only its first word there).
+ *        shift: the S of the fixed-point flux accumulators, as the render takes it from the lights.  photon_launches: how often the
+ *        photon pass was launched (1 + the retries; 0 where it was skipped).  variant: bit 0 the accel walk, bit 1 the accel's hot tables
+ *        staged in LDS (photon pass only), bit 2 the chain walk of nested Transforms, bit 3 the MEDIA kernels -- photon_kernel<ACCEL, LDS>,
+ *        photon_kernel_nest, eye_kernel<ACCEL>, eye_kernel_nest and their _media twins.
+ * Checked on the host first: RT_ERR_ARG (a null argument, a size, count, cap or iteration out of range, rows without a buffer),
+ * then what rt_render_sppm refuses, with its codes: RT_ERR_NOT_COMMITTED, RT_ERR_UNSUPPORTED (a background, area lights, moving spheres, noise
+ * textures, a light inside a ConstantMedium), RT_ERR_ARG (no lights) -- then RT_ERR_NO_DEVICE without a GPU.  Honours rt_tuning.no_lds.
+ * Returns RT_ERR_UNIT_ZERO where a unit() of either pass met a zero vector (as rt_render_sppm does); every output is then still written,
+ * with what the arithmetic gave (the photon pass is not repeated after it: a store that overflowed in the same launch is cut at its capacity). */
+typedef struct rt_debug_sppm_trace {
+    int32_t width, height;
+    int32_t iteration, photons_per_iter, max_bounces;
+    int32_t reserved;
+    uint64_t seed;
+    uint32_t capacity_global, capacity_caustic;
+    double* global;
+    double* caustic;
+    uint64_t global_rows, caustic_rows;
+    double* points;
+    uint64_t n_global, n_caustic;     /* OUT */
+    int32_t shift;                    /* OUT: S */
+    int32_t photon_launches;          /* OUT */
+    uint32_t variant;                 /* OUT */
+    uint32_t reserved2;
+} rt_debug_sppm_trace;
+int rt_debug_sppm_trace_device(const rt_scene* s, const rt_camera* cam, int device, rt_debug_sppm_trace* io);
 /* the shape build_grid gives the uniform grid over n photons whose bounding box is [lo3, hi3] (host logic only, no device needed):
  * cell = 2 * sqrt(area / n) of the box's surface area, not below longest extent / 160; dim = floor(extent / cell) + 1 per axis, 1..161.
  * Fallbacks: a box without area (a line or a point) takes cell = its longest extent, a point cell = 1; n == 0 gives cell = 1, dim = 1.

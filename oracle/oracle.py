@@ -461,7 +461,7 @@ class Scene:
     def sppm_iteration(self, width, height, it, photons_per_iter, k_global=100, k_caustic=50, max_bounces=4096, seed=1):
         """the photon maps and gather points of iteration `it` of render_sppm's pre-pass: (global [n, 9], caustic [n, 9], points [W*H, 7], S)
         in sppm_gather's layouts; S = the fixed-point shift the pre-pass takes from the scene's lights"""
-        cfg = (C.c_int * 5)(it + 1, int(photons_per_iter), int(k_global), int(k_caustic), int(max_bounces))
+        cfg = (C.c_int * 5)(min(int(it) + 1, 2 ** 31 - 1), int(photons_per_iter), int(k_global), int(k_caustic), int(max_bounces))  # (the count is not read)
         cap = 64 * int(photons_per_iter) + 1024
         g, c = np.zeros((cap, 9)), np.zeros((cap, 9))
         gp = np.zeros((width * height, 7))

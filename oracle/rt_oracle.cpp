@@ -2759,7 +2759,7 @@ int orc_sppm_iteration(void* s, int width, int height, uint64_t seed, const int*
     try {
         std::vector<Photon> all, cau;
         const uint64_t P = (uint64_t)cfg.photons_per_iter;
-        trace_photons(sc, cfg, seed, (uint64_t)it * P, (uint64_t)(it + 1) * P, all, cau);
+        trace_photons(sc, cfg, seed, (uint64_t)it * P, ((uint64_t)it + 1) * P, all, cau);  // (64-bit: it + 1 may not fit an int)
         counts2[0] = (int64_t)all.size();
         counts2[1] = (int64_t)cau.size();
         if (counts2[0] > capacity || counts2[1] > capacity || (counts2[0] && !glo9) || (counts2[1] && !cau9)) return ORC_ERR_ARG;

@@ -72,6 +72,7 @@ void debug_area_eval_device(const rt_scene& s, int mode, size_t n, const double*
 void debug_shade_device(const rt_scene& s, size_t n, const double* in, const uint64_t* keys, double* out) __attribute__((weak));
 void debug_light_eval_device(const rt_scene& s, int mode, size_t n, const double* in, const uint64_t* keys, double* out) __attribute__((weak));
 bool debug_sppm_gather_device(rt_debug_sppm_gather& io) __attribute__((weak));
+bool debug_sppm_trace_device(const rt_scene& s, const CameraDev& cam, rt_debug_sppm_trace& io) __attribute__((weak));
 bool debug_walk_device(const rt_scene& s, int kernel, size_t n, const double* rays, const uint64_t* keys, double t_min, double* out) __attribute__((weak));
 }  // namespace rtamd
 static bool env_debug_linked() { return &rtamd::debug_env_table_device != nullptr && &rtamd::debug_env_eval_device != nullptr; }
@@ -1095,6 +1096,32 @@ int rt_debug_sppm_gather_device(int device, rt_debug_sppm_gather* io) {
     });
     if (rc == RT_OK && unit_zero) {
         g_err = "unitizing zero vector (device, SPPM gather)";
+        return RT_ERR_UNIT_ZERO;
+    }
+    return rc;
+}
+// the SPPM trace diagnostic likewise: its own argument checks, then the refusals of a render (sppm_refuse, device.h), then the device
+int rt_debug_sppm_trace_device(const rt_scene* s, const rt_camera* cam, int device, rt_debug_sppm_trace* io) {
+    bool unit_zero = false;
+    const int rc = guard([&] {
+        REQUIRE(s && cam && io, "null argument");
+        REQUIRE(io->width >= 2 && io->height >= 2, "width and height must be >= 2 (the eye pass divides by width - 1 and height - 1)");
+        REQUIRE((uint64_t)io->width * (uint64_t)io->height <= 0x7FFFFFFFull, "too many pixels");
+        REQUIRE(io->iteration >= 0, "iteration must be >= 0");
+        REQUIRE(io->photons_per_iter >= 1 && io->max_bounces >= 1, "photons_per_iter and max_bounces must be >= 1");
+        REQUIRE(io->capacity_global <= 0x40000000u && io->capacity_caustic <= 0x40000000u, "capacity above 2^30 photons");
+        REQUIRE((io->global || io->global_rows == 0) && (io->caustic || io->caustic_rows == 0), "rows without a buffer");
+        sppm_refuse(*s, false);
+        const int n_dev = device_count();
+        if (n_dev < 1 || &rtamd::debug_sppm_trace_device == nullptr) throw RtError(RT_ERR_NO_DEVICE, "no HIP device");
+        REQUIRE(device >= 0 && device < n_dev, "no such device");
+        DeviceScope dev_scope(device);
+        const CameraDev cd = make_camera(*cam);
+        unit_zero = debug_sppm_trace_device(*s, cd, *io);
+        return (int)RT_OK;
+    });
+    if (rc == RT_OK && unit_zero) {
+        g_err = "unitizing zero vector (device, SPPM trace)";
         return RT_ERR_UNIT_ZERO;
     }
     return rc;

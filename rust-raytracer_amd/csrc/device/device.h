@@ -59,6 +59,24 @@ void debug_light_eval_device(const rt_scene& s, int mode, size_t n, const double
 // SPPM gather diagnostics on the current device (device/sppm_debug.inc; the arguments were checked by the caller): one iteration of
 // render_sppm's grid build, sort, gather and estimate on the caller's photon maps and gather points.  true: a unit() met a zero vector
 bool debug_sppm_gather_device(rt_debug_sppm_gather& io);
+// what the SPPM passes do not render, decided from the committed scene alone (no device): render_sppm and rt_debug_sppm_trace_device
+// refuse with these codes and messages, in this order
+inline void sppm_refuse(const rt_scene& s, bool open_shutter) {
+    if (!s.committed) throw RtError(RT_ERR_NOT_COMMITTED, "scene not committed");
+    if (s.flat.view.off_bg != 0u)
+        throw RtError(RT_ERR_UNSUPPORTED, "SPPM does not render a scene with a background: the photon pass has no environment emitter (DESIGN.md s4g)");
+    if (s.flat.view.off_area != 0u)
+        throw RtError(RT_ERR_UNSUPPORTED, "SPPM does not render a scene with area lights: the photon pass has no emitter for them (DESIGN.md s4i)");
+    if (s.lights.empty()) throw RtError(RT_ERR_ARG, "SPPM needs lights (rt_scene_set_lights)");
+    if (s.flat.view.n_msph != 0u || s.flat.view.has_noise != 0u || open_shutter)
+        throw RtError(RT_ERR_UNSUPPORTED, "the photon passes have no notion of time: the book-2 extensions (moving spheres, noise textures, an open shutter) render with integrator 0");
+    if ((s.flat.view.kinds_mask & (1u << NK_MEDIUM_BEGIN)) != 0 && s.flat.light_in_medium)
+        throw RtError(RT_ERR_UNSUPPORTED, "a light that lies inside the boundary of a ConstantMedium is not supported by the photon pass");
+}
+// SPPM trace diagnostics on the current device (device/sppm_trace_debug.inc; the arguments and sppm_refuse were checked by the caller): the
+// photon pass and the eye pass of ONE iteration, through render_sppm's own light table, variant choice, launches and grow-and-retry.
+// true: a unit() met a zero vector
+bool debug_sppm_trace_device(const rt_scene& s, const CameraDev& cam, rt_debug_sppm_trace& io);
 // closest-hit diagnostic with a ray time and a random stream per row, on the current device (device/walk_debug.inc; the arguments, the
 // scene, the times and debug_walk_lds_bytes were checked by the caller): rays n*7, keys n*3, out n*14.  true: a unit() met a zero vector
 bool debug_walk_device(const rt_scene& s, int kernel, size_t n, const double* rays, const uint64_t* keys, double t_min, double* out);

@@ -4933,78 +4933,172 @@ struct PhotonStore {
         HIP_CHECK(hipGetLastError());
     }
 };
+
+// ---- what render_sppm and the trace diagnostic (sppm_trace_debug.inc) share: the light table, the choice of the kernel variants, the
+// launches of the photon and eye passes and the grow-and-retry of the photon stores ----
+// AllLights::new (light.rs:202-217) + the fixed-point shift of the flux accumulators
+struct SppmLights {
+    DevBuf d_flux, d_scale, d_cum;
+    LightK lk{};
+    int S = 40;
+    void prepare(const rt_scene& s) {
+        const int nl = (int)s.lights.size();
+        std::vector<double> h_flux(3 * nl), h_scale(nl), h_cum(nl), lp(nl);
+        double tot = 0., maxp = 0.;
+        for (int i = 0; i < nl; i++) {
+            const ObjectRec& o = s.objects[s.lights[i]];
+            for (int c = 0; c < 3; c++) h_flux[3 * i + c] = o.light_flux[c];
+            h_scale[i] = o.light_scale;
+            double px = o.light_flux[0] * o.light_scale, py = o.light_flux[1] * o.light_scale, pz = o.light_flux[2] * o.light_scale;
+            lp[i] = std::sqrt(px * px + py * py + pz * pz);
+            tot = tot + lp[i];
+            maxp = std::fmax(maxp, std::fmax(std::fabs(px), std::fmax(std::fabs(py), std::fabs(pz))));
+        }
+        double total = 0.;
+        for (int i = 0; i < nl; i++) {
+            total = total + lp[i] / tot;
+            h_cum[i] = total;
+        }
+        S = 40;
+        if (maxp > 0. && std::isfinite(maxp)) {
+            int e;
+            std::frexp(maxp, &e);
+            S = 40 - e;
+            S = S < 0 ? 0 : (S > 60 ? 60 : S);
+        }
+        d_flux.alloc(h_flux.size() * 8); d_scale.alloc(nl * 8); d_cum.alloc(nl * 8);
+        HIP_CHECK(hipMemcpy(d_flux.p, h_flux.data(), h_flux.size() * 8, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_scale.p, h_scale.data(), nl * 8, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_cum.p, h_cum.data(), nl * 8, hipMemcpyHostToDevice));
+        lk = LightK{nl, total, (const double*)d_cum.p, (const double*)d_flux.p, (const double*)d_scale.p};
+    }
+};
+// which of the compiled photon / eye kernels a scene, a camera and a device get, and their launch shapes
+struct SppmLaunch {
+    FlatView view;
+    bool accel = false, photon_lds = false, nest = false, media = false;
+    size_t smem = 0, smem_photon = 0;
+    int pblocks = 1, eblocks = 1;
+    // rt_debug_sppm_trace's variant word
+    unsigned int word() const { return (accel ? 1u : 0u) | (photon_lds ? 2u : 0u) | (nest ? 4u : 0u) | (media ? 8u : 0u); }
+};
+SppmLaunch sppm_choose(const rt_scene& s, const CameraDev& cam, const Tuning& tun, int photons_per_iter, size_t npix) {
+    SppmLaunch L;
+    // ConstantMedium (D8): a volume event is a pass-through interaction in all three passes; the photon and eye walks take their path's stream
+    L.media = (s.flat.view.kinds_mask & (1u << NK_MEDIUM_BEGIN)) != 0;
+    int dev = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    const DevInfo& di = dev_info(dev);
+    L.view = s.flat.view;
+    FlatView& view = L.view;
+    view.base = device_blob(s, dev);
+    double cam_abs = std::fmax(std::fmax(std::fabs(cam.origin[0]), std::fabs(cam.origin[1])), std::fabs(cam.origin[2])) + std::fabs(cam.lens_radius);
+    L.accel = view.accel_ok && cam_abs <= view.origin_limit2 && std::isfinite(cam_abs) && walk_stack_bytes(view.stack2, 256) <= di.lds_max;
+    L.nest = s.flat.xf_nest != 0u;  // nested Transforms: the photon / eye passes take kernel 1's chain walk (their accel walks have none)
+    if (L.nest) L.accel = false;
+    // per-lane accel stacks: stack2 entries, as render_tiles gives kernel 2 and its MEDIA variants (traverse2_media's walks take the
+    // column one after another; a boundary's reference-order walk uses none)
+    L.smem = L.accel ? walk_stack_bytes(view.stack2, 256) : 0;
+    // photon pass: stage the accel's hot tables into LDS when at least two 256-thread blocks still fit on a CU
+    const size_t hot2 = (size_t)(view.stage2_end - view.stage2_begin);
+    L.smem_photon = hot2 + L.smem;
+    L.photon_lds = L.accel && hot2 > 0 && 2 * L.smem_photon <= di.lds_max && !tun.no_lds;
+    if (L.photon_lds && L.smem_photon > 48 * 1024)
+        HIP_CHECK(hipFuncSetAttribute(L.media ? (const void*)photon_kernel_media<true, true> : (const void*)photon_kernel<true, true>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.smem_photon));
+    // persistent photon waves: enough 256-thread blocks to fill every CU at 4 waves per SIMD, never more waves than chunks
+    L.pblocks = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)photons_per_iter + 4 * PHOTON_CHUNK - 1) / (4 * PHOTON_CHUNK), (int64_t)di.cus * 4));
+    L.eblocks = (int)std::min<size_t>((npix + 255) / 256, (size_t)di.cus * 8);
+    return L;
+}
+// the capacities the two photon stores start with; 0 = the default for P photons per iteration
+void sppm_capacities(int photons_per_iter, const Tuning& tun, unsigned int& cap_g, unsigned int& cap_c) {
+    if (cap_g == 0u) cap_g = (unsigned int)std::min<uint64_t>((uint64_t)photons_per_iter * 8 + 1024, 0x7FFFFFFFu);
+    if (cap_c == 0u) cap_c = (unsigned int)std::min<uint64_t>((uint64_t)photons_per_iter * 2 + 1024, 0x7FFFFFFFu);
+    if (tun.sppm_cap > 0) cap_g = cap_c = (unsigned int)tun.sppm_cap;  // rt_tuning test hook: forces the grow-and-retry path
+}
+// one photon pass (iteration skp.iteration) on `ps`, into the stores g and c
+void sppm_launch_photons(const SppmLaunch& L, const SppmK& skp, const LightK& lk, PhotonStore& g, PhotonStore& c, unsigned int* d_cursor, int* d_err_p,
+                         hipStream_t ps) {
+    const FlatView& view = L.view;
+    const int pblocks = L.pblocks;
+    const size_t smem = L.smem, smem_photon = L.smem_photon;
+    HIP_CHECK(hipMemsetAsync(g.count.p, 0, 4, ps));
+    HIP_CHECK(hipMemsetAsync(c.count.p, 0, 4, ps));
+    HIP_CHECK(hipMemsetAsync(d_cursor, 0, 4, ps));
+    if (L.media) {  // the same four choices, MEDIA variants
+        if (L.accel && L.photon_lds)
+            hipLaunchKernelGGL((photon_kernel_media<true, true>), dim3(pblocks), dim3(256), smem_photon, ps, view, skp, lk, g.b, c.b, d_cursor, d_err_p);
+        else if (L.accel)
+            hipLaunchKernelGGL((photon_kernel_media<true, false>), dim3(pblocks), dim3(256), smem, ps, view, skp, lk, g.b, c.b, d_cursor, d_err_p);
+        else if (L.nest)
+            hipLaunchKernelGGL(photon_kernel_nest_media, dim3(pblocks), dim3(256), 0, ps, view, skp, lk, g.b, c.b, d_cursor, d_err_p);
+        else
+            hipLaunchKernelGGL((photon_kernel_media<false, false>), dim3(pblocks), dim3(256), 0, ps, view, skp, lk, g.b, c.b, d_cursor, d_err_p);
+    } else if (L.accel && L.photon_lds)
+        hipLaunchKernelGGL((photon_kernel<true, true>), dim3(pblocks), dim3(256), smem_photon, ps, view, skp, lk, g.b, c.b, d_cursor, d_err_p);
+    else if (L.accel)
+        hipLaunchKernelGGL((photon_kernel<true, false>), dim3(pblocks), dim3(256), smem, ps, view, skp, lk, g.b, c.b, d_cursor, d_err_p);
+    else if (L.nest)  // nested Transforms: the chain walk (such scenes have no accel)
+        hipLaunchKernelGGL(photon_kernel_nest, dim3(pblocks), dim3(256), 0, ps, view, skp, lk, g.b, c.b, d_cursor, d_err_p);
+    else
+        hipLaunchKernelGGL((photon_kernel<false, false>), dim3(pblocks), dim3(256), 0, ps, view, skp, lk, g.b, c.b, d_cursor, d_err_p);
+    HIP_CHECK(hipGetLastError());
+}
+// waits for the photon pass on `ps`; it is repeated (relaunch()) with larger stores if one overflowed (the pass is deterministic).
+// -> the photons of both maps; returns how often it relaunched
+template <class F>
+int sppm_collect_photons(PhotonStore& sg, PhotonStore& sc, int* d_err_p, hipStream_t ps, unsigned int& ng, unsigned int& nc, F relaunch) {
+    int relaunched = 0;
+    for (;;) {
+        int h_err = 0;
+        HIP_CHECK(hipMemcpyAsync(&ng, sg.count.p, 4, hipMemcpyDeviceToHost, ps));
+        HIP_CHECK(hipMemcpyAsync(&nc, sc.count.p, 4, hipMemcpyDeviceToHost, ps));
+        HIP_CHECK(hipMemcpyAsync(&h_err, d_err_p, 4, hipMemcpyDeviceToHost, ps));
+        HIP_CHECK(hipStreamSynchronize(ps));
+        if (h_err & 1) throw RtError(RT_ERR_UNIT_ZERO, "unitizing zero vector (device, photon pass)");
+        if (!(h_err & 2)) break;
+        HIP_CHECK(hipMemsetAsync(d_err_p, 0, 4, ps));
+        if (ng > sg.b.cap) {
+            if (sg.b.cap >= 0x40000000u) throw RtError(RT_ERR_UNSUPPORTED, "photon map too large");
+            sg.alloc(std::max(ng + 1024u, sg.b.cap * 2u));
+        }
+        if (nc > sc.b.cap) {
+            if (sc.b.cap >= 0x40000000u) throw RtError(RT_ERR_UNSUPPORTED, "photon map too large");
+            sc.alloc(std::max(nc + 1024u, sc.b.cap * 2u));
+        }
+        relaunch();
+        relaunched++;
+    }
+    return relaunched;
+}
+// the eye pass of iteration sk.iteration on `stream`: gp = width * height x {valid, p, bsdf}
+void sppm_launch_eye(const SppmLaunch& L, const CamK* d_cam, const SppmK& sk, double* d_gp, int* d_err, hipStream_t stream) {
+    const FlatView& view = L.view;
+    const int eblocks = L.eblocks;
+    if (L.media) {
+        if (L.accel) hipLaunchKernelGGL(eye_kernel_media<true>, dim3(eblocks), dim3(256), L.smem, stream, view, d_cam, sk, d_gp, d_err);
+        else if (L.nest) hipLaunchKernelGGL(eye_kernel_nest_media, dim3(eblocks), dim3(256), 0, stream, view, d_cam, sk, d_gp, d_err);
+        else hipLaunchKernelGGL(eye_kernel_media<false>, dim3(eblocks), dim3(256), 0, stream, view, d_cam, sk, d_gp, d_err);
+    } else if (L.accel) hipLaunchKernelGGL(eye_kernel<true>, dim3(eblocks), dim3(256), L.smem, stream, view, d_cam, sk, d_gp, d_err);
+    else if (L.nest) hipLaunchKernelGGL(eye_kernel_nest, dim3(eblocks), dim3(256), 0, stream, view, d_cam, sk, d_gp, d_err);
+    else hipLaunchKernelGGL(eye_kernel<false>, dim3(eblocks), dim3(256), 0, stream, view, d_cam, sk, d_gp, d_err);
+}
 }  // namespace
 
 void render_sppm(const rt_scene& s, const CameraDev& cam, RenderPlan plan, const rt_sppm_config& cfg, double* d_tiles, double* stats_host,
                  void* stream_, rt_stats* st, uint64_t* totals2) {
-    if (!s.committed) throw RtError(RT_ERR_NOT_COMMITTED, "scene not committed");
-    const Tuning tun = tuning();  // one snapshot per call
-    if (s.flat.view.off_bg != 0u)
-        throw RtError(RT_ERR_UNSUPPORTED, "SPPM does not render a scene with a background: the photon pass has no environment emitter (DESIGN.md s4g)");
-    if (s.flat.view.off_area != 0u)
-        throw RtError(RT_ERR_UNSUPPORTED, "SPPM does not render a scene with area lights: the photon pass has no emitter for them (DESIGN.md s4i)");
-    if (s.lights.empty()) throw RtError(RT_ERR_ARG, "SPPM needs lights (rt_scene_set_lights)");
-    if (s.flat.view.n_msph != 0u || s.flat.view.has_noise != 0u || plan.time1 > plan.time0)
-        throw RtError(RT_ERR_UNSUPPORTED, "the photon passes have no notion of time: the book-2 extensions (moving spheres, noise textures, an open shutter) render with integrator 0");
-    // ConstantMedium (D8): a volume event is a pass-through interaction in all three passes; the photon and eye walks take their path's stream
-    const bool media = (s.flat.view.kinds_mask & (1u << NK_MEDIUM_BEGIN)) != 0;
-    if (media && s.flat.light_in_medium)
-        throw RtError(RT_ERR_UNSUPPORTED, "a light that lies inside the boundary of a ConstantMedium is not supported by the photon pass");
+    sppm_refuse(s, plan.time1 > plan.time0);  // (device.h: what the photon passes do not render)
     if (cfg.iterations < 1 || cfg.photons_per_iter < 1 || cfg.k_global < 1 || cfg.k_caustic < 1 || cfg.max_bounces < 1 || !(cfg.alpha > 0.))
         throw RtError(RT_ERR_ARG, "bad rt_sppm_config");
+    const Tuning tun = tuning();  // one snapshot per call
     hipStream_t stream = (hipStream_t)stream_;
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    const DevInfo& di = dev_info(dev);
-    FlatView view = s.flat.view;
-    view.base = device_blob(s, dev);
-    double cam_abs = std::fmax(std::fmax(std::fabs(cam.origin[0]), std::fabs(cam.origin[1])), std::fabs(cam.origin[2])) + std::fabs(cam.lens_radius);
-    bool accel = view.accel_ok && cam_abs <= view.origin_limit2 && std::isfinite(cam_abs) && walk_stack_bytes(view.stack2, 256) <= di.lds_max;
-    const bool nest = s.flat.xf_nest != 0u;  // nested Transforms: the photon / eye passes take kernel 1's chain walk (their accel walks have none)
-    if (nest) accel = false;
-    // per-lane accel stacks: stack2 entries, as render_tiles gives kernel 2 and its MEDIA variants (traverse2_media's walks take the
-    // column one after another; a boundary's reference-order walk uses none)
-    const size_t smem = accel ? walk_stack_bytes(view.stack2, 256) : 0;
-    // photon pass: stage the accel's hot tables into LDS when at least two 256-thread blocks still fit on a CU
-    const size_t hot2 = (size_t)(view.stage2_end - view.stage2_begin);
-    const size_t smem_photon = hot2 + smem;
-    const bool photon_lds = accel && hot2 > 0 && 2 * smem_photon <= di.lds_max && !tun.no_lds;
-    if (photon_lds && smem_photon > 48 * 1024)
-        HIP_CHECK(hipFuncSetAttribute(media ? (const void*)photon_kernel_media<true, true> : (const void*)photon_kernel<true, true>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_photon));
-
-    // AllLights::new (light.rs:202-217) + the fixed-point shift of the flux accumulators
-    const int nl = (int)s.lights.size();
-    std::vector<double> h_flux(3 * nl), h_scale(nl), h_cum(nl), lp(nl);
-    double tot = 0., maxp = 0.;
-    for (int i = 0; i < nl; i++) {
-        const ObjectRec& o = s.objects[s.lights[i]];
-        for (int c = 0; c < 3; c++) h_flux[3 * i + c] = o.light_flux[c];
-        h_scale[i] = o.light_scale;
-        double px = o.light_flux[0] * o.light_scale, py = o.light_flux[1] * o.light_scale, pz = o.light_flux[2] * o.light_scale;
-        lp[i] = std::sqrt(px * px + py * py + pz * pz);
-        tot = tot + lp[i];
-        maxp = std::fmax(maxp, std::fmax(std::fabs(px), std::fmax(std::fabs(py), std::fabs(pz))));
-    }
-    double total = 0.;
-    for (int i = 0; i < nl; i++) {
-        total = total + lp[i] / tot;
-        h_cum[i] = total;
-    }
-    int S = 40;
-    if (maxp > 0. && std::isfinite(maxp)) {
-        int e;
-        std::frexp(maxp, &e);
-        S = 40 - e;
-        S = S < 0 ? 0 : (S > 60 ? 60 : S);
-    }
-    DevBuf d_flux, d_scale, d_cum, d_cam, d_err, d_gp, d_stats, d_est, d_cursor;
+    const SppmLaunch L = sppm_choose(s, cam, tun, cfg.photons_per_iter, (size_t)plan.width * plan.height);
+    SppmLights lights;
+    lights.prepare(s);
+    const int S = lights.S;
+    DevBuf d_cam, d_err, d_gp, d_stats, d_est, d_cursor;
     d_cursor.alloc(4);
-    d_flux.alloc(h_flux.size() * 8); d_scale.alloc(nl * 8); d_cum.alloc(nl * 8);
-    HIP_CHECK(hipMemcpy(d_flux.p, h_flux.data(), h_flux.size() * 8, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_scale.p, h_scale.data(), nl * 8, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_cum.p, h_cum.data(), nl * 8, hipMemcpyHostToDevice));
-    LightK lk{nl, total, (const double*)d_cum.p, (const double*)d_flux.p, (const double*)d_scale.p};
     CamK ck = to_camk(cam);
     d_cam.alloc(sizeof(CamK));
     HIP_CHECK(hipMemcpy(d_cam.p, &ck, sizeof(CamK), hipMemcpyHostToDevice));
@@ -5028,9 +5122,8 @@ void render_sppm(const rt_scene& s, const CameraDev& cam, RenderPlan plan, const
     HIP_CHECK(hipStreamCreateWithFlags(&sp.s, hipStreamNonBlocking));
     Events evs;
     PhotonStore pg[2], pc[2];
-    unsigned int cap_g = (unsigned int)std::min<uint64_t>((uint64_t)cfg.photons_per_iter * 8 + 1024, 0x7FFFFFFFu);
-    unsigned int cap_c = (unsigned int)std::min<uint64_t>((uint64_t)cfg.photons_per_iter * 2 + 1024, 0x7FFFFFFFu);
-    if (tun.sppm_cap > 0) cap_g = cap_c = (unsigned int)tun.sppm_cap;  // rt_tuning test hook: forces the grow-and-retry path
+    unsigned int cap_g = 0, cap_c = 0;
+    sppm_capacities(cfg.photons_per_iter, tun, cap_g, cap_c);
     for (int j = 0; j < 2; j++) {
         pg[j].alloc(cap_g);
         pc[j].alloc(cap_c);
@@ -5045,41 +5138,10 @@ void render_sppm(const rt_scene& s, const CameraDev& cam, RenderPlan plan, const
     sk.seed = plan.seed; sk.S = S; sk.iteration = 0;
     sk.knn_cand = KNN_CAND;
     if (tun.knn_cand >= 0) sk.knn_cand = std::min(KNN_CAND, tun.knn_cand);  // rt_tuning test hook: forces the out-of-LDS selection
-    // persistent photon waves: enough 256-thread blocks to fill every CU at 4 waves per SIMD, never more waves than chunks
-    const int pblocks = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)cfg.photons_per_iter + 4 * PHOTON_CHUNK - 1) / (4 * PHOTON_CHUNK), (int64_t)di.cus * 4));
-    const int eblocks = (int)std::min<size_t>((npix + 255) / 256, (size_t)di.cus * 8);
     auto launch_photons = [&](int it) {  // on stream P, into store it % 2
-        PhotonStore &g = pg[it & 1], &c = pc[it & 1];
         SppmK skp = sk;
         skp.iteration = it;
-        HIP_CHECK(hipMemsetAsync(g.count.p, 0, 4, sp.s));
-        HIP_CHECK(hipMemsetAsync(c.count.p, 0, 4, sp.s));
-        HIP_CHECK(hipMemsetAsync(d_cursor.p, 0, 4, sp.s));
-        if (media) {  // the same four choices, MEDIA variants
-            if (accel && photon_lds)
-                hipLaunchKernelGGL((photon_kernel_media<true, true>), dim3(pblocks), dim3(256), smem_photon, sp.s, view, skp, lk, g.b, c.b,
-                                   (unsigned int*)d_cursor.p, (int*)d_err_p.p);
-            else if (accel)
-                hipLaunchKernelGGL((photon_kernel_media<true, false>), dim3(pblocks), dim3(256), smem, sp.s, view, skp, lk, g.b, c.b,
-                                   (unsigned int*)d_cursor.p, (int*)d_err_p.p);
-            else if (nest)
-                hipLaunchKernelGGL(photon_kernel_nest_media, dim3(pblocks), dim3(256), 0, sp.s, view, skp, lk, g.b, c.b, (unsigned int*)d_cursor.p,
-                                   (int*)d_err_p.p);
-            else
-                hipLaunchKernelGGL((photon_kernel_media<false, false>), dim3(pblocks), dim3(256), 0, sp.s, view, skp, lk, g.b, c.b,
-                                   (unsigned int*)d_cursor.p, (int*)d_err_p.p);
-        } else if (accel && photon_lds)
-            hipLaunchKernelGGL((photon_kernel<true, true>), dim3(pblocks), dim3(256), smem_photon, sp.s, view, skp, lk, g.b, c.b, (unsigned int*)d_cursor.p,
-                               (int*)d_err_p.p);
-        else if (accel)
-            hipLaunchKernelGGL((photon_kernel<true, false>), dim3(pblocks), dim3(256), smem, sp.s, view, skp, lk, g.b, c.b, (unsigned int*)d_cursor.p,
-                               (int*)d_err_p.p);
-        else if (nest)  // nested Transforms: the chain walk (such scenes have no accel)
-            hipLaunchKernelGGL(photon_kernel_nest, dim3(pblocks), dim3(256), 0, sp.s, view, skp, lk, g.b, c.b, (unsigned int*)d_cursor.p, (int*)d_err_p.p);
-        else
-            hipLaunchKernelGGL((photon_kernel<false, false>), dim3(pblocks), dim3(256), 0, sp.s, view, skp, lk, g.b, c.b, (unsigned int*)d_cursor.p,
-                               (int*)d_err_p.p);
-        HIP_CHECK(hipGetLastError());
+        sppm_launch_photons(L, skp, lights.lk, pg[it & 1], pc[it & 1], (unsigned int*)d_cursor.p, (int*)d_err_p.p, sp.s);
     };
     uint64_t tg = 0, tc = 0;
     auto t0 = std::chrono::steady_clock::now();
@@ -5090,25 +5152,7 @@ void render_sppm(const rt_scene& s, const CameraDev& cam, RenderPlan plan, const
         sk.iteration = it;
         PhotonStore &sg = pg[it & 1], &sc = pc[it & 1];
         unsigned int ng = 0, nc = 0;
-        for (;;) {  // wait for the photon pass; it is repeated with larger buffers if one overflowed (the pass is deterministic)
-            int h_err = 0;
-            HIP_CHECK(hipMemcpyAsync(&ng, sg.count.p, 4, hipMemcpyDeviceToHost, sp.s));
-            HIP_CHECK(hipMemcpyAsync(&nc, sc.count.p, 4, hipMemcpyDeviceToHost, sp.s));
-            HIP_CHECK(hipMemcpyAsync(&h_err, d_err_p.p, 4, hipMemcpyDeviceToHost, sp.s));
-            HIP_CHECK(hipStreamSynchronize(sp.s));
-            if (h_err & 1) throw RtError(RT_ERR_UNIT_ZERO, "unitizing zero vector (device, photon pass)");
-            if (!(h_err & 2)) break;
-            HIP_CHECK(hipMemsetAsync(d_err_p.p, 0, 4, sp.s));
-            if (ng > sg.b.cap) {
-                if (sg.b.cap >= 0x40000000u) throw RtError(RT_ERR_UNSUPPORTED, "photon map too large");
-                sg.alloc(std::max(ng + 1024u, sg.b.cap * 2u));
-            }
-            if (nc > sc.b.cap) {
-                if (sc.b.cap >= 0x40000000u) throw RtError(RT_ERR_UNSUPPORTED, "photon map too large");
-                sc.alloc(std::max(nc + 1024u, sc.b.cap * 2u));
-            }
-            launch_photons(it);
-        }
+        sppm_collect_photons(sg, sc, (int*)d_err_p.p, sp.s, ng, nc, [&] { launch_photons(it); });
         tg += ng;
         tc += nc;
         if (it + 1 < cfg.iterations) {  // next photon pass: its store was last read by the gather of iteration it - 1
@@ -5119,13 +5163,7 @@ void render_sppm(const rt_scene& s, const CameraDev& cam, RenderPlan plan, const
         build_grid(gc, sc.b, nc, stream);
         sg.sort_into_grid(gg, ng, stream);
         sc.sort_into_grid(gc, nc, stream);
-        if (media) {
-            if (accel) hipLaunchKernelGGL(eye_kernel_media<true>, dim3(eblocks), dim3(256), smem, stream, view, (const CamK*)d_cam.p, sk, (double*)d_gp.p, (int*)d_err.p);
-            else if (nest) hipLaunchKernelGGL(eye_kernel_nest_media, dim3(eblocks), dim3(256), 0, stream, view, (const CamK*)d_cam.p, sk, (double*)d_gp.p, (int*)d_err.p);
-            else hipLaunchKernelGGL(eye_kernel_media<false>, dim3(eblocks), dim3(256), 0, stream, view, (const CamK*)d_cam.p, sk, (double*)d_gp.p, (int*)d_err.p);
-        } else if (accel) hipLaunchKernelGGL(eye_kernel<true>, dim3(eblocks), dim3(256), smem, stream, view, (const CamK*)d_cam.p, sk, (double*)d_gp.p, (int*)d_err.p);
-        else if (nest) hipLaunchKernelGGL(eye_kernel_nest, dim3(eblocks), dim3(256), 0, stream, view, (const CamK*)d_cam.p, sk, (double*)d_gp.p, (int*)d_err.p);
-        else hipLaunchKernelGGL(eye_kernel<false>, dim3(eblocks), dim3(256), 0, stream, view, (const CamK*)d_cam.p, sk, (double*)d_gp.p, (int*)d_err.p);
+        sppm_launch_eye(L, (const CamK*)d_cam.p, sk, (double*)d_gp.p, (int*)d_err.p, stream);
         const size_t pix_per_block = GATHER_BLOCK / 64;  // one wave per pixel
         hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((npix + pix_per_block - 1) / pix_per_block)), dim3(GATHER_BLOCK), 0, stream, sk,
                            (const double*)d_gp.p, gg.k, sg.s, gc.k, sc.s, (double*)d_stats.p, (int*)d_err.p);
@@ -5311,5 +5349,7 @@ void debug_hit_device(const rt_scene& s, int kernel, size_t n, const double* ray
 #include "shade_debug.inc"
 // rt_debug_sppm_gather_device: one iteration of the SPPM gather on explicit photons and gather points
 #include "sppm_debug.inc"
+// rt_debug_sppm_trace_device: the photon and eye passes of one SPPM iteration on a committed scene, through render_sppm's own host functions
+#include "sppm_trace_debug.inc"
 // rt_debug_walk_device: closest hits of explicit rays with a ray time and a random stream (media, moving spheres)
 #include "walk_debug.inc"

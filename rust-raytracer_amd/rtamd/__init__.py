@@ -81,6 +81,15 @@ class rt_debug_sppm_gather(C.Structure):
                 ("grid_caustic", rt_debug_grid)]
 
 
+class rt_debug_sppm_trace(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("iteration", C.c_int32), ("photons_per_iter", C.c_int32),
+                ("max_bounces", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64), ("capacity_global", C.c_uint32),
+                ("capacity_caustic", C.c_uint32), ("global_", C.POINTER(C.c_double)), ("caustic", C.POINTER(C.c_double)),
+                ("global_rows", C.c_uint64), ("caustic_rows", C.c_uint64), ("points", C.POINTER(C.c_double)), ("n_global", C.c_uint64),
+                ("n_caustic", C.c_uint64), ("shift", C.c_int32), ("photon_launches", C.c_int32), ("variant", C.c_uint32),
+                ("reserved2", C.c_uint32)]
+
+
 class rt_denoise_config(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("normal_power_log2", C.c_int32), ("sigma_depth", C.c_double), ("sigma_albedo", C.c_double),
                 ("sigma_luma", C.c_double), ("eps", C.c_double), ("guides", C.c_int32), ("reserved", C.c_int32 * 5)]
@@ -252,6 +261,7 @@ _SIGS = [
     ("rt_debug_light_pdf_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, _dp]),
     ("rt_debug_walk_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, _dp, C.POINTER(C.c_uint64), C.c_double, _dp]),
     ("rt_debug_sppm_gather_device", C.c_int, [C.c_int, C.POINTER(rt_debug_sppm_gather)]),
+    ("rt_debug_sppm_trace_device", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.c_int, C.POINTER(rt_debug_sppm_trace)]),
     ("rt_debug_grid_shape", C.c_int, [_dp, _dp, C.c_uint64, _dp, C.POINTER(C.c_int32)]),
 ]
 ABI_SYMBOLS = [s[0] for s in _SIGS]
@@ -858,6 +868,39 @@ class World:
         _chk(self.L.rt_debug_walk_device(self.h, int(device), int(kernel), r.shape[0], r.ctypes.data_as(_dp), k.ctypes.data_as(C.POINTER(C.c_uint64)),
                                          float(t_min), out.ctypes.data_as(_dp)))
         return out
+
+    def debug_sppm_trace(self, camera, width, height, iteration=0, photons_per_iter=1, max_bounces=4096, seed=1, capacity=(0, 0), rows=None,
+                         photons=True, points=True, device=0):
+        """rt_debug_sppm_trace_device: the photon pass and the eye pass of iteration `iteration` of render_sppm's pre-pass, through the
+        render's own light table, variant choice, launches and grow-and-retry -> dict(global [n, 9], caustic [n, 9] = {position, power,
+        norm} in the device's order, points [width * height, 7] = {valid, p, bsdf}, n_global, n_caustic, S, photon_launches, variant:
+        bit 0 accel, 1 LDS tables, 2 nested chain walk, 3 MEDIA, unit_zero).  capacity = the device stores' initial photons (global,
+        caustic; 0 = the render's); rows = the host buffers' rows (default: sized by a first call where the defaults are too few);
+        photons=False / points=False skips that pass (its outputs are None)."""
+        io = rt_debug_sppm_trace()
+        io.width, io.height, io.iteration, io.photons_per_iter, io.max_bounces = int(width), int(height), int(iteration), int(photons_per_iter), int(max_bounces)
+        io.seed, io.capacity_global, io.capacity_caustic = int(seed), int(capacity[0]), int(capacity[1])
+        pts = np.zeros((int(width) * int(height), 7)) if points else None
+        if points:
+            io.points = pts.ctypes.data_as(_dp)
+        sized = rows is not None
+        rows = tuple(int(r) for r in rows) if sized else (8 * int(photons_per_iter) + 1024, 2 * int(photons_per_iter) + 1024)
+        while True:
+            g = np.zeros((rows[0], 9)) if photons else None
+            c = np.zeros((rows[1], 9)) if photons else None
+            if photons:
+                io.global_, io.global_rows = g.ctypes.data_as(_dp), rows[0]
+                io.caustic, io.caustic_rows = c.ctypes.data_as(_dp), rows[1]
+            rc = self.L.rt_debug_sppm_trace_device(self.h, C.byref(camera.c), int(device), C.byref(io))
+            if rc == -1 and not sized and photons and (io.n_global > rows[0] or io.n_caustic > rows[1]):  # RT_ERR_ARG with the counts: size a second call
+                rows, sized = (max(rows[0], int(io.n_global)), max(rows[1], int(io.n_caustic))), True
+                continue
+            break
+        if rc != -2:  # RT_ERR_UNIT_ZERO is a result here: every output is written
+            _chk(rc)
+        return {"global": g[:io.n_global].copy() if photons else None, "caustic": c[:io.n_caustic].copy() if photons else None, "points": pts,
+                "n_global": int(io.n_global), "n_caustic": int(io.n_caustic), "S": int(io.shift), "photon_launches": int(io.photon_launches),
+                "variant": int(io.variant), "unit_zero": rc == -2}
 
     def debug_light_sample(self, o_light, keys, device=0):
         """rt_debug_light_sample_device: [n, 4] = origin, object light index; keys uint64 [n, 3] -> [n, 6] = direction, unit-zero status,

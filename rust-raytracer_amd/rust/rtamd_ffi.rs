@@ -162,6 +162,32 @@ pub struct rt_debug_sppm_gather {
     pub grid_caustic: rt_debug_grid,
 }
 
+/// include/rtamd.h rt_debug_sppm_trace: inputs and outputs of the photon and eye passes of one SPPM iteration on a committed scene
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct rt_debug_sppm_trace {
+    pub width: i32,
+    pub height: i32,
+    pub iteration: i32,
+    pub photons_per_iter: i32,
+    pub max_bounces: i32,
+    pub reserved: i32,
+    pub seed: u64,
+    pub capacity_global: u32,
+    pub capacity_caustic: u32,
+    pub global: *mut c_double,
+    pub caustic: *mut c_double,
+    pub global_rows: u64,
+    pub caustic_rows: u64,
+    pub points: *mut c_double,
+    pub n_global: u64,
+    pub n_caustic: u64,
+    pub shift: i32,
+    pub photon_launches: i32,
+    pub variant: u32,
+    pub reserved2: u32,
+}
+
 /// include/rtamd.h rt_denoise_config (rt_default_denoise_config fills it)
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -398,6 +424,7 @@ extern "C" {
     pub fn rt_debug_light_pdf_device(s: *const rt_scene, device: c_int, n: usize, rays_host: *const c_double, pdf_host: *mut c_double) -> c_int;
     pub fn rt_debug_walk_device(s: *const rt_scene, device: c_int, kernel: c_int, n: usize, rays_host: *const c_double, keys_host: *const u64, t_min: c_double, out_host: *mut c_double) -> c_int;
     pub fn rt_debug_sppm_gather_device(device: c_int, io: *mut rt_debug_sppm_gather) -> c_int;
+    pub fn rt_debug_sppm_trace_device(s: *const rt_scene, cam: *const rt_camera, device: c_int, io: *mut rt_debug_sppm_trace) -> c_int;
     pub fn rt_debug_grid_shape(lo3: *const c_double, hi3: *const c_double, n: u64, cell: *mut c_double, dim3: *mut i32) -> c_int;
 }
 

@@ -123,6 +123,7 @@ void debug_rng_floats_device(uint64_t, uint64_t, uint64_t, int, double, double, 
 void debug_math_device(int, size_t, const double*, const double*, double*) { none(); }
 void debug_hit_device(const rt_scene&, int, size_t, const double*, double, double, double*) { none(); }
 bool debug_walk_device(const rt_scene&, int, size_t, const double*, const uint64_t*, double, double*) { none(); return false; }
+bool debug_sppm_trace_device(const rt_scene&, const CameraDev&, rt_debug_sppm_trace&) { none(); return false; }
 int device_count() { return stub_devices(); }
 void* dev_alloc(size_t n) {
     if (stub_devices() < 1) none();

@@ -7,47 +7,11 @@ import numpy as np
 import pytest
 
 import nested_scenes as ns
+from sppm_trace_cases import OB, _cornell_smoke, _cornell_smoke_book, _nested_fog, _pair  # noqa: F401  (both builders; shared with the trace cases)
 
 pytestmark = pytest.mark.gpu
 
 CFG = dict(iterations=3, photons_per_iter=20000, k_global=40, k_caustic=10)
-
-
-class OB:
-    """the oracle's builder has no light constructors: compose them as light.rs:74-86 / 134-146 do, and keep their flux and scale"""
-
-    def __init__(self, o):
-        self.o, self.desc = o, {}
-
-    def __getattr__(self, n):
-        return getattr(self.o, n)
-
-    def XZRectLight(self, xz0, xz1, y, flux, scale):
-        i = self.o.XZRectangle(xz0, xz1, y, self.o.DiffuseLight(self.o.ConstantTexture(flux)))
-        self.desc[i] = (flux, scale)
-        return i
-
-    def SphereDiffuseLight(self, c, r, flux, scale):
-        i = self.o.Sphere(c, r, self.o.DiffuseLight(self.o.ConstantTexture(flux)))
-        self.desc[i] = (flux, scale)
-        return i
-
-
-def _pair(build, cam_args, bvh_seed=1):
-    """build(B) -> (items, lights) on both builders: (rtamd.World, rtamd.Camera, oracle.Scene)"""
-    import oracle
-    import rtamd
-    w = rtamd.World()
-    items, lights = build(w)
-    w.new(items, lights=lights, bvh_seed=bvh_seed)
-    o = oracle.Scene()
-    ob = OB(o)
-    oitems, olights = build(ob)
-    o.World(oitems, bvh_seed)
-    o.set_lights(olights, flux=[ob.desc[i][0] for i in olights], scale=[ob.desc[i][1] for i in olights])
-    o.Camera(*cam_args)
-    f, t, up, vfov, asp, ap, fd = cam_args
-    return w, rtamd.Camera((f, t), up, vfov, asp, ap, fd), o
 
 
 def _assert_same(got, exp, floor):
@@ -59,37 +23,6 @@ def _assert_same(got, exp, floor):
     assert np.array_equal(st, est), "per-pixel SPPM statistics differ in %d pixels" % int((st != est).any(axis=2).sum())
     assert np.array_equal(img, eimg, equal_nan=True), "%d pixels differ" % int(((img != eimg) & ~(np.isnan(img) & np.isnan(eimg))).any(axis=2).sum())
     assert (eimg > 0).any(axis=2).mean() > floor      # not a black (or all-NaN) frame
-
-
-def _cornell_light(B):
-    return B.XZRectLight((213.0, 227.0), (343.0, 332.0), 554.0, (1.0, 1.0, 1.0), 1000000.0)
-
-
-def _cornell_smoke(B):
-    """Cornell walls, the ceiling light, a glass ball and two axis-aligned Cube-bounded media, one dark and one light (world level)"""
-    white, items = ns.walls(B)
-    glass = B.Dielectric(1.5, B.ConstantTexture((1.0, 1.0, 1.0)))
-    dark = B.Isotropic(B.ConstantTexture((0.05, 0.05, 0.05)))
-    light = B.Isotropic(B.ConstantTexture((0.9, 0.9, 0.9)))
-    lt = _cornell_light(B)
-    items += [lt, B.Sphere((400.0, 90.0, 150.0), 70.0, glass),
-              B.ConstantMedium(0.01, B.Cube((130.0, 0.0, 65.0), (295.0, 165.0, 230.0), white), dark),
-              B.ConstantMedium(0.01, B.Cube((265.0, 0.0, 295.0), (430.0, 330.0, 460.0), white), light)]
-    return items, [lt]
-
-
-def _cornell_smoke_book(B):
-    """the book's Cornell smoke: both fog boxes rotated and translated, the media under the Transforms (no accel: reference-order walks)"""
-    white, items = ns.walls(B)
-    dark = B.Isotropic(B.ConstantTexture((0.0, 0.0, 0.0)))
-    light = B.Isotropic(B.ConstantTexture((1.0, 1.0, 1.0)))
-    lt = _cornell_light(B)
-    box1 = B.Transform((0.0, 15.0, 0.0), (1.0, 1.0, 1.0), (265.0, 0.0, 295.0),
-                       B.ConstantMedium(0.01, B.Cube((0.0, 0.0, 0.0), (165.0, 330.0, 165.0), white), dark))
-    box2 = B.Transform((0.0, -18.0, 0.0), (1.0, 1.0, 1.0), (130.0, 0.0, 65.0),
-                       B.ConstantMedium(0.01, B.Cube((0.0, 0.0, 0.0), (165.0, 165.0, 165.0), white), light))
-    items += [lt, box1, box2]
-    return items, [lt]
 
 
 CORNELL_CAM = ns.CORNELL_CAM
@@ -171,20 +104,6 @@ def test_final_scene_reduced_with_a_rect_light():
     got = w.render_sppm(cam, width=48, height=48, spp=4, seed=2, **cfg)
     assert got[3]["kernel_used"] == 2
     _assert_same(got, exp, 0.4)
-
-
-def _nested_fog(B):
-    """nested Transforms (chains of 2 levels) beside and around media: a chain around a cube, a world-level fog whose boundary is a
-    2-level chain of a cube, a fog sphere at world level"""
-    white, items = ns.walls(B)
-    L = [((0.0, 0.0, 10.0), (1.0, 1.3, 1.0), (0.0, 0.0, 0.0)), ((0.0, -20.0, 0.0), (1.0, 1.0, 1.0), (150.0, 0.0, 120.0))]
-    box = ns.nest(B, L, B.Cube((0.0, 0.0, 0.0), (100.0, 100.0, 100.0), white))
-    fog_box = B.ConstantMedium(0.012, ns.nest(B, [((0.0, 30.0, 0.0), (1.0, 1.0, 1.0), (0.0, 0.0, 0.0)), ((5.0, 0.0, 0.0), (1.1, 1.0, 0.9), (330.0, 0.0, 300.0))],
-                                           B.Cube((0.0, 0.0, 0.0), (150.0, 300.0, 150.0), white)), B.Isotropic(B.ConstantTexture((0.8, 0.8, 0.9))))
-    fog_ball = B.ConstantMedium(0.02, B.Sphere((400.0, 90.0, 120.0), 80.0, white), B.Isotropic(B.ConstantTexture((0.3, 0.6, 0.3))))
-    lt = _cornell_light(B)
-    items += [lt, box, fog_box, fog_ball]
-    return items, [lt]
 
 
 @pytest.fixture(scope="module")

@@ -542,6 +542,43 @@ int rt_denoise(const rt_denoise_config* cfg, int32_t width, int32_t height, cons
  * the work has completed on that stream */
 int rt_denoise_device(const rt_denoise_config* cfg, int32_t width, int32_t height, const double* d_rgb, const double* d_variance,
                       const double* d_aov, double* d_out_rgb, double* d_out_variance, void* hip_stream);
+/* The energy-preserving mode: rt_denoise / rt_denoise_device with a SYMMETRIC luminance stop.  Same arguments, same rt_denoise_config;
+ * one term differs.  For a tap q != p
+ *   wl = 1 / (1 + |l_p - l_q| / (sigma_luma * sqrt(v_p + v_q) + eps))
+ * with v_p and v_q the variance input of THIS pass at the centre and at the tap (the caller's on the first pass, the propagated
+ * V / (W W) afterwards).  Everything else is rt_denoise's bit for bit (tap order, h, wn, wz, wa, the product h * wn * wz * wa * wl, W, C,
+ * V += (w w) v_q, the divisions, the ping-pong frames); tests/denoise_sym_ref.py restates it.  The weight p gives q is the weight q gives
+ * p, so a bright pixel among dark ones with v = 0 is neither averaged down by them nor rejected by them, and the frame keeps its mean
+ * (DESIGN.md s4e has the measurements).  variance == NULL is RT_ERR_ARG (without a variance the call would be rt_denoise); all of
+ * rt_denoise's other argument errors are kept. */
+int rt_denoise_sym(const rt_denoise_config* cfg, int32_t width, int32_t height, const double* rgb, const double* variance, const double* aov,
+                   double* out_rgb, double* out_variance);
+int rt_denoise_sym_device(const rt_denoise_config* cfg, int32_t width, int32_t height, const double* d_rgb, const double* d_variance,
+                          const double* d_aov, double* d_out_rgb, double* d_out_variance, void* hip_stream);
+
+/* One call from scene to clean frame, on one device (p->world 1, p->rank 0, p->device picks it); nothing but the requested outputs
+ * leaves the device.  p->spp must be even and >= 2.
+ *   noisy     the samples [0, spp/2) and [spp/2, spp) go into ONE accumulator through the resumable path (rt_render_accumulate_device), so
+ *             out_noisy is rt_render's frame bit for bit;
+ *   variance  with h = spp / 2, S_h the sums after the first range and S the sums after both: per channel A = S_h / h, B = (S - S_h) / h,
+ *             l = (0.2126 r + 0.7152 g) + 0.0722 b, variance = ((l_A - l_B) * (l_A - l_B)) / 4.0 -- of the pixel's mean luminance;
+ *   guides    aov_spp > 0: rt_render_aov with p's seed and t_min; the walk is p->kernel when that is 1 or 2, otherwise automatic.
+ *             aov_spp == 0: no guides, the filter runs on colour and variance alone (scenes with media or moving spheres);
+ *   filter    rt_denoise (luma_mode 0) or rt_denoise_sym (luma_mode 1) over noisy, variance and the guides, under cfg (NULL =
+ *             rt_default_denoise_config).
+ * out_rgb[H][W][3] (required) = the filtered frame; out_noisy[H][W][3], out_variance[H][W], out_aov[H][W][8] may be NULL; HOST memory.
+ * RT_ERR_ARG, before the device is touched: a null s, cam, p or out_rgb; spp odd or below 2; p->world != 1 or p->rank != 0; luma_mode
+ * outside 0..1; aov_spp < 0; out_aov with aov_spp == 0; a config rt_denoise refuses; params rt_render refuses.  After that the call
+ * returns what rt_render_accumulate_device and rt_render_aov return: kernel 6 and integrator 2 are RT_ERR_UNSUPPORTED, and so is
+ * aov_spp > 0 on a scene with media or moving spheres.  stats: seconds = the call's wall time; kernel_ms, launches and samples summed
+ * over the two render ranges; the rest from the first range. */
+int rt_denoised_render(const rt_scene* s, const rt_camera* cam, const rt_params* p, const rt_denoise_config* cfg, int32_t luma_mode,
+                       int32_t aov_spp, double* out_rgb, double* out_noisy, double* out_variance, double* out_aov, rt_stats* stats);
+/* the same with the outputs in DEVICE memory of the call's device, the work queued on `hip_stream` (hipStream_t as void*, NULL = default
+ * stream); returns after the work has completed on that stream */
+int rt_denoised_render_device(const rt_scene* s, const rt_camera* cam, const rt_params* p, const rt_denoise_config* cfg, int32_t luma_mode,
+                              int32_t aov_spp, double* d_out_rgb, double* d_out_noisy, double* d_out_variance, double* d_out_aov,
+                              void* hip_stream, rt_stats* stats);
 
 /* ---- tile-adaptive sampling (no reference counterpart) ------------------------------------------------------------ */
 /* A whole frame on one device (p->world 1, p->rank 0, p->device picks it) in which every 8x8 tile T gets its own sample count n_T.  With

@@ -859,16 +859,19 @@ void rt_default_denoise_config(rt_denoise_config* c) {
     c->eps = 1e-10;
     c->guides = 7;
 }
-static void check_denoise_args(const rt_denoise_config* cfg, int32_t width, int32_t height, const double* rgb, const double* variance,
-                               const double* aov, const double* out_rgb, const double* out_variance) {
-    REQUIRE(cfg && rgb && out_rgb, "null argument");
-    REQUIRE(width > 0 && height > 0 && (int64_t)width * height <= (int64_t(1) << 31), "width/height must be positive (at most 2^31 pixels)");
+static void check_denoise_config(const rt_denoise_config* cfg) {
     REQUIRE(cfg->iterations >= 1 && cfg->iterations <= 8, "iterations must be 1..8");
     REQUIRE(cfg->normal_power_log2 >= 0 && cfg->normal_power_log2 <= 16, "normal_power_log2 must be 0..16");
     for (double v : {cfg->sigma_depth, cfg->sigma_albedo, cfg->sigma_luma, cfg->eps})
         REQUIRE(std::isfinite(v) && v > 0., "sigma_depth, sigma_albedo, sigma_luma and eps must be finite and positive");
     REQUIRE(cfg->guides >= 0 && cfg->guides <= 7, "guides is a mask of bits 0 (normal), 1 (depth), 2 (albedo)");
     for (int32_t r : cfg->reserved) REQUIRE(r == 0, "reserved fields of rt_denoise_config must be 0");
+}
+static void check_denoise_args(const rt_denoise_config* cfg, int32_t width, int32_t height, const double* rgb, const double* variance,
+                               const double* aov, const double* out_rgb, const double* out_variance) {
+    REQUIRE(cfg && rgb && out_rgb, "null argument");
+    REQUIRE(width > 0 && height > 0 && (int64_t)width * height <= (int64_t(1) << 31), "width/height must be positive (at most 2^31 pixels)");
+    check_denoise_config(cfg);
     REQUIRE(!out_variance || variance, "out_variance needs a variance input");
     for (const double* o : {out_rgb, out_variance})
         REQUIRE(!o || (o != rgb && o != variance && o != aov), "outputs must not be inputs");
@@ -891,6 +894,61 @@ int rt_denoise_device(const rt_denoise_config* cfg, int32_t width, int32_t heigh
         denoise_device(*cfg, width, height, d_rgb, d_variance, d_aov, d_out_rgb, d_out_variance, hip_stream);
         return (int)RT_OK;
     });
+}
+// the symmetric luminance stop: rt_denoise's checks, and a variance (without one the call would be rt_denoise)
+int rt_denoise_sym(const rt_denoise_config* cfg, int32_t width, int32_t height, const double* rgb, const double* variance, const double* aov,
+                   double* out_rgb, double* out_variance) {
+    return guard([&] {
+        check_denoise_args(cfg, width, height, rgb, variance, aov, out_rgb, out_variance);
+        REQUIRE(variance, "rt_denoise_sym needs a variance: without one the filter is rt_denoise's");
+        require_device(denoise_sym_host != nullptr);
+        denoise_sym_host(*cfg, width, height, rgb, variance, aov, out_rgb, out_variance);
+        return (int)RT_OK;
+    });
+}
+int rt_denoise_sym_device(const rt_denoise_config* cfg, int32_t width, int32_t height, const double* d_rgb, const double* d_variance,
+                          const double* d_aov, double* d_out_rgb, double* d_out_variance, void* hip_stream) {
+    return guard([&] {
+        check_denoise_args(cfg, width, height, d_rgb, d_variance, d_aov, d_out_rgb, d_out_variance);
+        REQUIRE(d_variance, "rt_denoise_sym_device needs a variance: without one the filter is rt_denoise_device's");
+        require_device(denoise_sym_device != nullptr);
+        denoise_sym_device(*cfg, width, height, d_rgb, d_variance, d_aov, d_out_rgb, d_out_variance, hip_stream);
+        return (int)RT_OK;
+    });
+}
+
+// ---- one call from scene to clean frame (the driver: host/frame.cpp render_denoised) ----
+static int render_denoised_entry(const rt_scene* s, const rt_camera* cam, const rt_params* p, const rt_denoise_config* cfg, int32_t luma_mode,
+                                 int32_t aov_spp, double* out_rgb, double* out_noisy, double* out_variance, double* out_aov, bool on_device,
+                                 void* hip_stream, rt_stats* stats) {
+    return guard([&] {
+        REQUIRE(s && cam && p && out_rgb, "null argument");
+        REQUIRE(p->spp >= 2 && p->spp % 2 == 0, "rt_denoised_render needs an even spp >= 2 (two half-frames)");
+        REQUIRE(p->world == 1 && p->rank == 0, "rt_denoised_render renders whole frames: world must be 1 and rank 0");
+        REQUIRE(luma_mode == 0 || luma_mode == 1, "luma_mode must be 0 (rt_denoise's luminance stop) or 1 (rt_denoise_sym's)");
+        REQUIRE(aov_spp >= 0, "aov_spp must be >= 0 (0: no guides)");
+        REQUIRE(aov_spp > 0 || !out_aov, "out_aov must be NULL when aov_spp is 0 (no guides are rendered)");
+        rt_denoise_config dc;
+        if (cfg) dc = *cfg;
+        else rt_default_denoise_config(&dc);
+        check_denoise_config(&dc);
+        REQUIRE(p->width > 0 && p->height > 0 && (int64_t)p->width * p->height <= (int64_t(1) << 31), "width/height must be positive (at most 2^31 pixels)");
+        for (const double* o : {out_noisy, out_variance, out_aov})
+            REQUIRE(!o || o != out_rgb, "the outputs must be distinct buffers");
+        REQUIRE(!out_noisy || (out_noisy != out_variance && out_noisy != out_aov), "the outputs must be distinct buffers");
+        REQUIRE(!out_variance || out_variance != out_aov, "the outputs must be distinct buffers");
+        render_denoised(*s, *cam, *p, dc, luma_mode, aov_spp, out_rgb, out_noisy, out_variance, out_aov, on_device, hip_stream, stats);
+        return (int)RT_OK;
+    });
+}
+int rt_denoised_render(const rt_scene* s, const rt_camera* cam, const rt_params* p, const rt_denoise_config* cfg, int32_t luma_mode,
+                       int32_t aov_spp, double* out_rgb, double* out_noisy, double* out_variance, double* out_aov, rt_stats* stats) {
+    return render_denoised_entry(s, cam, p, cfg, luma_mode, aov_spp, out_rgb, out_noisy, out_variance, out_aov, false, nullptr, stats);
+}
+int rt_denoised_render_device(const rt_scene* s, const rt_camera* cam, const rt_params* p, const rt_denoise_config* cfg, int32_t luma_mode,
+                              int32_t aov_spp, double* d_out_rgb, double* d_out_noisy, double* d_out_variance, double* d_out_aov,
+                              void* hip_stream, rt_stats* stats) {
+    return render_denoised_entry(s, cam, p, cfg, luma_mode, aov_spp, d_out_rgb, d_out_noisy, d_out_variance, d_out_aov, true, hip_stream, stats);
 }
 
 int rt_tonemap_u8(const double* rgb, size_t n_channels, uint8_t* out) {

@@ -6,6 +6,7 @@
 // accel walk (stacks in LDS, stride blockDim.x, as hit_kernel keeps them).  GENERAL 3 is the chain walk of nested Transforms.  The hit
 // record is built with uv for every primitive, as the closest-hit diagnostic builds it; the albedo is tex_color of the material's one
 // texture (noise textures included: the GENERAL >= 2 form).  Sums in sample order, f64; out[pix] = {normal[3], t, albedo[3], coverage}.
+// render_aov_device leaves the guides in the caller's device memory (rt_denoised_render filters them there); render_aov copies them out.
 
 #include "denoise.h"
 
@@ -54,13 +55,10 @@ __global__ void __launch_bounds__(64) aov_kernel(FlatView sv, CamK cam, int widt
     q[7] = nh / (double)aov_spp;
 }
 
-void render_aov(const rt_scene& s, const CameraDev& cam, int width, int height, uint64_t seed, double t_min, int kernel, int aov_spp, double* out_host,
-                rt_stats* st) {
-    if (!s.committed) throw RtError(RT_ERR_NOT_COMMITTED, "scene not committed");
-    if (s.flat.view.kinds_mask & (1u << NK_MSPHERE))
-        throw RtError(RT_ERR_UNSUPPORTED, "rt_render_aov has no ray time: scenes with moving spheres are not supported");
-    if (s.flat.view.kinds_mask & (1u << NK_MEDIUM_BEGIN))
-        throw RtError(RT_ERR_UNSUPPORTED, "rt_render_aov: the first hit in a scene with a ConstantMedium depends on the path's random stream (no guides through media)");
+void render_aov_device(const rt_scene& s, const CameraDev& cam, int width, int height, uint64_t seed, double t_min, int kernel, int aov_spp, double* d_out,
+                       void* stream_, rt_stats* st) {
+    hipStream_t stream = (hipStream_t)stream_;
+    aov_refuse(s);
     int dev = 0;
     HIP_CHECK(hipGetDevice(&dev));
     const DevInfo& di = dev_info(dev);
@@ -84,23 +82,21 @@ void render_aov(const rt_scene& s, const CameraDev& cam, int width, int height, 
     const size_t smem = (kernel == 2) ? stack_bytes : 0;
     if (smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     const size_t npix = (size_t)width * (size_t)height;
-    DevBuf dout, err;
-    dout.alloc(npix * 8 * sizeof(double));
+    DevBuf err;
     err.alloc(4);
-    HIP_CHECK(hipMemset(err.p, 0, 4));
+    HIP_CHECK(hipMemsetAsync(err.p, 0, 4, stream));
     Events events;
     hipEvent_t e0 = events.make(), e1 = events.make();
     const unsigned blocks = (unsigned)((npix + 63) / 64);
-    HIP_CHECK(hipEventRecord(e0, 0));
-    hipLaunchKernelGGL(fn, dim3(blocks), dim3(64), smem, 0, view, to_camk(cam), width, height, seed, t_min, aov_spp, (double*)dout.p, (int*)err.p);
+    HIP_CHECK(hipEventRecord(e0, stream));
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(64), smem, stream, view, to_camk(cam), width, height, seed, t_min, aov_spp, d_out, (int*)err.p);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(e1, 0));
+    HIP_CHECK(hipEventRecord(e1, stream));
     HIP_CHECK(hipEventSynchronize(e1));
     int h_err = 0;
     HIP_CHECK(hipMemcpy(&h_err, err.p, 4, hipMemcpyDeviceToHost));
     if (h_err & 1) throw RtError(RT_ERR_UNIT_ZERO, "unitizing zero vector (device, rt_render_aov)");
     if (h_err & ~1) throw RtError(RT_ERR_INTERNAL, "device invariant failed in rt_render_aov (error bits " + std::to_string(h_err) + ")");
-    HIP_CHECK(hipMemcpy(out_host, dout.p, npix * 8 * sizeof(double), hipMemcpyDeviceToHost));
     if (st) {
         float ms = 0.f;
         HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
@@ -113,6 +109,16 @@ void render_aov(const rt_scene& s, const CameraDev& cam, int width, int height, 
         st->grid_blocks = (int32_t)blocks;
         st->scene_bytes = s.flat.info.bytes;
     }
+}
+
+void render_aov(const rt_scene& s, const CameraDev& cam, int width, int height, uint64_t seed, double t_min, int kernel, int aov_spp, double* out_host,
+                rt_stats* st) {
+    aov_refuse(s);  // (before the allocation: a refused scene touches no device)
+    const size_t npix = (size_t)width * (size_t)height;
+    DevBuf dout;
+    dout.alloc(npix * 8 * sizeof(double));
+    render_aov_device(s, cam, width, height, seed, t_min, kernel, aov_spp, (double*)dout.p, nullptr, st);
+    HIP_CHECK(hipMemcpy(out_host, dout.p, npix * 8 * sizeof(double), hipMemcpyDeviceToHost));
 }
 
 }  // namespace rtamd

@@ -5,13 +5,28 @@
 #include <cstdint>
 
 #include "../host/scene.h"
+#include "device.h"
 #include "rtamd.h"
 
 namespace rtamd {
 
+// what rt_render_aov does not render, decided from the committed scene alone (no device): render_aov_device refuses with these codes and
+// messages, and rt_denoised_render asks before it renders the frame
+inline void aov_refuse(const rt_scene& s) {
+    if (!s.committed) throw RtError(RT_ERR_NOT_COMMITTED, "scene not committed");
+    if (s.flat.view.kinds_mask & (1u << NK_MSPHERE))
+        throw RtError(RT_ERR_UNSUPPORTED, "rt_render_aov has no ray time: scenes with moving spheres are not supported");
+    if (s.flat.view.kinds_mask & (1u << NK_MEDIUM_BEGIN))
+        throw RtError(RT_ERR_UNSUPPORTED, "rt_render_aov: the first hit in a scene with a ConstantMedium depends on the path's random stream (no guides through media)");
+}
+
 // rt_render_aov on the current device: out_host[height][width][8] (HOST).  kernel: 0 auto, 1 reference-order walk, 2 accel walk.
 __attribute__((weak)) void render_aov(const rt_scene& s, const CameraDev& cam, int width, int height, uint64_t seed, double t_min, int kernel,
                                       int aov_spp, double* out_host, rt_stats* st);
+// the same into d_out[height][width][8], DEVICE memory of the current device, launched on `stream` (a hipStream_t); returns after the
+// kernel has completed on it.  render_aov is this plus the copy to the host.
+__attribute__((weak)) void render_aov_device(const rt_scene& s, const CameraDev& cam, int width, int height, uint64_t seed, double t_min,
+                                             int kernel, int aov_spp, double* d_out, void* stream, rt_stats* st);
 // rt_denoise_device on the current device, `stream` a hipStream_t; every pointer is DEVICE memory, variance / aov / out_variance may be
 // null.  cfg has been validated.  Returns after the passes have completed on `stream`.
 __attribute__((weak)) void denoise_device(const rt_denoise_config& cfg, int width, int height, const double* rgb, const double* variance,
@@ -19,5 +34,16 @@ __attribute__((weak)) void denoise_device(const rt_denoise_config& cfg, int widt
 // rt_denoise: the same on HOST buffers (copies in and out, synchronous)
 __attribute__((weak)) void denoise_host(const rt_denoise_config& cfg, int width, int height, const double* rgb, const double* variance,
                                         const double* aov, double* out_rgb, double* out_variance);
+// rt_denoise_sym_device / rt_denoise_sym: the same two with the symmetric luminance stop sqrt(v_p + v_q); variance is not null
+__attribute__((weak)) void denoise_sym_device(const rt_denoise_config& cfg, int width, int height, const double* rgb, const double* variance,
+                                              const double* aov, double* out_rgb, double* out_variance, void* stream);
+__attribute__((weak)) void denoise_sym_host(const rt_denoise_config& cfg, int width, int height, const double* rgb, const double* variance,
+                                            const double* aov, double* out_rgb, double* out_variance);
+// rt_denoised_render between the render and the filter: accum (S, the sums of all plan.spp samples) and half (S_h, their snapshot after
+// plan.spp / 2), tile-major accumulators of a whole frame (world 1) -> noisy[height][width][3] = S / spp (finalize_kernel's division) and
+// variance[height][width] = ((l_A - l_B) (l_A - l_B)) / 4 of the half means A = S_h / h, B = (S - S_h) / h, row-major; the pixels of edge
+// tiles that lie outside the image are dropped.  DEVICE memory; returns after the kernel has completed on `stream`.
+__attribute__((weak)) void denoise_split_halves(const RenderPlan& plan, const double* accum, const double* half, double* noisy, double* variance,
+                                                void* stream);
 
 }  // namespace rtamd

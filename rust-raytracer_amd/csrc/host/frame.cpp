@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "device/adaptive.h"
+#include "device/denoise.h"
 #include "device/region.h"
 
 namespace rtamd {
@@ -304,6 +305,58 @@ void render_adaptive(const rt_scene& s, const rt_camera& cam, const rt_params& p
     stitch_to_host(full, compact.f64(), T, frame.f64(), out_rgb);
     if (out_tile_spp) std::memcpy(out_tile_spp, n_t.data(), (size_t)T * sizeof(int32_t));
     clock.finish(stats, sum, samples);
+}
+
+// ---- one call from scene to clean frame ----
+void render_denoised(const rt_scene& s, const rt_camera& cam, const rt_params& p, const rt_denoise_config& cfg, int luma_mode, int aov_spp,
+                     double* out_rgb, double* out_noisy, double* out_variance, double* out_aov, bool on_device, void* stream, rt_stats* stats) {
+    RenderPlan pl = make_plan(&p);
+    require_committed(s);
+    if (p.kernel == 6 || p.integrator == 2)
+        throw RtError(RT_ERR_UNSUPPORTED, "rt_denoised_render runs with kernels 0 / 1 / 2 / 5 and integrators 0 / 1 (those of rt_render_accumulate_device)");
+    if (aov_spp > 0) aov_refuse(s);  // (before the frame is rendered; such scenes pass aov_spp = 0)
+    require_device(adaptive_copy_tiles != nullptr && denoise_split_halves != nullptr && render_aov_device != nullptr && denoise_device != nullptr &&
+                   denoise_sym_device != nullptr);
+    const CallClock clock;
+    DeviceScope dev_scope(p.device);  // (device outputs and the stream must belong to it)
+    const CameraDev cd = make_camera(cam);
+    const size_t npix = (size_t)pl.width * (size_t)pl.height;
+    const size_t acc_bytes = row_doubles(pl.tiles_total) * sizeof(double);
+    // the running sums S and their snapshot S_h after the first half; then whatever the caller did not give device memory for
+    DevBuf acc(acc_bytes), half(acc_bytes), own_rgb(on_device ? 16 : npix * 3 * sizeof(double)),
+        own_noisy((on_device && out_noisy) ? 16 : npix * 3 * sizeof(double)), own_var((on_device && out_variance) ? 16 : npix * sizeof(double)),
+        own_aov((aov_spp == 0 || (on_device && out_aov)) ? 16 : npix * 8 * sizeof(double));
+    double* d_rgb = on_device ? out_rgb : own_rgb.f64();
+    double* d_noisy = (on_device && out_noisy) ? out_noisy : own_noisy.f64();
+    double* d_var = (on_device && out_variance) ? out_variance : own_var.f64();
+    double* d_aov = aov_spp == 0 ? nullptr : (on_device && out_aov) ? out_aov : own_aov.f64();
+    const int h = pl.spp / 2;
+    rt_stats sum{};
+    for (int range = 0; range < 2; range++) {
+        pl.s_first = range == 0 ? 0 : h;
+        pl.s_last = range == 0 ? h : pl.spp;
+        pl.ext_accum = acc.f64();
+        rt_stats st{};
+        render_tiles(s, cd, pl, nullptr, stream, &st);
+        if (range == 0) {
+            sum = st;
+            adaptive_copy_tiles(half.f64(), nullptr, acc.f64(), nullptr, pl.tiles_total, stream);  // S_h
+        } else {
+            sum.kernel_ms += st.kernel_ms;
+            sum.launches += st.launches;
+        }
+    }
+    denoise_split_halves(pl, acc.f64(), half.f64(), d_noisy, d_var, stream);
+    if (aov_spp > 0)
+        render_aov_device(s, cd, pl.width, pl.height, pl.seed, pl.t_min, (p.kernel == 1 || p.kernel == 2) ? p.kernel : 0, aov_spp, d_aov, stream, nullptr);
+    (luma_mode == 1 ? denoise_sym_device : denoise_device)(cfg, pl.width, pl.height, d_noisy, d_var, d_aov, d_rgb, nullptr, stream);
+    if (!on_device) {
+        dev_copy_to_host(out_rgb, d_rgb, npix * 3 * sizeof(double));
+        if (out_noisy) dev_copy_to_host(out_noisy, d_noisy, npix * 3 * sizeof(double));
+        if (out_variance) dev_copy_to_host(out_variance, d_var, npix * sizeof(double));
+        if (out_aov) dev_copy_to_host(out_aov, d_aov, npix * 8 * sizeof(double));
+    }
+    clock.finish(stats, sum, pixels_in_image(pl) * (uint64_t)pl.spp);
 }
 
 // ---- pixel regions of a frame ----

@@ -101,6 +101,12 @@ void finalize_host(const rt_params& p, const double* accum_state, double* out_rg
 // rt_render_adaptive: the passes over the active tiles and the stopping tests between them
 void render_adaptive(const rt_scene& s, const rt_camera& cam, const rt_params& p, const rt_adaptive_config& cfg, double* out_rgb,
                      int32_t* out_tile_spp, rt_stats* stats);
+// rt_denoised_render(_device): the frame in two sample ranges into one accumulator with a snapshot between them, the split into the noisy
+// frame and the variance, the guides (aov_spp > 0) and the filter (luma_mode 0: rt_denoise's, 1: rt_denoise_sym's), all in device memory
+// (DESIGN.md s4e).  The outputs are HOST memory, or DEVICE memory of the call's device when on_device; all but out_rgb may be null.  Its
+// checks begin at RT_ERR_NOT_COMMITTED / RT_ERR_UNSUPPORTED: the entry point has checked the arguments and the config.
+void render_denoised(const rt_scene& s, const rt_camera& cam, const rt_params& p, const rt_denoise_config& cfg, int luma_mode, int aov_spp,
+                     double* out_rgb, double* out_noisy, double* out_variance, double* out_aov, bool on_device, void* stream, rt_stats* stats);
 // rt_region_*: pixel regions of a frame.  check_regions is the argument check all four entry points share (RT_ERR_ARG for
 // a null pointer, whatever make_plan refuses, a partition, n_regions outside 1..65536, a region that is empty or leaves the frame) and
 // returns the whole frame's plan; region_pixels = the pixels of the packed output (regions counted one by one); region_tile_list = the

@@ -4,7 +4,7 @@
 //   rtamd_render [--scene cornell|FILE.json|FILE.yaml] [--cube data/mesh/cube.obj] [-w W] [-h H] [--spp N]
 //                [--depth D] [--seed S] [--aspect A] [--integrator 0|1] [--sppm ITERATIONS PHOTONS_PER_ITER]
 //                [--gpus N | --devices 0,1,...] [--background r,g,b | --sky] [--env-sampling] [--region x0,y0,x1,y1] [-o out.png]
-//                [--describe] [--vec3-selftest]
+//                [--denoise [--aov-spp N] [--luma-mode M]] [--describe] [--vec3-selftest]
 // --gpus N spreads the frame over N GPUs of this node inside ONE capture_image call (rt_render_multi: tiles dealt round-robin, RCCL
 // gather; 0 = all visible); --devices names the HIP ordinal of every rank (an ordinal may repeat).
 // `rtamd_render --cube data/mesh/cube.obj --sppm 50 500000` is the reference binary: SPPM pre-pass + 256 spp, output/test.png
@@ -13,6 +13,9 @@
 // (rt_scene_set_env_sampling, automatic table size)
 // --region x0,y0,x1,y1 renders only the pixels [x0, x1) x [y0, y1) of the W x H frame (rt_region_render: the frame's own pixels, at the
 // cost of the 8x8 tiles they touch) and writes the cropped PNG
+// --denoise renders the frame and filters it in one call (rt_denoised_render: --spp must be even) and writes the denoised PNG; --aov-spp N
+// guide rays per pixel (default 4; 0: none, for scenes with media or moving spheres), --luma-mode 1 (default) the energy-preserving
+// symmetric luminance stop, 0 rt_denoise's
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -59,6 +62,8 @@ int main(int argc, char** argv) {
     bool env_sampling = false;
     rt_region region{0, 0, 0, 0};
     bool crop = false;
+    bool denoise_frame = false;
+    int aov_spp = 4, luma_mode = 1;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -91,6 +96,9 @@ int main(int argc, char** argv) {
             if (std::sscanf(next(), "%d,%d,%d,%d", &region.x0, &region.y0, &region.x1, &region.y1) != 4) { std::fprintf(stderr, "--region wants x0,y0,x1,y1\n"); return 2; }
             crop = true;
         }
+        else if (a == "--denoise") denoise_frame = true;
+        else if (a == "--aov-spp") aov_spp = std::atoi(next());
+        else if (a == "--luma-mode") luma_mode = std::atoi(next());
         else if (a == "-o") out = next();
         else if (a == "--checkpoint") { checkpoint = next(); }
         else if (a == "--run-samples") run_samples = std::atoi(next());
@@ -134,6 +142,18 @@ int main(int argc, char** argv) {
             img.save(out);
             std::printf("region (%d, %d, %d, %d): %llu samples traced, kernel %.1f ms, %.3fs\n", region.x0, region.y0, region.x1, region.y1,
                         (unsigned long long)st.samples, st.kernel_ms, std::chrono::duration<double>(std::chrono::steady_clock::now() - rt_start).count());
+            return 0;
+        }
+        if (denoise_frame) {
+            const std::vector<double> rad = world->render_denoised(cfg, aov_spp, luma_mode, nullptr, nullptr, nullptr, nullptr, 0, &st);
+            RgbImage img;
+            img.width = cfg.width;
+            img.height = cfg.height;
+            img.data.resize(rad.size());
+            check(rt_tonemap_u8(rad.data(), rad.size(), img.data.data()));
+            img.save(out);
+            std::printf("denoised (luma mode %d, %d guide rays per pixel): %llu samples, kernel %.1f ms in %d launches, %.3fs\n", luma_mode, aov_spp,
+                        (unsigned long long)st.samples, st.kernel_ms, st.launches, st.seconds);
             return 0;
         }
         std::vector<rt_stats> ranks;

@@ -535,6 +535,28 @@ class World {
         return aov;
     }
 
+    // One call from scene to clean frame (rt_denoised_render): cfg.sample_per_pixel (even) samples in two halves, their
+    // variance, aov_spp guide rays per pixel (0: none -- scenes with media or moving spheres) and the a-trous filter, all on the device.
+    // luma_mode 1 is the energy-preserving symmetric luminance stop (rt_denoise_sym), 0 rt_denoise's; dcfg NULL =
+    // rt_default_denoise_config.  Returns the denoised linear radiance [height][width][3]; noisy (rt_render's frame), variance
+    // [height][width] and aov [height][width][8] are filled where given.
+    std::vector<double> render_denoised(const Config& cfg, int aov_spp = 4, int luma_mode = 1, const rt_denoise_config* dcfg = nullptr,
+                                        std::vector<double>* noisy = nullptr, std::vector<double>* variance = nullptr,
+                                        std::vector<double>* aov = nullptr, int kernel = 0, rt_stats* stats = nullptr) const {
+        rt_params p;
+        rt_default_params(&p);
+        p.width = cfg.width; p.height = cfg.height; p.spp = cfg.sample_per_pixel; p.max_depth = cfg.max_depth;
+        p.t_min = cfg.t_min; p.seed = cfg.seed; p.integrator = cfg.integrator; p.kernel = kernel;
+        const size_t n = (size_t)cfg.width * cfg.height;
+        std::vector<double> rad(n * 3);
+        if (noisy) noisy->assign(n * 3, 0.);
+        if (variance) variance->assign(n, 0.);
+        if (aov) aov->assign(aov_spp > 0 ? n * 8 : 0, 0.);
+        check(rt_denoised_render(s_, &cam.c, &p, dcfg, luma_mode, aov_spp, rad.data(), noisy ? noisy->data() : nullptr,
+                                 variance ? variance->data() : nullptr, (aov && aov_spp > 0) ? aov->data() : nullptr, stats));
+        return rad;
+    }
+
     // Tile-adaptive sampling (rt_render_adaptive): every 8x8 tile gets acfg.min_spp samples, then doubles its count until
     // its two-buffer error drops below acfg.threshold or it reaches cfg.sample_per_pixel (acfg NULL = rt_default_adaptive_config).
     // Returns the linear radiance [height][width][3]; tile_spp (if given) receives each tile's final sample count, [tiles_y][tiles_x].

@@ -221,6 +221,13 @@ _SIGS = [
     ("rt_denoise", C.c_int, [C.POINTER(rt_denoise_config), C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp]),
     ("rt_denoise_device", C.c_int, [C.POINTER(rt_denoise_config), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
+    ("rt_denoise_sym", C.c_int, [C.POINTER(rt_denoise_config), C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp]),
+    ("rt_denoise_sym_device", C.c_int, [C.POINTER(rt_denoise_config), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    ("rt_denoised_render", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_denoise_config), C.c_int32, C.c_int32,
+                                     _dp, _dp, _dp, _dp, C.POINTER(rt_stats)]),
+    ("rt_denoised_render_device", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_denoise_config), C.c_int32,
+                                            C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(rt_stats)]),
     ("rt_default_adaptive_config", None, [C.POINTER(rt_adaptive_config)]),
     ("rt_render_adaptive", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_adaptive_config), _dp,
                                      C.POINTER(C.c_int32), C.POINTER(rt_stats)]),
@@ -779,13 +786,28 @@ class World:
         return out, st.as_dict()
 
     def render_denoised(self, camera, width=800, height=800, spp=256, guides=True, aov_spp=4, max_depth=50, t_min=1e-3, seed=1,
-                        kernel=0, device=-1, integrator=0, **cfg):
-        """A frame, its variance and its guides, filtered by rt_denoise.  spp must be even: samples [0, spp/2) and [spp/2, spp) go through
+                        kernel=0, device=-1, integrator=0, native=False, luma_mode=1, **cfg):
+        """A frame, its variance and its guides, filtered by rt_denoise.  native=True: the one call rt_denoised_render, which keeps
+        everything but the four results on the device and filters with rt_denoise (luma_mode 0) or rt_denoise_sym (luma_mode 1, the
+        energy-preserving stop); with luma_mode 0 its results are the composition's bit for bit.  native=False (the default) is the
+        composition below, which ignores luma_mode.  spp must be even: samples [0, spp/2) and [spp/2, spp) go through
         the resumable path (rt_render_accumulate) into ONE accumulator, so `noisy` is bit for bit render()'s frame; the half-means A and B
         give variance = (l_A - l_B)^2 / 4 of the pixel's mean luminance l.  guides=False skips rt_render_aov (aov is None then: scenes
         with media or moving spheres).  cfg: rt_denoise_config fields.  Returns (denoised, noisy, variance, aov)."""
         if spp < 2 or spp % 2:
             raise ValueError("render_denoised needs an even spp >= 2 (two half-frames), got %r" % (spp,))
+        if native:
+            p = default_params(width=width, height=height, spp=spp, max_depth=max_depth, t_min=t_min, seed=seed, kernel=kernel, device=device,
+                               integrator=integrator)
+            c = denoise_config(**cfg)
+            den, noisy = np.zeros((height, width, 3)), np.zeros((height, width, 3))
+            variance = np.zeros((height, width))
+            aov = np.zeros((height, width, 8)) if guides else None
+            st = rt_stats()
+            _chk(self.L.rt_denoised_render(self.h, C.byref(camera.c), C.byref(p), C.byref(c), int(luma_mode), int(aov_spp) if guides else 0,
+                                           den.ctypes.data_as(_dp), noisy.ctypes.data_as(_dp), variance.ctypes.data_as(_dp),
+                                           aov.ctypes.data_as(_dp) if guides else None, C.byref(st)))
+            return den, noisy, variance, aov
         p = default_params(width=width, height=height, spp=spp, max_depth=max_depth, t_min=t_min, seed=seed, kernel=kernel, device=device,
                            integrator=integrator)
         half = spp // 2
@@ -803,6 +825,18 @@ class World:
             aov = self.render_aov(camera, width, height, aov_spp=aov_spp, seed=seed, kernel=kernel if kernel in (1, 2) else 0, t_min=t_min,
                                   device=device)[0]
         return denoise(noisy, variance, aov, **cfg), noisy, variance, aov
+
+    def render_denoised_device(self, camera, params, d_out_ptr, d_noisy_ptr=None, d_variance_ptr=None, d_aov_ptr=None, aov_spp=4, luma_mode=1,
+                               stream_ptr=None, **cfg):
+        """rt_denoised_render_device: the denoised frame [H, W, 3] -- and, where a pointer is given, the noisy frame [H, W, 3], the variance
+        [H, W] and the guides [H, W, 8] -- into raw device pointers (e.g. torch tensor .data_ptr()) of the call's device, queued on
+        stream_ptr.  aov_spp = 0: no guides (d_aov_ptr must be None).  Returns the stats dict after the work has completed on that stream."""
+        c = denoise_config(**cfg)
+        st = rt_stats()
+        _chk(self.L.rt_denoised_render_device(self.h, C.byref(camera.c), C.byref(params), C.byref(c), int(luma_mode), int(aov_spp), C.c_void_p(d_out_ptr),
+                                              C.c_void_p(d_noisy_ptr or 0), C.c_void_p(d_variance_ptr or 0), C.c_void_p(d_aov_ptr or 0),
+                                              C.c_void_p(stream_ptr or 0), C.byref(st)))
+        return st.as_dict()
 
     def debug_hit(self, rays, t_min=1e-3, t_max=float("inf"), kernel=1):
         r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
@@ -1084,8 +1118,9 @@ def luminance(rgb):
     return (0.2126 * rgb[..., 0] + 0.7152 * rgb[..., 1]) + 0.0722 * rgb[..., 2]
 
 
-def denoise(rgb, variance=None, aov=None, return_variance=False, **cfg):
-    """rt_denoise: the a-trous filter on host arrays.  rgb [H, W, 3]; variance [H, W] of each pixel's mean luminance (None: no luminance
+def denoise(rgb, variance=None, aov=None, return_variance=False, symmetric=False, **cfg):
+    """rt_denoise, or with symmetric=True rt_denoise_sym (the luminance stop sqrt(v_p + v_q), which keeps the frame's mean; it needs a
+    variance): the a-trous filter on host arrays.  rgb [H, W, 3]; variance [H, W] of each pixel's mean luminance (None: no luminance
     weight); aov [H, W, 8] from World.render_aov (None: no guides).  cfg: rt_denoise_config fields (iterations, normal_power_log2,
     sigma_depth, sigma_albedo, sigma_luma, eps, guides).  Returns the filtered [H, W, 3], and with return_variance also the filtered variance."""
     c = denoise_config(**cfg)
@@ -1106,16 +1141,19 @@ def denoise(rgb, variance=None, aov=None, return_variance=False, **cfg):
         aov_p = aov.ctypes.data_as(_dp)
     out = np.zeros_like(rgb)
     out_var = np.zeros((h, w), dtype=np.float64) if return_variance else None
-    _chk(lib().rt_denoise(C.byref(c), w, h, rgb.ctypes.data_as(_dp), var_p, aov_p, out.ctypes.data_as(_dp),
-                          out_var.ctypes.data_as(_dp) if out_var is not None else None))
+    fn = lib().rt_denoise_sym if symmetric else lib().rt_denoise
+    _chk(fn(C.byref(c), w, h, rgb.ctypes.data_as(_dp), var_p, aov_p, out.ctypes.data_as(_dp), out_var.ctypes.data_as(_dp) if out_var is not None else None))
     return (out, out_var) if return_variance else out
 
 
-def denoise_device(width, height, d_rgb_ptr, d_out_ptr, d_variance_ptr=None, d_aov_ptr=None, d_out_variance_ptr=None, stream_ptr=None, **cfg):
-    """rt_denoise_device: raw device pointers (e.g. torch tensor .data_ptr()) of the current device; returns when the passes are done"""
+def denoise_device(width, height, d_rgb_ptr, d_out_ptr, d_variance_ptr=None, d_aov_ptr=None, d_out_variance_ptr=None, stream_ptr=None,
+                   symmetric=False, **cfg):
+    """rt_denoise_device (symmetric=True: rt_denoise_sym_device): raw device pointers (e.g. torch tensor .data_ptr()) of the current device;
+    returns when the passes are done"""
     c = denoise_config(**cfg)
-    _chk(lib().rt_denoise_device(C.byref(c), int(width), int(height), C.c_void_p(d_rgb_ptr), C.c_void_p(d_variance_ptr or 0), C.c_void_p(d_aov_ptr or 0),
-                                 C.c_void_p(d_out_ptr), C.c_void_p(d_out_variance_ptr or 0), C.c_void_p(stream_ptr or 0)))
+    fn = lib().rt_denoise_sym_device if symmetric else lib().rt_denoise_device
+    _chk(fn(C.byref(c), int(width), int(height), C.c_void_p(d_rgb_ptr), C.c_void_p(d_variance_ptr or 0), C.c_void_p(d_aov_ptr or 0),
+            C.c_void_p(d_out_ptr), C.c_void_p(d_out_variance_ptr or 0), C.c_void_p(stream_ptr or 0)))
 
 
 def tonemap_u8(rgb):

@@ -388,6 +388,10 @@ extern "C" {
     pub fn rt_default_denoise_config(c: *mut rt_denoise_config);
     pub fn rt_denoise(cfg: *const rt_denoise_config, width: i32, height: i32, rgb: *const c_double, variance: *const c_double, aov: *const c_double, out_rgb: *mut c_double, out_variance: *mut c_double) -> c_int;
     pub fn rt_denoise_device(cfg: *const rt_denoise_config, width: i32, height: i32, d_rgb: *const c_double, d_variance: *const c_double, d_aov: *const c_double, d_out_rgb: *mut c_double, d_out_variance: *mut c_double, hip_stream: *mut c_void) -> c_int;
+    pub fn rt_denoise_sym(cfg: *const rt_denoise_config, width: i32, height: i32, rgb: *const c_double, variance: *const c_double, aov: *const c_double, out_rgb: *mut c_double, out_variance: *mut c_double) -> c_int;
+    pub fn rt_denoise_sym_device(cfg: *const rt_denoise_config, width: i32, height: i32, d_rgb: *const c_double, d_variance: *const c_double, d_aov: *const c_double, d_out_rgb: *mut c_double, d_out_variance: *mut c_double, hip_stream: *mut c_void) -> c_int;
+    pub fn rt_denoised_render(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, cfg: *const rt_denoise_config, luma_mode: i32, aov_spp: i32, out_rgb: *mut c_double, out_noisy: *mut c_double, out_variance: *mut c_double, out_aov: *mut c_double, stats: *mut rt_stats) -> c_int;
+    pub fn rt_denoised_render_device(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, cfg: *const rt_denoise_config, luma_mode: i32, aov_spp: i32, d_out_rgb: *mut c_double, d_out_noisy: *mut c_double, d_out_variance: *mut c_double, d_out_aov: *mut c_double, hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
     pub fn rt_render_sppm(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, cfg: *const rt_sppm_config, out_rgb: *mut c_double, stats_out: *mut c_double, photons_stored: *mut u64, stats: *mut rt_stats) -> c_int;
     pub fn rt_region_doubles(p: *const rt_params, n_regions: c_int, regions: *const rt_region) -> i64;
     pub fn rt_region_tiles(p: *const rt_params, n_regions: c_int, regions: *const rt_region, capacity: i64, out_tiles: *mut i32) -> i64;
@@ -782,6 +786,20 @@ impl Scene {
         check(unsafe { rt_render_aov(self.raw, cam, p, aov_spp, out.as_mut_ptr(), &mut st) })?;
         Ok((out, st))
     }
+    /// rt_denoised_render: one call from scene to clean frame, everything but the results on the device.  p.spp even; luma_mode 1 = the
+    /// energy-preserving symmetric luminance stop (rt_denoise_sym), 0 = rt_denoise's; aov_spp 0 = no guides (media, moving spheres);
+    /// cfg None = rt_default_denoise_config.  Returns the denoised frame [h][w][3], the noisy frame (rt_render's, bit for bit) and stats.
+    pub fn render_denoised(&self, cam: &rt_camera, p: &rt_params, cfg: Option<&rt_denoise_config>, luma_mode: i32, aov_spp: i32) -> Result<(Vec<f64>, Vec<f64>, rt_stats), RtError> {
+        let n = (p.width.max(0) as usize) * (p.height.max(0) as usize);
+        let mut out = vec![0.0f64; n * 3];
+        let mut noisy = vec![0.0f64; n * 3];
+        let mut st = rt_stats::default();
+        check(unsafe {
+            rt_denoised_render(self.raw, cam, p, cfg.map_or(std::ptr::null(), |c| c as *const rt_denoise_config), luma_mode, aov_spp, out.as_mut_ptr(),
+                               noisy.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut(), &mut st)
+        })?;
+        Ok((out, noisy, st))
+    }
     pub fn render_sppm(&self, cam: &rt_camera, p: &rt_params, cfg: &rt_sppm_config) -> Result<(Vec<f64>, rt_stats), RtError> {
         let mut out = vec![0.0f64; (p.width as usize) * (p.height as usize) * 3];
         let mut st = rt_stats::default();
@@ -1002,6 +1020,24 @@ pub fn denoise(width: i32, height: i32, rgb: &[f64], variance: Option<&[f64]>, a
     check(unsafe {
         rt_denoise(&c, width, height, rgb.as_ptr(), variance.map_or(std::ptr::null(), |v| v.as_ptr()), aov.map_or(std::ptr::null(), |a| a.as_ptr()),
                    out.as_mut_ptr(), std::ptr::null_mut())
+    })?;
+    Ok(out)
+}
+
+/// rt_denoise_sym: the same filter with the symmetric luminance stop sqrt(v_p + v_q), which keeps the frame's mean; the variance is required
+pub fn denoise_sym(width: i32, height: i32, rgb: &[f64], variance: &[f64], aov: Option<&[f64]>, cfg: Option<&rt_denoise_config>) -> Result<Vec<f64>, RtError> {
+    let n = (width.max(0) as usize) * (height.max(0) as usize);
+    if n == 0 || rgb.len() != n * 3 || variance.len() != n || aov.map_or(false, |a| a.len() != n * 8) {
+        return Err(RtError { code: -1, message: "denoise_sym: buffer sizes do not match the frame".to_string() });
+    }
+    let mut c = rt_denoise_config::default();
+    match cfg {
+        Some(x) => c = *x,
+        None => unsafe { rt_default_denoise_config(&mut c) },
+    }
+    let mut out = vec![0.0f64; n * 3];
+    check(unsafe {
+        rt_denoise_sym(&c, width, height, rgb.as_ptr(), variance.as_ptr(), aov.map_or(std::ptr::null(), |a| a.as_ptr()), out.as_mut_ptr(), std::ptr::null_mut())
     })?;
     Ok(out)
 }

@@ -371,3 +371,45 @@ def _lattice():
                         out.append(np.concatenate([p, d]))
                         kind.append(2)
     return np.array(out), dict(kind=np.array(kind))
+
+
+# ---- lit instance scenes for whole frames under integrators 1 and 2 (tests/reach_scenes.py) -----------------------------------------------------
+LIT_CAM = ((0.0, 4.0, -9.0), (0.0, 0.5, 0.0), (0.0, 1.0, 0.0), 40.0, 1.5, 0.0, 9.0)
+
+
+def lit_items(B, n, inline, tie):
+    """-> (items, lights): n instances of three small tori (f32 vertices: kernels 5 / 6 defer them; more than 32 instances take the 64-bit
+    pending mask) in rings under a sphere light (B.SphereDiffuseLight: rtamd.World, or sppm_trace_cases.OB over the oracle), on a floor.
+    inline: plus a Transform over a BVH of spheres, which kernels 5 / 6 enter in the lane.  tie: the floor is a rectangle (a scene with a
+    rectangle or a cube takes the exact-tie variants), else a large sphere."""
+    from rtamd import shapes
+
+    def mesh(m, mat, seed):
+        try:
+            return B.Mesh(m[0], m[1], m[2], mat, bvh_seed=seed)
+        except TypeError:
+            return B.Mesh(m[0], m[1], m[2], mat, seed)
+
+    grey = B.Lambertian(B.ConstantTexture((0.7, 0.7, 0.7)))
+    red = B.Lambertian(B.ConstantTexture((0.7, 0.3, 0.2)))
+    glass = B.Dielectric(1.5, B.ConstantTexture((1.0, 1.0, 1.0)))
+    metal = B.Metal(B.ConstantTexture((0.8, 0.85, 0.9)), 0.1)
+    objs = [mesh(shapes.torus(6, 8), grey, 1), mesh(shapes.torus(5, 10), glass, 2), mesh(shapes.torus(8, 6), metal, 3)]
+    rng = _rng("lit", n)
+    items = []
+    for k in range(n):
+        ring, a = k // 12, 2.0 * np.pi * (k % 12) / 12.0 + 0.3 * (k // 12)
+        r = 1.6 + 1.3 * ring
+        s = float(rng.uniform(0.35, 0.55))
+        items.append(B.Transform(_t(rng.uniform(-180.0, 180.0, 3)), (s, s * float(rng.uniform(0.7, 1.3)), s),
+                                 (float(r * np.cos(a)), 0.45 + 0.5 * (k % 3), float(r * np.sin(a))), objs[k % 3]))
+    if inline:
+        balls = [B.Sphere(_t(c), 0.12, glass if k % 3 == 0 else red) for k, c in enumerate(rng.uniform(-0.5, 0.5, size=(9, 3)))]
+        try:
+            grp = B.BVHNode_new(balls, bvh_seed=4)
+        except TypeError:
+            grp = B.BVHNode_new(balls, 4)
+        items.append(B.Transform((10.0, 40.0, 0.0), (1.5, 1.0, 1.5), (0.0, 0.8, 0.0), grp))
+    items.append(B.XZRectangle((-30.0, -30.0), (30.0, 30.0), 0.0, grey) if tie else B.Sphere((0.0, -1000.0, 0.0), 1000.0, grey))
+    lt = B.SphereDiffuseLight((0.0, 7.5, 0.0), 3.0, (1.0, 1.0, 1.0), 300.0)  # (large: integrator 0 finds it at 1 spp in one pixel of five)
+    return items + [lt], [lt]

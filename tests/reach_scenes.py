@@ -1,0 +1,201 @@
+"""One case per compiled render-kernel instantiation that the suite did not launch before tests/test_kernel_reach_gpu.py existed
+(tools/launch_coverage.py measured which: 64 of the 160 instantiations of pt_kernel, pt_kernel_coop and pt_kernel_wf; 60 have a case), for
+tests/test_kernel_reach_gpu.py (the renders, HIP == oracle) and tests/test_launch_coverage_record.py (every case's instantiation is
+`launched` by that file in tests/golden/kernel_launch_coverage.json).
+
+A case names the instantiation as the coverage record does (the demangled name without namespace and parameter list, e.g.
+`pt_kernel<false, 1, 2, 1, false, true>`) and holds the smallest call that selects it by render_tiles' rules (csrc/device/kernels.hip):
+  scene      a key of SCENES: both sides of a scene from the existing builders (light_scenes, nested_scenes, sppm_trace_cases,
+             instance_scenes); the scene kind gives GENERAL / MEDIA / the background bit / TIE / MIXED / the pending mask's width
+  mode       "render" (rt_render, integrator 0 or 1) or "sppm" (rt_render_sppm: its final pass is integrator 2)
+  kernel_id  the requested kernel (1, 2, 5 or 6); no_lds: rt_tuning's no_lds, the variants that read the scene from L2
+  side       which side of a tile-count threshold the case needs, tested against the stats of the call itself:
+             "pool"  kernel 2, tiles_owned <  waves of the launch (grid_blocks x block_threads / 64): the out-of-order-fold twin
+             "fold"  kernel 2, tiles_owned >= waves: the in-order-fold twin -- a LARGE frame, sized from an 8 x 8 probe render
+             "early" kernel 5, tiles_owned <  waves (<= 2 x CUs x 16, the rule's bound, at up to two 1024-thread blocks a CU)
+             "late"  kernel 5, tiles_owned >= 2 x waves (>= 2 x CUs x 16): the twin that folds after the main loop -- a LARGE frame
+             None    the instantiation has no twin
+
+UNREACHABLE: instantiations no valid call selects -> (rule, "file:line" of the rule).  TOO_LARGE: instantiations whose smallest
+selecting workload is slower than the slowest test of the suite -> measured seconds.  Both are empty: every compiled instantiation is
+selected by some call.  WITHHELD: instantiations whose case hung on the device -> the reason; they have no case until the cause is
+found ("Kernel launch coverage")."""
+from collections import namedtuple
+
+Case = namedtuple("Case", "kernel scene mode kernel_id integrator no_lds side")
+
+UNREACHABLE = {}
+TOO_LARGE = {}
+# Instantiations whose case is withheld: the SPPM final pass through kernel 6 (rt_render_sppm with kernel = 6; nothing launched it before
+# either).  As the FIRST render of a process the call on the inst[2,tie] scene made no progress within two minutes and was killed; after
+# other renders in the same process it finished but differed from the oracle (and from kernels 1, 2, 5 and from itself in another
+# process) in one pixel of 240, by the weight of one sample.  The cause is not found yet, so no test runs rt_render_sppm with kernel 6.
+_WF_SPPM = "rt_render_sppm with kernel 6 hung as the first render of a process and differed from the oracle by one sample in one pixel after others; cause not found"
+WITHHELD = {"pt_kernel_wf<2, false, false>": _WF_SPPM, "pt_kernel_wf<2, false, true>": _WF_SPPM,
+            "pt_kernel_wf<2, true, false>": _WF_SPPM, "pt_kernel_wf<2, true, true>": _WF_SPPM}
+
+SMALL = (20, 12)  # partial tiles on both edges: 3 x 2 tiles
+SMALL_SPP = dict(render=16, sppm=2)  # (integrator 0 finds the lamps by chance: 16 spp light more than one pixel in ten)
+SPPM_SMALL = dict(iterations=2, photons_per_iter=2000, k_global=20, k_caustic=5)
+SPPM_LARGE = dict(iterations=1, photons_per_iter=2000, k_global=20, k_caustic=5)
+
+
+def _b(v):
+    return "true" if v else "false"
+
+
+def pt(lds, general, accel, integ, media=False, pool=False):
+    return "pt_kernel<%s, %d, %d, %d, %s, %s>" % (_b(lds), general, accel, integ, _b(media), _b(pool))
+
+
+def coop(integ, mixed, early, wide, tie):
+    return "pt_kernel_coop<%d, %s, %s, %s, %s>" % (integ, _b(mixed), _b(early), "unsigned long" if wide else "unsigned int", _b(tie))
+
+
+def wf(integ, mixed, tie):
+    return "pt_kernel_wf<%d, %s, %s>" % (integ, _b(mixed), _b(tie))
+
+
+# ---- scenes: key -> () -> (rtamd.World, rtamd.Camera, oracle.Scene, extra render keywords of the product) ---------------------------------------
+def _pair(build, cam_args, bvh_seed, bg=None):
+    """build(B) -> (items, lights) on both builders (sppm_trace_cases._pair, with the commit deferred so that a background can be set)"""
+    import oracle
+    import light_scenes as ls
+    from sppm_trace_cases import OB
+    w = ls.deferred_world()
+    items, lights = build(w)
+    w.new(items, lights=lights, bvh_seed=bvh_seed)
+    o = oracle.Scene()
+    ob = OB(o)
+    oitems, olights = build(ob)
+    o.World(oitems, bvh_seed)
+    o.set_lights(olights, flux=[ob.desc[i][0] for i in olights], scale=[ob.desc[i][1] for i in olights])
+    o.Camera(*cam_args)
+    return ls.finish_product(w, bg), ls._camera(cam_args), ls.finish_oracle(o, bg), {}
+
+
+def _pair_file(name):
+    """a scene file of tests/golden/scenes on both loaders, as light_scenes.pair_scene_10"""
+    import oracle
+    import rtamd
+    from conftest import scene_path
+    w, cam = rtamd.load_scene_file(scene_path(name))
+    return w, cam.with_aspect(1.5), oracle.load_scene_file(scene_path(name), aspect=1.5), {}
+
+
+def _open_shutter(pair):
+    """an open shutter makes any scene a book-2 scene (GENERAL == 2): every sample draws a time"""
+    w, cam, o, kw = pair
+    o.set_shutter(0.0, 1.0)
+    return w, cam, o, dict(kw, shutter=(0.0, 1.0))
+
+
+def _scenes():
+    import instance_scenes as inst
+    import light_scenes as ls
+    import nested_scenes as ns
+    import sppm_trace_cases as sc
+    out = {
+        "spheres": lambda: _pair_file("scene_500.json"),                                # GENERAL 0
+        "spheres_shutter": lambda: _open_shutter(_pair_file("scene_500.json")),         # GENERAL 2, no medium
+        "spheres_shutter_sky": lambda: _open_shutter(ls.pair_scene_10(ls.GRADIENT)),    # ... under a background (scene_10: LDS-resident)
+        "cornell": lambda: ls.pair_cornell(None),                                       # GENERAL 1, a lamp
+        "smoke": lambda: ls.pair_smoke(None),                                           # GENERAL 1 + MEDIA, a lamp
+        "n4": lambda: ls.pair_nested("n4", None),                                       # GENERAL 3, a lamp, glass (SPPM: caustic photons)
+        "n6": lambda: ls.pair_nested("n6", None),                                       # GENERAL 3 + MEDIA under Transforms: kernel 1 only
+        "nested_fog": lambda: _pair(sc._nested_fog, ns.CORNELL_CAM, 4),                 # GENERAL 3 + MEDIA at world level: kernel 2 applies
+        "nested_fog_sky": lambda: _pair(sc._nested_fog, ns.CORNELL_CAM, 4, ls.GRADIENT),
+    }
+    for n, inline, tie in INSTANCE_SCENES.values():
+        out[_inst_key(n, inline, tie)] = (lambda n=n, inline=inline, tie=tie: _pair(lambda B: inst.lit_items(B, n, inline, tie), inst.LIT_CAM, 3))
+    return out
+
+
+def _inst_key(n, inline, tie):
+    return "inst[%d%s%s]" % (n, ",inline" if inline else "", ",tie" if tie else "")
+
+
+# (mixed, wide) -> (instances, inline): MIXED is the code for scenes with instances the service cannot defer; the 64-bit pending mask
+# (more than 32 instances) exists in the MIXED form only and covers scenes without inline instances too
+INSTANCE_SCENES = {(mixed, wide, tie): (33 if wide else 2, mixed and not wide, tie)
+                   for mixed, wide in ((False, False), (True, False), (True, True)) for tie in (False, True)}
+# expected info() fields of the instance scenes: accel_instances counts the inline instance too
+INSTANCE_INFO = {_inst_key(n, inline, tie): dict(accel_ok=1, accel_compact=1, accel_instances=n + int(inline)) for n, inline, tie in INSTANCE_SCENES.values()}
+
+_PAIRS = {}
+
+
+def pair(key):
+    """both sides of SCENES[key], built once"""
+    if key not in _PAIRS:
+        _PAIRS[key] = _scenes()[key]()
+    return _PAIRS[key]
+
+
+# ---- the cases ----------------------------------------------------------------------------------------------------------------------------------
+# what the suite launched before this file existed (tools/launch_coverage.py, first run): no case for these
+_COOP_BEFORE = {coop(0, False, False, False, True), coop(0, False, True, False, False), coop(0, False, True, False, True), coop(0, True, True, False, True),
+                coop(0, True, True, True, True), coop(1, False, True, False, True), coop(2, False, True, False, True)}
+_WF_BEFORE = {wf(0, False, False), wf(0, False, True), wf(0, True, True)}
+
+
+def _pt_cases():
+    C = Case
+    return [
+        # kernel 1 and the pool twins of kernel 2 out of LDS: small frames
+        C(pt(False, 1, 1, 1), "cornell", "render", 1, 1, 1, None),
+        C(pt(False, 1, 1, 2), "cornell", "sppm", 1, 2, 1, None),
+        C(pt(False, 1, 1, 2, True), "smoke", "sppm", 1, 2, 1, None),
+        C(pt(False, 1, 2, 1, False, True), "cornell", "render", 2, 1, 1, "pool"),
+        C(pt(False, 1, 2, 2, False, True), "cornell", "sppm", 2, 2, 1, "pool"),
+        # book-2 scenes without a medium, with and without a background
+        C(pt(False, 2, 1, 0), "spheres_shutter", "render", 1, 0, 1, None),
+        C(pt(False, 2, 2, 0), "spheres_shutter", "render", 2, 0, 1, None),
+        C(pt(False, 2, 1, 4), "spheres_shutter_sky", "render", 1, 0, 1, None),
+        C(pt(False, 2, 2, 4), "spheres_shutter_sky", "render", 2, 0, 1, None),
+        C(pt(True, 2, 1, 4), "spheres_shutter_sky", "render", 1, 0, 0, None),
+        C(pt(True, 2, 2, 4), "spheres_shutter_sky", "render", 2, 0, 0, None),
+        # nested chains out of LDS: integrators 1 and 2, media
+        C(pt(False, 3, 1, 1), "n4", "render", 1, 1, 1, None),
+        C(pt(False, 3, 2, 1), "n4", "render", 2, 1, 1, None),
+        C(pt(False, 3, 1, 2), "n4", "sppm", 1, 2, 1, None),
+        C(pt(False, 3, 2, 2), "n4", "sppm", 2, 2, 1, None),
+        C(pt(False, 3, 1, 0, True), "n6", "render", 1, 0, 1, None),
+        C(pt(False, 3, 1, 2, True), "nested_fog", "sppm", 1, 2, 1, None),
+        C(pt(False, 3, 2, 2, True), "nested_fog", "sppm", 2, 2, 1, None),
+        # nested chains + a world-level medium on the accel walk, with and without a background
+        C(pt(True, 3, 2, 0, True), "nested_fog", "render", 2, 0, 0, None),
+        C(pt(False, 3, 2, 0, True), "nested_fog", "render", 2, 0, 1, None),
+        C(pt(True, 3, 2, 4, True), "nested_fog_sky", "render", 2, 0, 0, None),
+        C(pt(False, 3, 2, 4, True), "nested_fog_sky", "render", 2, 0, 1, None),
+        # the in-order-fold twins of kernel 2: frames of at least as many tiles as the launch has waves
+        C(pt(False, 0, 2, 0), "spheres", "render", 2, 0, 1, "fold"),
+        C(pt(False, 1, 2, 1), "cornell", "render", 2, 1, 1, "fold"),
+        C(pt(False, 1, 2, 2), "cornell", "sppm", 2, 2, 1, "fold"),
+        C(pt(True, 1, 2, 2), "cornell", "sppm", 2, 2, 0, "fold"),
+    ]
+
+
+def _instance_cases():
+    out = []
+    for (mixed, wide, tie), (n, inline, _) in sorted(INSTANCE_SCENES.items()):
+        key = _inst_key(n, inline, tie)
+        for integ in (0, 1, 2):
+            mode = "sppm" if integ == 2 else "render"
+            for early in (True, False):
+                name = coop(integ, mixed, early, wide, tie)
+                if name not in _COOP_BEFORE:
+                    out.append(Case(name, key, mode, 5, integ, 0, "early" if early else "late"))
+            if not wide:  # (kernel 6 has one pending-mask width)
+                name = wf(integ, mixed, tie)
+                if name not in _WF_BEFORE and name not in WITHHELD:
+                    out.append(Case(name, key, mode, 6, integ, 0, None))
+    return out
+
+
+CASES = _pt_cases() + _instance_cases()
+
+
+def lds_of(case):
+    """scene_in_lds the case's stats must show: pt_kernel's LDS parameter; kernels 5 / 6 never stage the whole scene"""
+    return int(case.kernel.startswith("pt_kernel<true")) if case.kernel_id in (1, 2) else 0

@@ -34,8 +34,20 @@ def compare(name, dev, ref, cols, rows=None):
 
 @pytest.mark.parametrize("name", list(sc.SHADE_FAMILIES))
 def test_shade_equals_the_oracle(name):
-    w, _, _ = world()
-    o, _ = sc.oracle_scene()
+    _shade_equals_the_oracle(name, True)
+
+
+@pytest.mark.parametrize("name", [n for n in sc.SHADE_FAMILIES if n != "noise"])
+def test_shade_without_a_noise_texture_equals_the_oracle(name):
+    """the same families on the scene built without the marble (the materials keep their indices: the marble is the last one): a scene
+    without a noise texture shades through the kernel form that holds no noise code (shade_eval_kernel<1>, as render_tiles chooses the
+    GENERAL == 1 variants), which the families above never launch"""
+    _shade_equals_the_oracle(name, False)
+
+
+def _shade_equals_the_oracle(name, noise):
+    w, _, _ = world(noise)
+    o, _ = sc.oracle_scene(noise)
     f = sc.family(name)
     dev = w.debug_shade(f["rows"], f["keys"])
     ref, draws = o.shade(f["rows"], f["keys"])

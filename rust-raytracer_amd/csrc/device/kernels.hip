@@ -921,8 +921,7 @@ DEV bool box32(float lox, float loy, float loz, float hix, float hiy, float hiz,
 // The stack.  A lane's stack is a column of LDS words, `stride` words apart (row k = entry k of every lane of the workgroup), and every
 // call of traverse2 owns the whole column: callers that run several walks for one ray (traverse2_media's TRACK / LIMIT walks, the
 // instance walks of kernels 5 / 6 after their DEFER walk) run them one after another, each from an empty stack.
-//   * WIDE (the LDS-resident node table): row 0 holds REF_DONE, written by traverse2 itself on entry (a resumed SLICE walk rewrites
-//     the value its column already has); the walk's entries start at row 1.  A pop is therefore unconditional -- `sp -= step;
+//   * WIDE (the LDS-resident node table): row 0 holds REF_DONE, written by traverse2 itself on entry; the walk's entries start at row 1.  A pop is therefore unconditional -- `sp -= step;
 //     cur = stk[sp]` -- and the pop of an empty stack returns the sentinel, on which the node loop and the outer loop both end.
 //     Nothing pops after that.  The plain form keeps its emptiness test and starts at row 0: measured, the sentinel gains it
 //     nothing (C4 / C5 reduced inside their spread) and costs the book-2 variant 5 % in spills.
@@ -954,29 +953,21 @@ DEV double track_bound(const MediaTrack& K, double best) {
 // for the NK_INSTANCE_INLINE items of scenes that have any: compiling the enter path into their world-space walk costs C4 6 %).
 // RESOLVE: an exact tie (TIE_FLAG) is settled before returning; false: the caller does it (traverse2_media: one call site for its two walks).
 // TIEDEF: a DEFER walk (kernels 5 / 6) notes exact ties among the world-level items as well; its caller settles them (RESOLVE is false there).
-// SLICE (round 5; the MEDIA variants of kernel 2): the walk can be SUSPENDED.  A wave stays in this loop until its longest ray is through:
-// on the book-2 final scene 7.9 descend-and-leaf rounds per walk where a lane needs 1.8 (phase statistics) -- a few rays cross
-// the 1000-sphere cluster or skim the ground boxes while the rest of the wave waits.  With SLICE the lanes that are still walking leave the
-// loop together as soon as fewer than `slice_th` of them are left (a wave-uniform test once per round); what a walk needs to go on -- the
-// node to continue at, the stack pointer (the stack itself stays in the lane's LDS column), the instance it is inside of; the best hit so
-// far goes back to the caller as the result -- is handed back in *ws, the finished lanes shade and start their next segment, and the
-// next call continues the suspended walks beside the fresh ones.  The walk itself is unchanged: same nodes, same order, same candidates,
-// hence the same hit.  (On the LDS-resident scenes the rounds' tail is short -- 3.5 rounds against 1.5 on the headline scene -- and the
-// slicing only costs registers: measured -1.4 % there, -21 % on the Cornell box; the switch RT_SLICE_TH compiles it into the MEDIA variants
-// alone, and it is OFF in the product: no gain there either, see RT_SLICE_TH.)
+// (Round 5 measured SUSPENDING the walk -- a wave stays in this loop until its longest ray is through: on the book-2 final scene 7.9
+// descend-and-leaf rounds per walk where a lane needs 1.8; the lanes still walking left the loop together once fewer than N of them were
+// left and resumed beside the fresh walks of the next iteration -- and rejected it: -1.4 % on the headline scene, -21 % on the Cornell box,
+// and in the MEDIA variants of kernel 2 alone, reduced book-2 scene, N = 24: 34 instead of 55 node steps and 3.6 instead of 7.9 leaf
+// sections per iteration, but 20 % more iterations, shading at 41 instead of 50 lanes and 25 more spilled registers: 836 against 849
+// Msamples/s (N = 12: 859; C5 as named 608 / 625 against 686).  DESIGN.md s5, profiles/r05/phase_c5r_sliced_th24.txt.  It is not in the
+// tree: commit 9057ee8 is the last that holds it, as -DRT_SLICE_TH=N.)
 // (Round 7 measured an EARLY EXIT from the node loop of the WIDE form -- the wave leaves it once lanes at a leaf >= 7/8 of the lanes still
 // walking, the others re-enter with cur and their stack untouched; two ballots' bit counts and a scalar compare per node step -- and
 // rejected it: headline 2 564-2 566 Msamples/s against the parent's 2 877-2 879, -10.9 %, where tools/walk_model.cpp had priced the
 // saved wave-steps at +1..2 %.  DESIGN.md s5-r7, profiles/r07/README.md.  It is not in the tree.)
-struct WalkState {
-    uint32_t cur;  // node / leaf to continue at; REF_DONE: no walk in progress
-    uint32_t sp;   // stack offset in words (WIDE: the LDS byte address)
-    int cur_xf;    // the instance the walk is inside of (xform index), -1: world space
-};
 template <int GENERAL, bool DEFER = false, bool TOP = true, bool WIDE = false, class PEND = uint32_t, bool LIMIT = false, bool ENTER = !DEFER, bool TRACK = false, bool RESOLVE = true,
-          bool TIEDEF = false, bool SLICE = false>
+          bool TIEDEF = false>
 DEV Hit traverse2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, double t_min, double t_max, PEND* pend = nullptr, uint32_t order_limit = 0xFFFFFFFFu,
-                  MediaTrack* track = nullptr, WalkState* ws = nullptr, const Hit* h_in = nullptr, int slice_th = 0) {
+                  MediaTrack* track = nullptr) {
     D3 o = wo, d = wd;
     Hit h;
     h.t = t_max;
@@ -984,24 +975,12 @@ DEV Hit traverse2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, d
     h.xf = -1;
     h.kp = 0;
     int cur_xf = -1;
-    const bool resume = SLICE && ws->cur != REF_DONE;
-    if (resume) {  // a suspended walk goes on: its best hit so far, and the ray in the space of the instance it is inside of
-        h = *h_in;
-        cur_xf = ws->cur_xf;
-        if (GENERAL == 3 && cur_xf >= 0) {
-            chain_ray(A, (uint32_t)cur_xf, CHAIN_ALL, o, d);
-        } else if (GENERAL && cur_xf >= 0) {
-            const double* Minv = A.xforms + 32 * cur_xf;
-            o = xf_point(Minv, wo);
-            d = xf_dir(Minv, wd);
-        }
-    }
     double a = sqlen(d);
     // exact ties are noted here unless the walk sees only a part of the scene (LIMIT: only t is used); a walk that defers instances
     // (kernels 5 / 6) notes them in its TIE variants (TIEDEF)
     constexpr bool TIE = TIE_RULE && GENERAL != 0 && (!DEFER || TIEDEF) && !LIMIT && !(TRACK && RT_TIE_NOTRACK);
-    Ray32 r = make_ray32(o, d, t_min, (SLICE && TRACK) ? track_bound(*track, h.t) : (SLICE ? h.t : t_max));
-    float best_all32 = SLICE ? ray32_best(h.t) : r.best;  // TRACK: the best hit's own (outward-rounded) t, beside r.best = the track bound
+    Ray32 r = make_ray32(o, d, t_min, t_max);
+    float best_all32 = r.best;  // TRACK: the best hit's own (outward-rounded) t, beside r.best = the track bound
     if (WIDE) ray32_wide_addr(r, A.n2w_lds);
     int sp = 0;  // stack offset in words (a multiple of stride): avoids an integer multiply per push/pop
     // WIDE: the stack pointer is the LDS byte address itself (one add per push / pop instead of shift-add + add)
@@ -1010,17 +989,7 @@ DEV Hit traverse2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, d
     uint32_t spw = WIDE ? (uint32_t)(uintptr_t)(AS_L uint32_t*)stk + spw_step : 0u;
     if (WIDE) *(AS_L uint32_t*)stk = REF_DONE;
     uint32_t cur = WIDE ? wide_ref(A.root2) : A.root2;
-    if (resume) {
-        cur = ws->cur;
-        if (WIDE) spw = ws->sp;
-        else sp = (int)ws->sp;
-    }
-    bool suspended = false;
     for (;;) {
-        if (SLICE && (int)__popcll(__ballot(1)) < slice_th) {  // (the lanes whose walks are over have left the loop: the ballot counts the walkers)
-            suspended = true;
-            break;
-        }
         while ((cur >> REF_TAG_SHIFT) == 0u) {  // inner node: test both children
             PH_EV(10);
 #ifdef RTAMD_PHASE_STATS
@@ -1223,12 +1192,6 @@ DEV Hit traverse2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, d
         }
         PH_END(9, ph_leaf0);
     }
-    if (SLICE) {
-        ws->cur = suspended ? cur : REF_DONE;
-        ws->sp = WIDE ? spw : (uint32_t)sp;
-        ws->cur_xf = cur_xf;
-        if (suspended) return h;  // (its flag, if any, travels in h.xf)
-    }
     // the last exact tie noted, if its later party is still the hit: would the reference have visited that object at all?
     if (TIE && RESOLVE && tie_flagged(h.xf)) h = tie_resolve<GENERAL>(A, wo, wd, t_min, t_max, h);
     return h;
@@ -1295,12 +1258,8 @@ DEV bool medium_boundary(const Acc& A, const MediumDev& M, D3 o, D3 d, double& t
     t_b = r2h.t;
     return true;
 }
-// SLICE: the accel walk of step 2 may come back SUSPENDED (traverse2's SLICE: ws->cur != REF_DONE; the result is then its best hit so far and
-// t_save[] the two tracked minima): the caller skips the shading and calls again next iteration; step 1 is then repeated (it draws no random
-// number and its results depend on the ray alone), the walk resumes, and steps 3 run once, when the walk is over.
-template <int GENERAL, bool TOP, bool WIDE, bool SLICE = false>
-DEV Hit traverse2_media(const Acc& A, uint32_t n_media, uint32_t* stk, const int stride, D3 o, D3 d, double t_min, Rng& rng, WalkState* ws = nullptr, const Hit* h_in = nullptr,
-                        double* t_save = nullptr, int slice_th = 0) {
+template <int GENERAL, bool TOP, bool WIDE>
+DEV Hit traverse2_media(const Acc& A, uint32_t n_media, uint32_t* stk, const int stride, D3 o, D3 d, double t_min, Rng& rng) {
     // 1. the boundary queries of the media (no random number is drawn here); the first two media the ray crosses are TRACKED by the
     //    accel walk (MediaTrack), so that one walk yields the closest surface S and, for each of the two, the closest surface the
     //    reference visits before it.  (A second, order-restricted walk per medium -- the first version -- cost more than the
@@ -1326,18 +1285,8 @@ DEV Hit traverse2_media(const Acc& A, uint32_t n_media, uint32_t* stk, const int
         }
     }
     // 2. the accel walk
-    if (SLICE && ws->cur != REF_DONE) {  // a suspended walk goes on: what it had tracked so far
-        K.T[0] = t_save[0];
-        K.T[1] = t_save[1];
-    }
-    Hit S = (tk0 != 0xFFFFFFFFu)
-                ? traverse2<GENERAL, false, TOP, WIDE, uint32_t, false, true, true, false, false, SLICE>(A, stk, stride, o, d, t_min, INFINITY, nullptr, 0xFFFFFFFFu, &K, ws, h_in, slice_th)
-                : traverse2<GENERAL, false, TOP, WIDE, uint32_t, false, true, false, false, false, SLICE>(A, stk, stride, o, d, t_min, INFINITY, nullptr, 0xFFFFFFFFu, nullptr, ws, h_in, slice_th);
-    if (SLICE && ws->cur != REF_DONE) {  // suspended: the rest happens when the walk is over
-        t_save[0] = K.T[0];
-        t_save[1] = K.T[1];
-        return S;
-    }
+    Hit S = (tk0 != 0xFFFFFFFFu) ? traverse2<GENERAL, false, TOP, WIDE, uint32_t, false, true, true, false>(A, stk, stride, o, d, t_min, INFINITY, nullptr, 0xFFFFFFFFu, &K)
+                                 : traverse2<GENERAL, false, TOP, WIDE, uint32_t, false, true, false, false>(A, stk, stride, o, d, t_min, INFINITY);
     if (TIE_RULE && GENERAL && tie_flagged(S.xf)) S = tie_resolve<GENERAL>(A, o, d, t_min, INFINITY, S);  // two surfaces share the best t ("EXACT ties" above)
     // 3. the media in the reference's order
     Hit best = S;
@@ -2307,14 +2256,6 @@ __device__ __attribute__((noinline)) UnitInfo next_unit(uint32_t* wst_, uint32_t
 }
 
 // GENERAL: 0 = spheres under BVH nodes only, 1 = every primitive of the reference, 2 = 1 + the book-2 extensions (D9: moving spheres, noise textures, an open shutter)
-// A/B switch, OFF in the product (measured and rejected in round 5): with -DRT_SLICE_TH=N the MEDIA variants of kernel 2 suspend
-// their accel walks (traverse2's SLICE) once fewer than N lanes of the wave are still walking -- at most half of those that entered the walk,
-// so that a wave with few paths left (the end of a launch) still moves.  Reduced book-2 scene, N = 24: 34 instead of 55 node steps and 3.6 instead
-// of 7.9 leaf sections per iteration, 20 % more iterations, shading at 41 instead of 50 lanes, 25 more spilled registers: 836 against 849
-// Msamples/s (N = 12: 859; C5 as named 608 / 625 against 686) -- profiles/r05/phase_c5r_sliced_th24.txt.
-#ifndef RT_SLICE_TH
-#define RT_SLICE_TH 0
-#endif
 // A/B switch, ON in the product (round 7): 0 leaves the NodeW rows of kernel 2 with the blob's pads (box_shrink = 0 in every launch)
 #ifndef RT_TIGHTEN_BOXES
 #define RT_TIGHTEN_BOXES 1
@@ -2428,14 +2369,6 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
     const unsigned long long tail_t0 = __builtin_amdgcn_s_memrealtime();
 #endif
     int fold_wait = 0;  // iterations until the head of the ring is looked at again (wave-uniform)
-    constexpr bool SLICE = ACCEL == 2 && MEDIA && RT_SLICE_TH > 0;
-    WalkState ws;  // SLICE: this lane's suspended walk (cur == REF_DONE: none), its best hit so far and the two tracked minima
-    ws.cur = REF_DONE;
-    ws.sp = 0u;
-    ws.cur_xf = -1;
-    Hit hs;
-    hs.t = INFINITY; hs.node = -1; hs.xf = -1; hs.kp = 0;
-    double ws_t[2] = {INFINITY, INFINITY};
 #ifdef RTAMD_PHASE_STATS
     if (threadIdx.x < 48) s_ph[threadIdx.x] = 0ull;
     __syncthreads();
@@ -2523,18 +2456,10 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
             if (alive) {
                 PH_EV(13);
                 PH_BEGIN(ph_t0);
-                Hit h;
-                if (SLICE) {  // the walk goes on until fewer than slice_th lanes are left in it; those come back next iteration (ws.cur != REF_DONE)
-                    const int n_walk = (int)__popcll(__ballot(1));
-                    h = traverse2_media<GENERAL, !LDS, LDS, true>(A, sv.n_media, stk, stk_stride, o, d, rk.t_min, rng, &ws, &hs, ws_t, min((int)RT_SLICE_TH, n_walk >> 1));
-                    hs = h;
-                } else {
-                    h = (ACCEL == 2) ? (MEDIA ? traverse2_media<GENERAL, !LDS, LDS>(A, sv.n_media, stk, stk_stride, o, d, rk.t_min, rng)
-                                               : traverse2<GENERAL, false, !LDS, LDS>(A, stk, stk_stride, o, d, rk.t_min, INFINITY))
+                Hit h = (ACCEL == 2) ? (MEDIA ? traverse2_media<GENERAL, !LDS, LDS>(A, sv.n_media, stk, stk_stride, o, d, rk.t_min, rng)
+                                              : traverse2<GENERAL, false, !LDS, LDS>(A, stk, stk_stride, o, d, rk.t_min, INFINITY))
                                      : traverse<GENERAL, MEDIA>(A, o, d, rk.t_min, INFINITY, &rng);
-                }
                 PH_END(1, ph_t0);
-              if (!SLICE || ws.cur == REF_DONE) {
                 PH_BEGIN(ph_p0);
                 bool done = true;
                 if (h.node >= 0 && depth > 0) {  // Q12: depth test after the hit, before emission
@@ -2581,7 +2506,6 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
                     alive = false;
                 }
                 PH_END(8, ph_p0);
-              }
             }
         }
     }
@@ -4222,65 +4146,84 @@ size_t release_workspaces() {  // frees every idle workspace (all devices); retu
 typedef void (*pt_fn)(FlatView, CamK, RenderK, double*, double*, unsigned int*, unsigned int*, int*);
 typedef void (*pt_coop_fn)(FlatView, CamK, RenderK, double*, double*, unsigned int*, unsigned int*, int*, uint64_t*);
 
-template <int ACCEL>
-static pt_fn pick_pt_kernel(bool lds, bool general, int integ) {
-    if (integ == 1) return lds ? pt_kernel<true, true, ACCEL, 1> : pt_kernel<false, true, ACCEL, 1>;  // mixture / SPPM: general primitive set only
-    if (integ == 2) return lds ? pt_kernel<true, true, ACCEL, 2> : pt_kernel<false, true, ACCEL, 2>;
-    return lds ? (general ? pt_kernel<true, true, ACCEL, 0> : pt_kernel<true, false, ACCEL, 0>)
-               : (general ? pt_kernel<false, true, ACCEL, 0> : pt_kernel<false, false, ACCEL, 0>);
-}
-// the POOL variants (out-of-order fold for a rank that owns fewer tiles than the GPU has waves) exist for kernel 2
-static pt_fn pick_pt_kernel_pool(bool lds, bool general, int integ) {
-    if (integ == 1) return lds ? pt_kernel<true, true, 2, 1, false, true> : pt_kernel<false, true, 2, 1, false, true>;
-    if (integ == 2) return lds ? pt_kernel<true, true, 2, 2, false, true> : pt_kernel<false, true, 2, 2, false, true>;
-    return lds ? (general ? pt_kernel<true, true, 2, 0, false, true> : pt_kernel<true, false, 2, 0, false, true>)
-               : (general ? pt_kernel<false, true, 2, 0, false, true> : pt_kernel<false, false, 2, 0, false, true>);
-}
-// the background variants (INTEG | INTEG_BG) of kernels 1 and 2: integrators 0 and 1 on the same GENERAL / MEDIA choices as
-// without a background (g: 0 spheres only, 1 general, 2 book 2, 3 nested chains; integrator 1 runs on g >= 1, MEDIA with integrator 0 only)
-template <int ACCEL, bool LDS>
-static pt_fn pick_pt_kernel_bg(int g, bool media, int integ) {
-    constexpr int B = INTEG_BG;
-    if (g == 0) return pt_kernel<LDS, 0, ACCEL, B>;
-    if (g == 1) return media ? pt_kernel<LDS, 1, ACCEL, B, true> : (integ == 1) ? pt_kernel<LDS, 1, ACCEL, B | 1> : pt_kernel<LDS, 1, ACCEL, B>;
-    if (g == 2) return media ? pt_kernel<LDS, 2, ACCEL, B, true> : pt_kernel<LDS, 2, ACCEL, B>;
-    return media ? pt_kernel<LDS, 3, ACCEL, B, true> : (integ == 1) ? pt_kernel<LDS, 3, ACCEL, B | 1> : pt_kernel<LDS, 3, ACCEL, B>;
-}
-// the env sampling variants (INTEG_ENV on top of 1 | INTEG_BG): integrator 1 where pick_pt_kernel_bg returns a B | 1 variant
-template <int ACCEL, bool LDS>
-static pt_fn pick_pt_kernel_env(bool nest) {
-    constexpr int E = INTEG_ENV | INTEG_BG | 1;
-    return nest ? pt_kernel<LDS, 3, ACCEL, E> : pt_kernel<LDS, 1, ACCEL, E>;
-}
-// the area light variants (INTEG_AREA on top of 1 | INTEG_BG): integrator 1 of a scene with area lights, whatever its background
-template <int ACCEL, bool LDS>
-static pt_fn pick_pt_kernel_area(bool nest) {
-    constexpr int E = INTEG_AREA | INTEG_BG | 1;
-    return nest ? pt_kernel<LDS, 3, ACCEL, E> : pt_kernel<LDS, 1, ACCEL, E>;
+// ---- the pt_kernel variants: every instantiation is named in PT_VARIANTS, once, and nowhere else ----
+// A row is one <GENERAL, INTEG, MEDIA> and exists for kernels 1 and 2, with the scene in LDS or not.  GENERAL: 0 spheres only, 1 general,
+// 2 book 2, 3 nested chains (SceneVariant::g()).  INTEG: integrator 0 / 1 / 2; | INTEG_BG with a background; 1 | INTEG_BG |
+// INTEG_ENV with the background as a light (s4h); 1 | INTEG_BG | INTEG_AREA with area lights, whatever the background (s4i).  Integrators
+// 1 and 2 run on the general primitive set only; integrator 1 never with MEDIA, the book-2 kinds with integrator 0 only, the SPPM pass
+// without a background.  The POOL rows (out-of-order fold for a rank that owns fewer tiles than the GPU has waves) exist for kernel 2.
+#define PT_ROW(X, G, I, M) X(false, G, 1, I, M, false) X(true, G, 1, I, M, false) X(false, G, 2, I, M, false) X(true, G, 2, I, M, false)
+#define PT_ROW_POOL(X, G, I) X(false, G, 2, I, false, true) X(true, G, 2, I, false, true)
+#define PT_VARIANTS(X)                                                                                                     \
+    PT_ROW(X, 0, 0, false) PT_ROW(X, 0, INTEG_BG, false)                                                                   \
+    PT_ROW(X, 1, 0, false) PT_ROW(X, 1, 0, true) PT_ROW(X, 1, INTEG_BG, false) PT_ROW(X, 1, INTEG_BG, true)                \
+    PT_ROW(X, 1, 1, false) PT_ROW(X, 1, INTEG_BG | 1, false)                                                               \
+    PT_ROW(X, 1, INTEG_ENV | INTEG_BG | 1, false) PT_ROW(X, 1, INTEG_AREA | INTEG_BG | 1, false)                           \
+    PT_ROW(X, 1, 2, false) PT_ROW(X, 1, 2, true)                                                                           \
+    PT_ROW(X, 2, 0, false) PT_ROW(X, 2, 0, true) PT_ROW(X, 2, INTEG_BG, false) PT_ROW(X, 2, INTEG_BG, true)                \
+    PT_ROW(X, 3, 0, false) PT_ROW(X, 3, 0, true) PT_ROW(X, 3, INTEG_BG, false) PT_ROW(X, 3, INTEG_BG, true)                \
+    PT_ROW(X, 3, 1, false) PT_ROW(X, 3, INTEG_BG | 1, false)                                                               \
+    PT_ROW(X, 3, INTEG_ENV | INTEG_BG | 1, false) PT_ROW(X, 3, INTEG_AREA | INTEG_BG | 1, false)                           \
+    PT_ROW(X, 3, 2, false) PT_ROW(X, 3, 2, true)                                                                           \
+    PT_ROW_POOL(X, 0, 0) PT_ROW_POOL(X, 1, 0) PT_ROW_POOL(X, 1, 1) PT_ROW_POOL(X, 1, 2)
+struct PtKey {
+    bool lds;
+    int general, accel, integ;
+    bool media, pool;
+    bool operator==(const PtKey& o) const {
+        return lds == o.lds && general == o.general && accel == o.accel && integ == o.integ && media == o.media && pool == o.pool;
+    }
+};
+struct PtVariant {
+    PtKey key;
+    pt_fn fn;
+};
+#define PT_ENTRY(L, G, A, I, M, P) {{L, G, A, I, M, P}, pt_kernel<L, G, A, I, M, P>},
+static const PtVariant PT_TABLE[] = {PT_VARIANTS(PT_ENTRY)};
+#undef PT_ENTRY
+static_assert(sizeof(PT_TABLE) / sizeof(PT_TABLE[0]) == 112, "PT_VARIANTS: 26 rows x 4 + 4 POOL rows x 2");
+static pt_fn pt_variant(const PtKey& k) {
+    for (const PtVariant& v : PT_TABLE)
+        if (v.key == k) return v.fn;
+    throw RtError(RT_ERR_INTERNAL, "no pt_kernel<" + std::to_string(k.lds) + ", " + std::to_string(k.general) + ", " + std::to_string(k.accel) + ", " + std::to_string(k.integ) +
+                                       ", " + std::to_string(k.media) + ", " + std::to_string(k.pool) + "> is compiled (PT_VARIANTS)");
 }
 
-static void render_tiles_wf(const rt_scene& s, const FlatView& view, const CameraDev& cam, const RenderPlan& plan, const Tuning& tun, double* d_tiles,
-                            hipStream_t stream, rt_stats* st, int dev, const DevInfo& di, uint32_t stack6, uint32_t n_entry6, size_t lds_pt, uint32_t stack6w,
-                            size_t tables_w);
+// ---- the pt_kernel_coop variants, likewise: <INTEG, MIXED, EARLY, PEND, TIE> ----
+// MIXED: the scene has inline instances too; PEND: uint64_t for 33..64 instances (the MIXED code covers scenes without inline instances
+// too); EARLY: the twin that folds from the main loop; TIE: tie_scene().  A row exists for the three integrators, EARLY and TIE or not.
+#define COOP_ROW(X, M, W)                                                                                                 \
+    X(0, M, false, W, false) X(0, M, false, W, true) X(0, M, true, W, false) X(0, M, true, W, true) X(1, M, false, W, false) \
+    X(1, M, false, W, true) X(1, M, true, W, false) X(1, M, true, W, true) X(2, M, false, W, false) X(2, M, false, W, true) \
+    X(2, M, true, W, false) X(2, M, true, W, true)
+#define COOP_VARIANTS(X) COOP_ROW(X, false, false) COOP_ROW(X, true, false) COOP_ROW(X, true, true)
+template <bool WIDE>
+using coop_pend = typename std::conditional<WIDE, uint64_t, uint32_t>::type;
+struct CoopKey {
+    int integ;
+    bool mixed, early, wide, tie;
+    bool operator==(const CoopKey& o) const { return integ == o.integ && mixed == o.mixed && early == o.early && wide == o.wide && tie == o.tie; }
+};
+struct CoopVariant {
+    CoopKey key;
+    pt_coop_fn fn;
+};
+#define COOP_ENTRY(I, M, E, W, T) {{I, M, E, W, T}, pt_kernel_coop<I, M, E, coop_pend<W>, T>},
+static const CoopVariant COOP_TABLE[] = {COOP_VARIANTS(COOP_ENTRY)};
+#undef COOP_ENTRY
+static_assert(sizeof(COOP_TABLE) / sizeof(COOP_TABLE[0]) == 36, "COOP_VARIANTS: 3 rows x 12");
+static pt_coop_fn coop_variant(const CoopKey& k) {
+    for (const CoopVariant& v : COOP_TABLE)
+        if (v.key == k) return v.fn;
+    throw RtError(RT_ERR_INTERNAL, "no pt_kernel_coop<" + std::to_string(k.integ) + ", " + std::to_string(k.mixed) + ", " + std::to_string(k.early) + ", " +
+                                       (k.wide ? "uint64_t" : "uint32_t") + ", " + std::to_string(k.tie) + "> is compiled (COOP_VARIANTS)");
+}
 
 // Kernels 5 / 6 run their TIE variants ("EXACT ties" above traverse<>) for every scene that holds a rectangle or a cube: only those have
 // boxes that can BEGIN exactly where another surface lies (bvh.rs:88 + aabb.rs:28-30).  Scenes of spheres and triangle meshes alone keep the
 // variants without the flag (as the sphere-only variants of kernels 1 / 2 carry no tie code).
 static bool tie_scene(const FlatView& v) {
     return TIE_RULE != 0 && (v.kinds_mask & ((1u << NK_RECT_YZ) | (1u << NK_RECT_XZ) | (1u << NK_RECT_XY) | (1u << NK_CUBE))) != 0u;
-}
-template <bool TIE>
-static void pick_coop(int integ, bool mixed, bool wide, pt_coop_fn& fn, pt_coop_fn& fn_early) {
-    if (wide) {
-        fn_early = (integ == 1) ? pt_kernel_coop<1, true, true, uint64_t, TIE> : (integ == 2) ? pt_kernel_coop<2, true, true, uint64_t, TIE> : pt_kernel_coop<0, true, true, uint64_t, TIE>;
-        fn = (integ == 1) ? pt_kernel_coop<1, true, false, uint64_t, TIE> : (integ == 2) ? pt_kernel_coop<2, true, false, uint64_t, TIE> : pt_kernel_coop<0, true, false, uint64_t, TIE>;
-    } else if (mixed) {
-        fn_early = (integ == 1) ? pt_kernel_coop<1, true, true, uint32_t, TIE> : (integ == 2) ? pt_kernel_coop<2, true, true, uint32_t, TIE> : pt_kernel_coop<0, true, true, uint32_t, TIE>;
-        fn = (integ == 1) ? pt_kernel_coop<1, true, false, uint32_t, TIE> : (integ == 2) ? pt_kernel_coop<2, true, false, uint32_t, TIE> : pt_kernel_coop<0, true, false, uint32_t, TIE>;
-    } else {
-        fn_early = (integ == 1) ? pt_kernel_coop<1, false, true, uint32_t, TIE> : (integ == 2) ? pt_kernel_coop<2, false, true, uint32_t, TIE> : pt_kernel_coop<0, false, true, uint32_t, TIE>;
-        fn = (integ == 1) ? pt_kernel_coop<1, false, false, uint32_t, TIE> : (integ == 2) ? pt_kernel_coop<2, false, false, uint32_t, TIE> : pt_kernel_coop<0, false, false, uint32_t, TIE>;
-    }
 }
 
 // Which pt_kernel family a scene takes (host only).  moving / book2 / general / nest / media are render_tiles' own predicates: GENERAL is
@@ -4303,66 +4246,77 @@ static SceneVariant scene_variant(const rt_scene& s, bool open_shutter) {
     return v;
 }
 
-void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& plan_in, double* d_tiles, void* stream_, rt_stats* st) {
-    if (!s.committed) throw RtError(RT_ERR_NOT_COMMITTED, "scene not committed");
-    const Tuning tun = tuning();  // one snapshot per call
-    const RenderPlan& plan = plan_in;
-    hipStream_t stream = (hipStream_t)stream_;
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    const DevInfo& di = dev_info(dev);
-
-    FlatView view = s.flat.view;
-    double upload_ms = 0.;
-    uint64_t env_total = 0;
-    view.base = device_blob(s, dev, &upload_ms, &env_total);
-    if (st) st->upload_ms = upload_ms;
+// ---- stage 1 of render_tiles: which kernel renders the call, or why none does ----
+struct KernelChoice {
+    int kernel = 0;  // 1, 2, 5 or 6: plan.kernel, or what the automatic rule made of 0
+    bool lds = false;  // kernels 1 / 2: the scene's hot tables are staged into LDS
+    bool bg = false, env = false, area = false;  // the scene has a background; an env table that is not black; area lights and integrator 1
+    SceneVariant variant{};
+    size_t lds_max = 0;  // the device's LDS, less the time slots of a scene with moving spheres
+    double cam_abs = 0.;  // largest |coordinate| of a point on the lens
+    size_t hot_bytes = 0, stack_bytes = 0;  // kernels 1 / 2 / 5: the staged tables; the stacks and bookkeeping behind them
+    uint32_t stack5 = 0;  // kernel 5: rows of a lane's stack
+    // kernel 6: stack rows and entry nodes of the path launch and its LDS; stack rows and world tables of the walk launch
+    uint32_t stack6 = 0, n_entry6 = 0, stack6w = 0;
+    size_t wf_lds_pt = 0, wf_tables_w = 0;
+};
+// The one place that computes pt_kernel's template arguments from the predicates (DESIGN.md s4 "Kernel selection")
+static PtKey pt_key(const KernelChoice& c, int integ, bool pool) {
+    const SceneVariant& v = c.variant;
+    const int general = std::max(v.g(), (v.media || integ != 0) ? 1 : 0);  // media, mixture and SPPM: general primitive set only
+    // (area implies integrator 1; media and the book-2 kinds were refused for integrator 1: GENERAL is 1 or 3 under ENV / AREA.  The AREA
+    // variant tests the background and the env table at run time)
+    const int i = c.area ? (INTEG_AREA | INTEG_BG | 1) : (c.bg && c.env && integ == 1) ? (INTEG_ENV | INTEG_BG | 1) : integ | (c.bg ? INTEG_BG : 0);
+    return PtKey{c.lds, general, c.kernel, i, v.media, pool && c.kernel == 2};
+}
+static KernelChoice choose_kernel(const rt_scene& s, const FlatView& view, const CameraDev& cam, const RenderPlan& plan, const Tuning& tun, const DevInfo& di,
+                                  uint64_t env_total) {
+    KernelChoice c;
     // env sampling: the background is a light of integrator 1 -- unless its table sums to zero (a black background)
-    const bool env = view.off_env != 0u && env_total != 0ull;
-    const SceneVariant variant = scene_variant(s, plan.time1 > plan.time0);
-    const bool moving = variant.moving, book2 = variant.book2;
+    c.env = view.off_env != 0u && env_total != 0ull;
+    const SceneVariant variant = c.variant = scene_variant(s, plan.time1 > plan.time0);
+    const bool moving = variant.moving, book2 = variant.book2, general = variant.general, nest = variant.nest, media = variant.media;
     if (moving) {  // a moving sphere's box covers its positions between ITS time0 and time1 only (scene.cpp: add_moving_sphere)
         const double sh0 = plan.time0, sh1 = plan.time1 > plan.time0 ? plan.time1 : plan.time0;
         if (!(sh0 >= s.flat.msph_t0_max && sh1 <= s.flat.msph_t1_min))
             throw RtError(RT_ERR_ARG, "the shutter [time0, time1] = [" + std::to_string(sh0) + ", " + std::to_string(sh1) + "] must lie inside [time0, time1] of every moving sphere ([" +
                                           std::to_string(s.flat.msph_t0_max) + ", " + std::to_string(s.flat.msph_t1_min) + "] for this scene): their boxes are built for that range");
     }
-    const bool general = variant.general, nest = variant.nest;
-    const size_t lds_max = di.lds_max - (moving ? (size_t)PT_BLOCK * sizeof(double) : 0);
+    const size_t lds_max = c.lds_max = di.lds_max - (moving ? (size_t)PT_BLOCK * sizeof(double) : 0);
     // The accel kernels need the camera inside the region the f32 boxes were padded for (flatten.cpp: origin_limit2) and
     // t_min >= 0 (box32's proof); otherwise kernel 1 (reference order) renders.
-    double cam_abs = std::fmax(std::fmax(std::fabs(cam.origin[0]), std::fabs(cam.origin[1])), std::fabs(cam.origin[2])) + std::fabs(cam.lens_radius);
+    const double cam_abs = c.cam_abs =
+        std::fmax(std::fmax(std::fabs(cam.origin[0]), std::fabs(cam.origin[1])), std::fabs(cam.origin[2])) + std::fabs(cam.lens_radius);
     const bool camera_ok = cam_abs <= view.origin_limit2 && std::isfinite(cam_abs) && plan.t_min >= 0.;
     const size_t stack2_bytes = walk_stack_bytes(view.stack2, PT_BLOCK);
     const size_t hot1 = (size_t)view.stage_bytes, hot2 = (size_t)(view.stage2_end - view.stage2_begin);
     const bool accel2_usable = view.accel_ok && camera_ok && stack2_bytes <= lds_max;  // per-lane stacks live in LDS
-    const bool media = variant.media;
     // kernel 5 = kernel 2's BVH with the cooperative instance service (pt_kernel_coop): for scenes with LARGE mesh instances
     // the two walks of kernel 5 never share a stack; the world-space walk includes the instances it enters in the lane (NK_INSTANCE_INLINE)
-    const uint32_t stack5 = coop_stack_rows(view);
-    const size_t stack5_bytes = walk_stack_bytes(stack5, PT_BLOCK);
+    c.stack5 = coop_stack_rows(view);
+    const size_t stack5_bytes = walk_stack_bytes(c.stack5, PT_BLOCK);
     const size_t coop_world = coop_world_bytes(view);  // world-level tables, always in LDS for this kernel
     const size_t coop_lds = (size_t)3 * COOP_RING * sizeof(uint16_t) + 8 * sizeof(uint32_t) + ((sizeof(CoopArgs) + 15) & ~size_t(15)) + coop_world;  // + three rings of pool-slot ids, counters, argument block
     const bool coop_usable = accel2_usable && general && !media && !book2 && view.coop_data_ok != 0 && view.n_inst2 >= 1 && view.n_inst2 <= (uint32_t)COOP_MAX_INST &&
                              view.inst_depth2 <= (uint32_t)COOP_STACK_MAX && coop_world <= 32768 && stack5_bytes + coop_lds <= lds_max && plan.max_depth < (1 << 24);
     // kernel 6 = the same instance service across the whole GPU and across launches (wavefront.inc)
-    const uint32_t stack6 = std::max<uint32_t>(std::max(view.world_depth2 + 2u, view.stack2_inline), (uint32_t)WF_ENTRY_STACK + 1u);
-    const uint32_t n_entry6 = std::min<uint32_t>((uint32_t)COOP_ENTRY_NODES, view.n_nodes2);
-    const size_t wf_lds_pt = coop_world + (size_t)std::min<uint32_t>(128u, view.world_top2) * sizeof(Node2) + (size_t)n_entry6 * sizeof(NodeQ) +
-                             walk_stack_bytes(stack6, PT_BLOCK) + ((size_t)WF_BOOK_WORDS + CFG_WORDS + 8) * sizeof(uint32_t);
-    const uint32_t stack6w = view.inst_depth2 + 2u;
-    const size_t wf_tables_w = coop_a16(view.stage_bytes - view.off_xforms) + coop_a16(8u * view.n_inst2) + coop_a16((uint32_t)sizeof(QGrid) * view.n_inst2);
-    const size_t wf_lds_walk_min = wf_tables_w + walk_stack_bytes(stack6w, WF_WALK_BLOCK);
+    c.stack6 = std::max<uint32_t>(std::max(view.world_depth2 + 2u, view.stack2_inline), (uint32_t)WF_ENTRY_STACK + 1u);
+    c.n_entry6 = std::min<uint32_t>((uint32_t)COOP_ENTRY_NODES, view.n_nodes2);
+    c.wf_lds_pt = coop_world + (size_t)std::min<uint32_t>(128u, view.world_top2) * sizeof(Node2) + (size_t)c.n_entry6 * sizeof(NodeQ) +
+                  walk_stack_bytes(c.stack6, PT_BLOCK) + ((size_t)WF_BOOK_WORDS + CFG_WORDS + 8) * sizeof(uint32_t);
+    c.stack6w = view.inst_depth2 + 2u;
+    c.wf_tables_w = coop_a16(view.stage_bytes - view.off_xforms) + coop_a16(8u * view.n_inst2) + coop_a16((uint32_t)sizeof(QGrid) * view.n_inst2);
+    const size_t wf_lds_walk_min = c.wf_tables_w + walk_stack_bytes(c.stack6w, WF_WALK_BLOCK);
     const bool wf_usable = accel2_usable && general && !media && !book2 && view.coop_data_ok != 0 && view.n_inst2 >= 1 && view.n_inst2 <= (uint32_t)WF_MAX_INST &&
-                           coop_world <= 32768 && wf_lds_pt <= lds_max && wf_lds_walk_min <= lds_max && plan.max_depth < (1 << 24);
+                           coop_world <= 32768 && c.wf_lds_pt <= lds_max && wf_lds_walk_min <= lds_max && plan.max_depth < (1 << 24);
     // a background (rt_scene_set_background): kernels 1 and 2 only (kernels 5 / 6 have no background variants), never the SPPM pass
-    const bool bg = view.off_bg != 0u;
+    const bool bg = c.bg = view.off_bg != 0u;
     int kernel = plan.kernel;
     if (bg && (kernel == 5 || kernel == 6))
         throw RtError(RT_ERR_UNSUPPORTED, "kernels 5 / 6 have no background variant: a scene with a background renders with kernel 1 or 2 (kernel 0 picks one)");
     if (bg && plan.integrator == 2) throw RtError(RT_ERR_UNSUPPORTED, "the SPPM integrator has no background (the photon pass has no environment emitter)");
     // area lights (rt_scene_set_area_lights): strategies of integrator 1 on kernels 1 and 2; integrator 0 ignores them
-    const bool area = view.off_area != 0u && plan.integrator == 1;
+    const bool area = c.area = view.off_area != 0u && plan.integrator == 1;
     if (area && (kernel == 5 || kernel == 6))
         throw RtError(RT_ERR_UNSUPPORTED, "kernels 5 / 6 have no area light variant: integrator 1 renders a scene with area lights with kernel 1 or 2 (kernel 0 picks one)");
     if (view.off_area != 0u && plan.integrator == 2)
@@ -4383,210 +4337,130 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
     if ((kernel == 2 || kernel == 5) && !accel2_usable)
         throw RtError(RT_ERR_UNSUPPORTED, "kernel 2 requested but no usable accel for this scene/camera (unbounded item, depth overflow, stacks "
                                           "larger than LDS, negative t_min, or camera farther than 64x the scene extent); use kernel 0/1");
+    c.kernel = kernel;
     const size_t ring_meta = ((size_t)(PT_BLOCK / 64) * (RING_UNITS * 4 + 8) + CFG_WORDS) * sizeof(uint32_t);  // ring / job bookkeeping, behind the stacks
-    const size_t stack_bytes = ((kernel == 2) ? stack2_bytes : (kernel == 5) ? stack5_bytes : 0) + ring_meta + ((kernel == 5) ? coop_lds : 0);
+    c.stack_bytes = ((kernel == 2) ? stack2_bytes : (kernel == 5) ? stack5_bytes : 0) + ring_meta + ((kernel == 5) ? coop_lds : 0);
     if (plan.tile_list && !plan.ext_accum) throw RtError(RT_ERR_INTERNAL, "a tile list needs the caller's (compact) accumulator");
     if (plan.ext_accum && (kernel == 6 || plan.integrator == 2))
         throw RtError(RT_ERR_UNSUPPORTED, "resumable rendering (rt_render_accumulate_device) runs with kernels 1 / 2 / 5 and integrators 0 / 1");
-    if (kernel == 6) {
-        render_tiles_wf(s, view, cam, plan, tun, d_tiles, stream, st, dev, di, stack6, n_entry6, wf_lds_pt, stack6w, wf_tables_w);
-        return;
-    }
+    const int integ = plan.integrator;
+    // (kernel 6 has no background or area light variants: its integrator 1 samples the object lights alone)
+    if (integ == 1 && view.n_lights == 0 && (kernel == 6 || (!c.env && !area))) throw RtError(RT_ERR_ARG, "integrator 1 (light importance sampling) needs rt_scene_set_lights");
+    if (integ == 2 && !plan.sppm_est) throw RtError(RT_ERR_ARG, "integrator 2 (SPPM) is reached through rt_render_sppm");
+    if (kernel == 6) return c;  // (scene in L2 / HBM always; media and the book-2 kinds made it unusable above)
     // kernel 2 expands the Node2 array (64 B per node) into the NodeW form (96 B) while staging it
     const size_t nodew = ((size_t)(view.n_nodes2 + NODEW_CHUNK - 1) / NODEW_CHUNK) * 3 * NODEW_FAR;
-    const size_t hot_bytes = (kernel == 2 || kernel == 5) ? hot2 - (size_t)view.n_nodes2 * sizeof(Node2) + nodew : hot1;
-    const bool lds = hot_bytes > 0 && hot_bytes + stack_bytes <= lds_max && !tun.no_lds && kernel != 5;  // kernel 5: scene in L2/HBM always
-    const int integ = plan.integrator;
-    if (integ == 1 && view.n_lights == 0 && !env && !area) throw RtError(RT_ERR_ARG, "integrator 1 (light importance sampling) needs rt_scene_set_lights");
-    if (integ == 2 && !plan.sppm_est) throw RtError(RT_ERR_ARG, "integrator 2 (SPPM) is reached through rt_render_sppm");
+    c.hot_bytes = (kernel == 2 || kernel == 5) ? hot2 - (size_t)view.n_nodes2 * sizeof(Node2) + nodew : hot1;
+    c.lds = c.hot_bytes > 0 && c.hot_bytes + c.stack_bytes <= lds_max && !tun.no_lds && kernel != 5;  // kernel 5: scene in L2/HBM always
     if (integ != 0 && book2)
         throw RtError(RT_ERR_UNSUPPORTED, "the book-2 extensions (moving spheres, noise textures, an open shutter) render with integrator 0 (kernels 1 and 2)");
     if (media && integ == 1)
         throw RtError(RT_ERR_UNSUPPORTED, "scenes with a ConstantMedium render with integrator 0 only (the medium's random draw is part of the "
                                           "reference-order walk; light sampling and SPPM have no volume events)");
-    pt_fn fn = (kernel == 1) ? pick_pt_kernel<1>(lds, general, integ) : pick_pt_kernel<2>(lds, general, integ);
-    pt_coop_fn fn_coop = nullptr;
-    pt_coop_fn fn_coop_early = nullptr;  // the variant that folds from the main loop: for a rank that owns few tiles (see pt_kernel_coop)
-    if (kernel == 5) {
-        // 33..64 instances: the 64-bit pending mask (the MIXED code covers scenes without inline instances too); exact ties: see tie_scene()
-        const bool wide = view.n_inst2 > 32u, mixed = view.n_inline2 != 0u;
-        if (tie_scene(view)) pick_coop<true>(integ, mixed, wide, fn_coop, fn_coop_early);
-        else pick_coop<false>(integ, mixed, wide, fn_coop, fn_coop_early);
-    }
-    if (media)  // (integrator 2: the SPPM final pass, rt_render_sppm; volume events are passed through to the first Diffuse hit)
-        fn = (integ == 2) ? ((kernel == 2) ? (lds ? pt_kernel<true, true, 2, 2, true> : pt_kernel<false, true, 2, 2, true>)
-                                           : (lds ? pt_kernel<true, true, 1, 2, true> : pt_kernel<false, true, 1, 2, true>))
-                          : ((kernel == 2) ? (lds ? pt_kernel<true, true, 2, 0, true> : pt_kernel<false, true, 2, 0, true>)
-                                           : (lds ? pt_kernel<true, true, 1, 0, true> : pt_kernel<false, true, 1, 0, true>));
-    if (book2)  // GENERAL == 2
-        fn = media ? ((kernel == 2) ? (lds ? pt_kernel<true, 2, 2, 0, true> : pt_kernel<false, 2, 2, 0, true>)
-                                    : (lds ? pt_kernel<true, 2, 1, 0, true> : pt_kernel<false, 2, 1, 0, true>))
-                   : ((kernel == 2) ? (lds ? pt_kernel<true, 2, 2, 0> : pt_kernel<false, 2, 2, 0>) : (lds ? pt_kernel<true, 2, 1, 0> : pt_kernel<false, 2, 1, 0>));
-    if (nest) {  // nested Transforms: the chain walk (GENERAL == 3) of kernels 1 and 2 (kernels 5 / 6 were refused: no compact data)
-        if (kernel == 1)
-            fn = media ? ((integ == 2) ? (lds ? pt_kernel<true, 3, 1, 2, true> : pt_kernel<false, 3, 1, 2, true>)
-                                       : (lds ? pt_kernel<true, 3, 1, 0, true> : pt_kernel<false, 3, 1, 0, true>))
-               : (integ == 1) ? (lds ? pt_kernel<true, 3, 1, 1> : pt_kernel<false, 3, 1, 1>)
-               : (integ == 2) ? (lds ? pt_kernel<true, 3, 1, 2> : pt_kernel<false, 3, 1, 2>)
-                              : (lds ? pt_kernel<true, 3, 1, 0> : pt_kernel<false, 3, 1, 0>);
-        else if (kernel == 2)
-            fn = media ? ((integ == 2) ? (lds ? pt_kernel<true, 3, 2, 2, true> : pt_kernel<false, 3, 2, 2, true>)
-                                       : (lds ? pt_kernel<true, 3, 2, 0, true> : pt_kernel<false, 3, 2, 0, true>))
-               : (integ == 1) ? (lds ? pt_kernel<true, 3, 2, 1> : pt_kernel<false, 3, 2, 1>)
-               : (integ == 2) ? (lds ? pt_kernel<true, 3, 2, 2> : pt_kernel<false, 3, 2, 2>)
-                              : (lds ? pt_kernel<true, 3, 2, 0> : pt_kernel<false, 3, 2, 0>);
-        else
-            throw RtError(RT_ERR_INTERNAL, "nested Transforms reached kernel " + std::to_string(kernel));
-    }
-    if (bg) {
-        const int g = nest ? 3 : book2 ? 2 : (general || integ == 1) ? 1 : 0;
-        fn = (kernel == 2) ? (lds ? pick_pt_kernel_bg<2, true>(g, media, integ) : pick_pt_kernel_bg<2, false>(g, media, integ))
-                           : (lds ? pick_pt_kernel_bg<1, true>(g, media, integ) : pick_pt_kernel_bg<1, false>(g, media, integ));
-    }
-    if (bg && env && integ == 1)  // (media and the book-2 kinds were refused above: GENERAL is 1 or 3 here)
-        fn = (kernel == 2) ? (lds ? pick_pt_kernel_env<2, true>(nest) : pick_pt_kernel_env<2, false>(nest))
-                           : (lds ? pick_pt_kernel_env<1, true>(nest) : pick_pt_kernel_env<1, false>(nest));
-    if (area)  // (likewise GENERAL 1 or 3; the variant tests the background and the env table at run time)
-        fn = (kernel == 2) ? (lds ? pick_pt_kernel_area<2, true>(nest) : pick_pt_kernel_area<2, false>(nest))
-                           : (lds ? pick_pt_kernel_area<1, true>(nest) : pick_pt_kernel_area<1, false>(nest));
+    // nested Transforms: the chain walk (GENERAL == 3) of kernels 1 and 2 (kernels 5 / 6 were refused: no compact data)
+    if (nest && kernel != 1 && kernel != 2) throw RtError(RT_ERR_INTERNAL, "nested Transforms reached kernel " + std::to_string(kernel));
+    return c;
+}
+
+// ---- stage 2: the kernel variant, its LDS, the grid and the workspace of a launch of kernels 1 / 2 / 5 ----
+struct LaunchLayout {
+    pt_fn fn = nullptr;  // kernels 1 / 2
+    pt_coop_fn fn_coop = nullptr;  // kernel 5
+    int n_top = 0, n_topq = 0;  // nodes cached in LDS when the scene is not: Node2 (f32), NodeQ (compact, kernel 5)
+    size_t smem = 0;
+    int grid = 0;
+    bool pool = false;
+    float node_shrink = 0.f;
+    int64_t n_pix = 0;
+    size_t ring_bytes = 0, accum_bytes = 0, ticket_bytes = 0, coop_bytes = 0;  // what the workspace must hold
+    size_t workspace_bytes = 0;  // what this launch uses of it (rt_stats)
+};
+static LaunchLayout launch_layout(const FlatView& view, const RenderPlan& plan, const Tuning& tun, const DevInfo& di, const KernelChoice& c) {
+    LaunchLayout L;
+    const int kernel = c.kernel, integ = plan.integrator;
+    const size_t lds_max = c.lds_max, stack_bytes = c.stack_bytes;
     // scene too large for LDS: spend what is left after the stacks on the shallowest BVH levels (the Node2 array is depth-sorted)
-    int n_top = 0, n_topq = 0;
-    if (kernel == 2 && !lds && lds_max > stack_bytes) {
+    if (kernel == 2 && !c.lds && lds_max > stack_bytes) {
         size_t room = (lds_max - stack_bytes) / sizeof(Node2);
         if (tun.n_top >= 0) room = std::min<size_t>(room, (size_t)tun.n_top);
-        n_top = (int)std::min<size_t>(room, view.n_nodes2);
+        L.n_top = (int)std::min<size_t>(room, view.n_nodes2);
     }
     if (kernel == 5 && lds_max > stack_bytes) {  // f32 nodes for the world-space walk (at most 128), the rest of LDS for the compact object-space nodes
         size_t room = lds_max - stack_bytes;
-        n_top = (int)std::min<size_t>(std::min<size_t>(room / sizeof(Node2), 128), view.world_top2);
-        if (tun.n_top >= 0) n_top = std::min(n_top, tun.n_top);
-        room -= (size_t)n_top * sizeof(Node2);
-        n_topq = (int)std::min<size_t>(room / sizeof(NodeQ), view.n_nodes2);
-        if (tun.n_top >= 0) n_topq = std::min(n_topq, tun.n_top);
+        L.n_top = (int)std::min<size_t>(std::min<size_t>(room / sizeof(Node2), 128), view.world_top2);
+        if (tun.n_top >= 0) L.n_top = std::min(L.n_top, tun.n_top);
+        room -= (size_t)L.n_top * sizeof(Node2);
+        L.n_topq = (int)std::min<size_t>(room / sizeof(NodeQ), view.n_nodes2);
+        if (tun.n_top >= 0) L.n_topq = std::min(L.n_topq, tun.n_top);
     }
-    const size_t smem = (lds ? hot_bytes : (size_t)n_top * sizeof(Node2) + (size_t)n_topq * sizeof(NodeQ)) + stack_bytes + (moving ? (size_t)PT_BLOCK * sizeof(double) : 0);
-    if (kernel == 5 && COOP_EARLY_FOLD && plan.tiles_owned < (int64_t)2 * di.cus * (PT_BLOCK / 64)) fn_coop = fn_coop_early;  // (one workgroup per CU)
-    const void* fptr = (kernel == 5) ? (const void*)fn_coop : (const void*)fn;
+    const size_t smem = L.smem = (c.lds ? c.hot_bytes : (size_t)L.n_top * sizeof(Node2) + (size_t)L.n_topq * sizeof(NodeQ)) + stack_bytes +
+                                 (c.variant.moving ? (size_t)PT_BLOCK * sizeof(double) : 0);
+    // kernel 5: the variant that folds from the main loop for a rank that owns few tiles (see pt_kernel_coop)
+    const bool early = kernel == 5 && COOP_EARLY_FOLD && plan.tiles_owned < (int64_t)2 * di.cus * (PT_BLOCK / 64);  // (one workgroup per CU)
+    if (kernel == 5)  // 33..64 instances: the 64-bit pending mask; exact ties: see tie_scene()
+        L.fn_coop = coop_variant(CoopKey{integ, view.n_inline2 != 0u || view.n_inst2 > 32u, early, view.n_inst2 > 32u, tie_scene(view)});
+    else
+        L.fn = pt_variant(pt_key(c, integ, false));
+    const void* fptr = (kernel == 5) ? (const void*)L.fn_coop : (const void*)L.fn;
     if (smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute(fptr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     int blocks_per_cu = 0;
     HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, fptr, PT_BLOCK, smem));
     if (blocks_per_cu < 1) blocks_per_cu = 1;
-    const int grid = di.cus * blocks_per_cu;
-    // a rank that owns fewer tiles than the launch has waves: single-unit jobs (below) folded out of order (next_unit_pool)
-    const bool pool = POOL_MODE && SINGLE_UNITS_BELOW_WAVES && plan.tiles_owned < (int64_t)grid * (PT_BLOCK / 64) &&
-                      ((kernel == 2 && !media && !book2 && !nest && !bg && !area) || (kernel == 5 && fn_coop == fn_coop_early));
-    if (pool && kernel == 2) {
-        fn = pick_pt_kernel_pool(lds, general, integ);  // (same resources as the variant the occupancy was asked for)
-        if (smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    const int grid = L.grid = di.cus * blocks_per_cu;
+    // a rank that owns fewer tiles than the launch has waves: single-unit jobs (render_tiles' loop) folded out of order (next_unit_pool)
+    const SceneVariant& v = c.variant;
+    L.pool = POOL_MODE && SINGLE_UNITS_BELOW_WAVES && plan.tiles_owned < (int64_t)grid * (PT_BLOCK / 64) &&
+             ((kernel == 2 && !v.media && !v.book2 && !v.nest && !c.bg && !c.area) || (kernel == 5 && early));
+    if (L.pool && kernel == 2) {
+        L.fn = pt_variant(pt_key(c, integ, true));  // (same resources as the variant the occupancy was asked for)
+        if (smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)L.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     }
-
     // The LDS node table of kernel 2 is padded for THIS render's ray origins (common/tighten.h): the lens (cam_abs, the
     // quantity camera_ok was tested with: |lens offset| <= lens_radius on every axis) and points on the scene's items or inside its
     // media (their extent is part of origin_limit2 / 64: build_bvhs starts ew from media_extent).  A scene with any instance keeps the
     // stored pads: the table then holds object-space BVHs too, whose pads come from the instances' own origin bounds.  Regions, adaptive
     // passes, resumable ranges and the ranks of rt_render_multi all launch from here, with the camera of their frame.
-    const float node_shrink = (RT_TIGHTEN_BOXES && kernel == 2 && lds) ? box_shrink(view.origin_limit2, render_origin_bound(view.origin_limit2, cam_abs), view.n_inst2 == 0u) : 0.f;
-    const int64_t n_pix = plan.tiles_owned * TILE_PIX;
+    L.node_shrink = (RT_TIGHTEN_BOXES && kernel == 2 && c.lds) ? box_shrink(view.origin_limit2, render_origin_bound(view.origin_limit2, c.cam_abs), view.n_inst2 == 0u) : 0.f;
+    L.n_pix = plan.tiles_owned * TILE_PIX;
     // workspace: RING_UNITS unit buffers (12 KB) per resident wave -- independent of the image -- plus accumulator and tickets
-    const size_t ring_bytes = (size_t)grid * (PT_BLOCK / 64) * RING_UNITS * UNIT_DOUBLES * sizeof(double);
-    WorkspaceLease lease(dev, ring_bytes, std::max<size_t>(16, (size_t)n_pix * 3 * sizeof(double)),
-                         std::max<size_t>(16, (size_t)plan.tiles_owned * sizeof(unsigned int)),
-                         (kernel == 5) ? (size_t)grid * COOP_POOL * COOP_REC * sizeof(uint64_t) : 0);
-    struct Ptr {
-        void* p;
-    };
-    char* small = (char*)lease.w->small;
-    Ptr ringp{lease.w->ring}, accum{plan.ext_accum ? (void*)plan.ext_accum : lease.w->accum}, tickets{lease.w->tickets}, counter{small}, err{small + 16};
-    const int s_first = plan.ext_accum ? plan.s_first : 0, s_last = (plan.ext_accum && plan.s_last >= 0) ? plan.s_last : plan.spp;
-    HIP_CHECK(hipMemsetAsync(small, 0, WS_SMALL, stream));
-    Events events;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pt_ev;
-    CamK ck = to_camk(cam);
-    int launches = 0;
-    for (int s0 = s_first; s0 < s_last; s0 += plan.spp_chunk) {
-        const int s1 = std::min(s0 + plan.spp_chunk, s_last);
-        RenderK rk = {};
-        rk.width = plan.width; rk.height = plan.height; rk.max_depth = plan.max_depth;
-        rk.t_min = plan.t_min; rk.seed = plan.seed;
-        rk.s_begin = s0; rk.s_end = s1;
-        rk.sub_spp = plan.sub_spp;
-        rk.subs_per_tile = (s1 - s0 + plan.sub_spp - 1) / plan.sub_spp;
-        // jobs of JOB_UNITS units halve the cross-wave hand-offs; small launches keep single units for load balance
-        // (measured: headline 592 ms with 2, 606 with 1 and a 4-slot ring, 593 with 4; 9 M-sample frame 7.0 ms with 1 or 2, 9.3 with 4)
-        const bool many_units = plan.tiles_owned * (int64_t)rk.subs_per_tile >= (int64_t)64 * grid * (PT_BLOCK / 64);
-        // (a rank that owns fewer tiles than the GPU has waves traces consecutive jobs of one tile at the same time: single units hand the
-        // tile's ticket on sooner -- 1/8 of the headline frame 68.2 -> 66.6 ms, while the whole frame loses 1.2 % with single units)
-        const bool tiles_cover_waves = !SINGLE_UNITS_BELOW_WAVES || plan.tiles_owned >= (int64_t)grid * (PT_BLOCK / 64);
-        rk.job_units = std::max(1, std::min(many_units && tiles_cover_waves ? JOB_UNITS : 1, rk.subs_per_tile));
-        rk.tiles_owned = (int)std::max<int64_t>(1, plan.tiles_owned);
-        rk.pool_mode = pool ? 1 : 0;  // (job_units is 1: the rank's tiles do not cover the waves)
-        Schedule sch;
-        const int jobs_per_tile = make_schedule(sch, rk.tiles_owned, grid * (PT_BLOCK / 64), rk.s_begin, rk.s_end, rk.sub_spp, rk.job_units);  // host/schedule.cpp
-        static_assert(sizeof(rk.lvl) == sizeof(sch.lvl), "RenderK::lvl is Schedule::lvl");
-        std::memcpy(rk.lvl, sch.lvl, sizeof(rk.lvl));
-        rk.subs_per_tile = sch.units_per_tile;
-        int64_t units = plan.tiles_owned * (int64_t)jobs_per_tile;
-        if (units > 0x7FFFFFFF) throw RtError(RT_ERR_UNSUPPORTED, "too many work units per launch");
-        rk.n_units = (int)units;
-        rk.tiles_x = plan.tiles_x; rk.rank = plan.rank; rk.world = plan.world;
-        rk.sppm_est = plan.sppm_est;
-        rk.time0 = plan.time0;
-        rk.time1 = plan.time1;
-        rk.time_slots = moving ? 1 : 0;
-        rk.tile_list = plan.tile_list;
-        rk.box_shrink = node_shrink;
-        rk.n_top = n_top;
-        rk.n_topq = n_topq;
-        rk.coop_stack = (int)stack5;
-        rk.coop_pool = tun.coop_pool > 0 ? std::min(tun.coop_pool, (int)COOP_POOL) : (int)COOP_POOL;
-        HIP_CHECK(hipMemsetAsync(counter.p, 0, sizeof(unsigned int), stream));
-        HIP_CHECK(hipMemsetAsync((char*)counter.p + 64, 0, JOB_LISTS * sizeof(unsigned int), stream));  // the per-list job counters (words 16.. of the small block)
-        HIP_CHECK(hipMemsetAsync(tickets.p, 0, std::max<size_t>(16, (size_t)plan.tiles_owned * sizeof(unsigned int)), stream));
-        hipEvent_t e0 = events.make(), e1 = events.make();
-        HIP_CHECK(hipEventRecord(e0, stream));
-        if (rk.n_units > 0) {
-            if (kernel == 5)
-                hipLaunchKernelGGL(fn_coop, dim3(grid), dim3(PT_BLOCK), smem, stream, view, ck, rk, (double*)ringp.p, (double*)accum.p,
-                                   (unsigned int*)tickets.p, (unsigned int*)counter.p, (int*)err.p, (uint64_t*)lease.w->coop);
-            else
-                hipLaunchKernelGGL(fn, dim3(grid), dim3(PT_BLOCK), smem, stream, view, ck, rk, (double*)ringp.p, (double*)accum.p,
-                                   (unsigned int*)tickets.p, (unsigned int*)counter.p, (int*)err.p);
-            HIP_CHECK(hipGetLastError());
-        }
-        HIP_CHECK(hipEventRecord(e1, stream));
-        pt_ev.emplace_back(e0, e1);
-        launches++;
+    L.ring_bytes = (size_t)grid * (PT_BLOCK / 64) * RING_UNITS * UNIT_DOUBLES * sizeof(double);
+    L.accum_bytes = std::max<size_t>(16, (size_t)L.n_pix * 3 * sizeof(double));
+    L.ticket_bytes = std::max<size_t>(16, (size_t)plan.tiles_owned * sizeof(unsigned int));
+    L.coop_bytes = (kernel == 5) ? (size_t)grid * COOP_POOL * COOP_REC * sizeof(uint64_t) : 0;
+    L.workspace_bytes = L.ring_bytes + (size_t)L.n_pix * 3 * sizeof(double) + (size_t)plan.tiles_owned * sizeof(unsigned int) + L.coop_bytes;
+    return L;
+}
+
+// ---- stage 4: what a call reports (kernels 1 / 2 / 5 and 6; the callers add their own reserved[] words) ----
+static void fill_stats(rt_stats* st, const rt_scene& s, const RenderPlan& plan, int kernel, bool lds, int grid, double kernel_ms, int launches, size_t workspace_bytes) {
+    if (!st) return;
+    st->kernel_ms = kernel_ms;
+    st->reduce_ms = 0.;  // the ordered reduction happens inside pt_kernel
+    st->launches = launches;
+    st->kernel_used = kernel;
+    st->scene_in_lds = lds ? 1 : 0;
+    st->block_threads = PT_BLOCK;
+    st->grid_blocks = grid;
+    st->spp_chunk = plan.spp_chunk;
+    st->scene_bytes = s.flat.blob.size();
+    st->reserved[1] = (uint64_t)workspace_bytes;
+}
+
+// ---- stage 5: what the statistics builds (tools/build_variant.sh stats -D...) print after a call; nothing in the product ----
+// kernel 6 (RTAMD_WF_STATS) passes its cycle count as `launches`, its walk grid, segment length and cached NodeQ count
+static void print_tool_stats(int kernel, bool lds, int grid, const rt_stats* st, int launches = 0, int grid_w = 0, uint32_t seg = 0, uint32_t n_topq_w = 0) {
+#ifdef RTAMD_WF_STATS
+    if (kernel == 6) {
+        unsigned long long hs[16], z[16] = {0};
+        HIP_CHECK(hipMemcpyFromSymbol(hs, HIP_SYMBOL(g_wf_stats), sizeof(hs)));
+        const char* names[12] = {"parks", "adoptions", "generated", "wave iterations", "wave exits: ring full / no unit", "wave exits: gate closed", "wave exits: finished",
+                                 "wave cycles in launches", "alive lanes summed", "entry walks", "walk passes", "walk pass lanes"};
+        fprintf(stderr, "[wf stats] cycles %d  grid %d x %d  walk grid %d  seg %u  n_topq_w %u\n", launches, grid, PT_BLOCK, grid_w, seg, n_topq_w);
+        for (int i = 0; i < 12; i++) fprintf(stderr, "[wf stats] %-34s %14llu\n", names[i], hs[i]);
+        HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_wf_stats), z, sizeof(z)));
     }
-    if (n_pix > 0 && !plan.ext_accum) {
-        hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((n_pix + 255) / 256)), dim3(256), 0, stream, (const double*)accum.p, d_tiles,
-                           n_pix, plan.spp, plan.width, plan.height, plan.tiles_x, plan.rank, plan.world);
-        HIP_CHECK(hipGetLastError());
-    }
-    int h_err = 0;
-    HIP_CHECK(hipMemcpyAsync(&h_err, err.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
-    if (st) {
-        double kms = 0;
-        for (auto& p : pt_ev) {
-            float ms = 0;
-            HIP_CHECK(hipEventElapsedTime(&ms, p.first, p.second));
-            kms += ms;
-        }
-        st->kernel_ms = kms;
-        st->reduce_ms = 0.;  // the ordered reduction happens inside pt_kernel
-        st->launches = launches;
-        st->kernel_used = kernel;
-        st->scene_in_lds = lds ? 1 : 0;
-        st->block_threads = PT_BLOCK;
-        st->grid_blocks = grid;
-        st->spp_chunk = plan.spp_chunk;
-        st->scene_bytes = s.flat.blob.size();
-        st->reserved[1] = (uint64_t)(ring_bytes + (size_t)n_pix * 3 * sizeof(double) + (size_t)plan.tiles_owned * sizeof(unsigned int) +
-                                     ((kernel == 5) ? (size_t)grid * COOP_POOL * COOP_REC * sizeof(uint64_t) : 0));  // workspace bytes
-        uint32_t shrink_bits;
-        std::memcpy(&shrink_bits, &node_shrink, 4);
-        st->reserved[3] = shrink_bits;  // (rt_render_multi overwrites entry 0's with its own count afterwards)
-    }
+#endif
+    if (kernel == 6) return;  // (the builds below count in pt_kernel and pt_kernel_coop)
 #ifdef RTAMD_COOP_STATS
     if (kernel == 5) {
         unsigned long long hs[16], z[16] = {0};
@@ -4671,6 +4545,120 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
         HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_fold_stats), z, sizeof(z)));
     }
 #endif
+}
+
+static void render_tiles_wf(const rt_scene& s, const FlatView& view, const CameraDev& cam, const RenderPlan& plan, const Tuning& tun, double* d_tiles,
+                            hipStream_t stream, rt_stats* st, int dev, const DevInfo& di, const KernelChoice& c);
+
+// Stage 3 is what is left here: the launch loop of kernels 1 / 2 / 5 and the finalize pass (kernel 6: render_tiles_wf)
+void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& plan, double* d_tiles, void* stream_, rt_stats* st) {
+    if (!s.committed) throw RtError(RT_ERR_NOT_COMMITTED, "scene not committed");
+    const Tuning tun = tuning();  // one snapshot per call
+    hipStream_t stream = (hipStream_t)stream_;
+    int dev = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    const DevInfo& di = dev_info(dev);
+
+    FlatView view = s.flat.view;
+    double upload_ms = 0.;
+    uint64_t env_total = 0;
+    view.base = device_blob(s, dev, &upload_ms, &env_total);
+    if (st) st->upload_ms = upload_ms;
+    const KernelChoice c = choose_kernel(s, view, cam, plan, tun, di, env_total);
+    const int kernel = c.kernel;
+    if (kernel == 6) {
+        render_tiles_wf(s, view, cam, plan, tun, d_tiles, stream, st, dev, di, c);
+        return;
+    }
+    const LaunchLayout lay = launch_layout(view, plan, tun, di, c);
+    const int grid = lay.grid;
+    WorkspaceLease lease(dev, lay.ring_bytes, lay.accum_bytes, lay.ticket_bytes, lay.coop_bytes);
+    struct Ptr {
+        void* p;
+    };
+    char* small = (char*)lease.w->small;
+    Ptr ringp{lease.w->ring}, accum{plan.ext_accum ? (void*)plan.ext_accum : lease.w->accum}, tickets{lease.w->tickets}, counter{small}, err{small + 16};
+    const int s_first = plan.ext_accum ? plan.s_first : 0, s_last = (plan.ext_accum && plan.s_last >= 0) ? plan.s_last : plan.spp;
+    HIP_CHECK(hipMemsetAsync(small, 0, WS_SMALL, stream));
+    Events events;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pt_ev;
+    CamK ck = to_camk(cam);
+    int launches = 0;
+    for (int s0 = s_first; s0 < s_last; s0 += plan.spp_chunk) {
+        const int s1 = std::min(s0 + plan.spp_chunk, s_last);
+        RenderK rk = {};
+        rk.width = plan.width; rk.height = plan.height; rk.max_depth = plan.max_depth;
+        rk.t_min = plan.t_min; rk.seed = plan.seed;
+        rk.s_begin = s0; rk.s_end = s1;
+        rk.sub_spp = plan.sub_spp;
+        rk.subs_per_tile = (s1 - s0 + plan.sub_spp - 1) / plan.sub_spp;
+        // jobs of JOB_UNITS units halve the cross-wave hand-offs; small launches keep single units for load balance
+        // (measured: headline 592 ms with 2, 606 with 1 and a 4-slot ring, 593 with 4; 9 M-sample frame 7.0 ms with 1 or 2, 9.3 with 4)
+        const bool many_units = plan.tiles_owned * (int64_t)rk.subs_per_tile >= (int64_t)64 * grid * (PT_BLOCK / 64);
+        // (a rank that owns fewer tiles than the GPU has waves traces consecutive jobs of one tile at the same time: single units hand the
+        // tile's ticket on sooner -- 1/8 of the headline frame 68.2 -> 66.6 ms, while the whole frame loses 1.2 % with single units)
+        const bool tiles_cover_waves = !SINGLE_UNITS_BELOW_WAVES || plan.tiles_owned >= (int64_t)grid * (PT_BLOCK / 64);
+        rk.job_units = std::max(1, std::min(many_units && tiles_cover_waves ? JOB_UNITS : 1, rk.subs_per_tile));
+        rk.tiles_owned = (int)std::max<int64_t>(1, plan.tiles_owned);
+        rk.pool_mode = lay.pool ? 1 : 0;  // (job_units is 1: the rank's tiles do not cover the waves)
+        Schedule sch;
+        const int jobs_per_tile = make_schedule(sch, rk.tiles_owned, grid * (PT_BLOCK / 64), rk.s_begin, rk.s_end, rk.sub_spp, rk.job_units);  // host/schedule.cpp
+        static_assert(sizeof(rk.lvl) == sizeof(sch.lvl), "RenderK::lvl is Schedule::lvl");
+        std::memcpy(rk.lvl, sch.lvl, sizeof(rk.lvl));
+        rk.subs_per_tile = sch.units_per_tile;
+        int64_t units = plan.tiles_owned * (int64_t)jobs_per_tile;
+        if (units > 0x7FFFFFFF) throw RtError(RT_ERR_UNSUPPORTED, "too many work units per launch");
+        rk.n_units = (int)units;
+        rk.tiles_x = plan.tiles_x; rk.rank = plan.rank; rk.world = plan.world;
+        rk.sppm_est = plan.sppm_est;
+        rk.time0 = plan.time0;
+        rk.time1 = plan.time1;
+        rk.time_slots = c.variant.moving ? 1 : 0;
+        rk.tile_list = plan.tile_list;
+        rk.box_shrink = lay.node_shrink;
+        rk.n_top = lay.n_top;
+        rk.n_topq = lay.n_topq;
+        rk.coop_stack = (int)c.stack5;
+        rk.coop_pool = tun.coop_pool > 0 ? std::min(tun.coop_pool, (int)COOP_POOL) : (int)COOP_POOL;
+        HIP_CHECK(hipMemsetAsync(counter.p, 0, sizeof(unsigned int), stream));
+        HIP_CHECK(hipMemsetAsync((char*)counter.p + 64, 0, JOB_LISTS * sizeof(unsigned int), stream));  // the per-list job counters (words 16.. of the small block)
+        HIP_CHECK(hipMemsetAsync(tickets.p, 0, lay.ticket_bytes, stream));
+        hipEvent_t e0 = events.make(), e1 = events.make();
+        HIP_CHECK(hipEventRecord(e0, stream));
+        if (rk.n_units > 0) {
+            if (kernel == 5)
+                hipLaunchKernelGGL(lay.fn_coop, dim3(grid), dim3(PT_BLOCK), lay.smem, stream, view, ck, rk, (double*)ringp.p, (double*)accum.p,
+                                   (unsigned int*)tickets.p, (unsigned int*)counter.p, (int*)err.p, (uint64_t*)lease.w->coop);
+            else
+                hipLaunchKernelGGL(lay.fn, dim3(grid), dim3(PT_BLOCK), lay.smem, stream, view, ck, rk, (double*)ringp.p, (double*)accum.p,
+                                   (unsigned int*)tickets.p, (unsigned int*)counter.p, (int*)err.p);
+            HIP_CHECK(hipGetLastError());
+        }
+        HIP_CHECK(hipEventRecord(e1, stream));
+        pt_ev.emplace_back(e0, e1);
+        launches++;
+    }
+    if (lay.n_pix > 0 && !plan.ext_accum) {
+        hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((lay.n_pix + 255) / 256)), dim3(256), 0, stream, (const double*)accum.p, d_tiles,
+                           lay.n_pix, plan.spp, plan.width, plan.height, plan.tiles_x, plan.rank, plan.world);
+        HIP_CHECK(hipGetLastError());
+    }
+    int h_err = 0;
+    HIP_CHECK(hipMemcpyAsync(&h_err, err.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    if (st) {
+        double kms = 0;
+        for (auto& p : pt_ev) {
+            float ms = 0;
+            HIP_CHECK(hipEventElapsedTime(&ms, p.first, p.second));
+            kms += ms;
+        }
+        fill_stats(st, s, plan, kernel, c.lds, grid, kms, launches, lay.workspace_bytes);
+        uint32_t shrink_bits;
+        std::memcpy(&shrink_bits, &lay.node_shrink, 4);
+        st->reserved[3] = shrink_bits;  // (rt_render_multi overwrites entry 0's with its own count afterwards)
+    }
+    print_tool_stats(kernel, c.lds, grid, st);
     if (h_err & 1) throw RtError(RT_ERR_UNIT_ZERO, "unitizing zero vector (device)");
     if (h_err & ~1) throw RtError(RT_ERR_INTERNAL, "device invariant failed (error bits " + std::to_string(h_err) + ": 2 = an instance below an instance "
                                                    "reached an object-space walk, 4 = a kernel 5 ring entry was not published in time)");
@@ -4682,12 +4670,10 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
 // launches), so there is one synchronisation per batch, not per cycle.
 static const int WF_BATCH = 8;
 static void render_tiles_wf(const rt_scene& s, const FlatView& view, const CameraDev& cam, const RenderPlan& plan, const Tuning& tun, double* d_tiles,
-                            hipStream_t stream, rt_stats* st, int dev, const DevInfo& di, uint32_t stack6, uint32_t n_entry6, size_t lds_pt, uint32_t stack6w,
-                            size_t tables_w) {
-    const size_t lds_max = di.lds_max;
+                            hipStream_t stream, rt_stats* st, int dev, const DevInfo& di, const KernelChoice& c) {
+    const size_t lds_max = di.lds_max, lds_pt = c.wf_lds_pt, tables_w = c.wf_tables_w;
+    const uint32_t stack6 = c.stack6, n_entry6 = c.n_entry6, stack6w = c.stack6w;
     const int integ = plan.integrator;
-    if (integ == 1 && view.n_lights == 0) throw RtError(RT_ERR_ARG, "integrator 1 (light importance sampling) needs rt_scene_set_lights");
-    if (integ == 2 && !plan.sppm_est) throw RtError(RT_ERR_ARG, "integrator 2 (SPPM) is reached through rt_render_sppm");
     typedef void (*pt_wf_fn)(FlatView, CamK, RenderK, double*, double*, unsigned int*, unsigned int*, int*, WfArgs);
     const bool tie = tie_scene(view);  // the TIE variants of both launches ("EXACT ties" above traverse<>)
     pt_wf_fn fn = tie ? ((view.n_inline2 != 0u) ? ((integ == 1) ? pt_kernel_wf<1, true, true> : (integ == 2) ? pt_kernel_wf<2, true, true> : pt_kernel_wf<0, true, true>)
@@ -4821,30 +4807,9 @@ static void render_tiles_wf(const rt_scene& s, const FlatView& view, const Camer
     int h_err = 0;
     HIP_CHECK(hipMemcpyAsync(&h_err, err, sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
-    if (st) {
-        st->kernel_ms = kms;
-        st->reduce_ms = 0.;
-        st->launches = launches;
-        st->kernel_used = 6;
-        st->scene_in_lds = 0;
-        st->block_threads = PT_BLOCK;
-        st->grid_blocks = grid;
-        st->spp_chunk = plan.spp_chunk;
-        st->scene_bytes = s.flat.blob.size();
-        st->reserved[1] = (uint64_t)(ring_bytes + (size_t)n_pix * 3 * sizeof(double) + (size_t)plan.tiles_owned * sizeof(unsigned int) + wf_bytes);
-        st->reserved[2] = (uint64_t)grid_w | ((uint64_t)n_topq_w << 32);
-    }
-#ifdef RTAMD_WF_STATS
-    {
-        unsigned long long hs[16], z[16] = {0};
-        HIP_CHECK(hipMemcpyFromSymbol(hs, HIP_SYMBOL(g_wf_stats), sizeof(hs)));
-        const char* names[12] = {"parks", "adoptions", "generated", "wave iterations", "wave exits: ring full / no unit", "wave exits: gate closed", "wave exits: finished",
-                                 "wave cycles in launches", "alive lanes summed", "entry walks", "walk passes", "walk pass lanes"};
-        fprintf(stderr, "[wf stats] cycles %d  grid %d x %d  walk grid %d  seg %u  n_topq_w %u\n", launches, grid, PT_BLOCK, grid_w, seg, n_topq_w);
-        for (int i = 0; i < 12; i++) fprintf(stderr, "[wf stats] %-34s %14llu\n", names[i], hs[i]);
-        HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_wf_stats), z, sizeof(z)));
-    }
-#endif
+    fill_stats(st, s, plan, 6, false, grid, kms, launches, ring_bytes + (size_t)n_pix * 3 * sizeof(double) + (size_t)plan.tiles_owned * sizeof(unsigned int) + wf_bytes);
+    if (st) st->reserved[2] = (uint64_t)grid_w | ((uint64_t)n_topq_w << 32);
+    print_tool_stats(6, false, grid, st, launches, grid_w, seg, n_topq_w);
     if (h_err & 1) throw RtError(RT_ERR_UNIT_ZERO, "unitizing zero vector (device)");
     if (h_err & ~1) throw RtError(RT_ERR_INTERNAL, "device invariant failed (error bits " + std::to_string(h_err) + ")");
 }

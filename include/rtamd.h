@@ -580,6 +580,41 @@ int rt_denoised_render_device(const rt_scene* s, const rt_camera* cam, const rt_
                               int32_t aov_spp, double* d_out_rgb, double* d_out_noisy, double* d_out_variance, double* d_out_aov,
                               void* hip_stream, rt_stats* stats);
 
+/* ---- ambient occlusion (no reference counterpart) -------------------------------------------------------------------- */
+/* Ambient occlusion / sky visibility, a bent normal and the ambient term lit by the scene's background, on one device (p->world 1,
+ * p->rank 0, p->device picks it); the pass generates its own rays.  Read from p: width, height, seed, t_min, kernel (0 / 1 / 2, as
+ * rt_render_aov), device; everything else in p is ignored.  All arithmetic is f64 without contraction.
+ *   camera ray   for pixel pix = y * width + x and sample s in [0, ao_spp): rt_render's sample s -- stream (p->seed, pix, s), the same
+ *                jitter and lens draws -- and its first hit World::hit(ray, p->t_min, +inf).  A miss contributes nothing; a hit gives
+ *                its point P and the record's front-facing normal n.
+ *   occlusion    for each hit and k in [0, K), K = rays_per_hit: a fresh stream (p->seed XOR 0x9E3779B97F4A7C15, pix, s * K + k);
+ *                u = unit(random_in_unit_sphere(stream)) as a Lambertian scatters; v = n + u, v = n where near_zero(v); d = unit(v)
+ *                (cosine-distributed around n).  The ray is OCCLUDED iff World::hit(Ray(P, d), p->t_min, max_distance) returns a hit:
+ *                every surface occludes (lights, glass, emitters); an occluder farther than max_distance does not count.
+ *   sums         in (s, k) order from 0.0; hits = camera rays that hit, N = hits * K.
+ * out_ao[height][width][8] (HOST) = {visibility = unoccluded / N, bent[3] = (sum over unoccluded rays of d) / N (not renormalised: its
+ * length tells how open the cone is), ambient[3] = (sum over unoccluded rays of B(d)) / N with B what shades a miss (rt_scene_set_background;
+ * exactly 0 where the scene has none), coverage = hits / ao_spp}; a pixel without a hit is eight zeros.  The result does not depend on
+ * the walk or the launch shape; tests/ao_ref.py restates it over the oracle.
+ * Checked before the device is touched: RT_ERR_ARG (a null s, cam, p, cfg or output; width / height < 1; p->world != 1 or p->rank != 0; a
+ * kernel outside 0..2; a config value outside its range; reserved != 0), RT_ERR_NOT_COMMITTED, RT_ERR_UNSUPPORTED (a scene with a
+ * ConstantMedium or moving spheres, as rt_render_aov; kernel 2 without a usable accel: no accel, t_min < 0, the camera farther from the
+ * origin than the scene's origin bound, stacks larger than LDS) -- then RT_ERR_NO_DEVICE without a GPU.
+ * stats: seconds, kernel_ms, launches (1), upload_ms, samples (= width * height * ao_spp), kernel_used (1 or 2), block_threads,
+ * grid_blocks, scene_bytes. */
+typedef struct rt_ao_config {
+    int32_t ao_spp;        /* camera rays per pixel, 1..4096; default 4 */
+    int32_t rays_per_hit;  /* K: occlusion rays per camera-ray hit, 1..256; default 4 */
+    double max_distance;   /* > 0, +inf allowed (the default): an occluder farther away does not count */
+    int32_t reserved[4];   /* must be 0 */
+} rt_ao_config;
+void rt_default_ao_config(rt_ao_config* c);
+int rt_ao_render(const rt_scene* s, const rt_camera* cam, const rt_params* p, const rt_ao_config* cfg, double* out_ao, rt_stats* stats);
+/* the same with d_out_ao in DEVICE memory of the call's device, the kernel launched on `hip_stream` (hipStream_t as void*, NULL =
+ * default stream); returns after the work has completed on that stream */
+int rt_ao_render_device(const rt_scene* s, const rt_camera* cam, const rt_params* p, const rt_ao_config* cfg, double* d_out_ao,
+                        void* hip_stream, rt_stats* stats);
+
 /* ---- tile-adaptive sampling (no reference counterpart) ------------------------------------------------------------ */
 /* A whole frame on one device (p->world 1, p->rank 0, p->device picks it) in which every 8x8 tile T gets its own sample count n_T.  With
  * h = min_spp / 2 the passes trace the sample ranges [0, h), [h, 2h), [2h, 4h), [4h, 8h), ..., each capped at p->spp (the last one is
@@ -724,6 +759,15 @@ int rt_debug_light_pdf_device(const rt_scene* s, int device, size_t n, const dou
  * in a render (64 times its extent). */
 int rt_debug_walk_device(const rt_scene* s, int device, int kernel, size_t n, const double* rays_host, const uint64_t* keys_host, double t_min,
                          double* out_host);
+/* any-hit of explicit rays, through the device function rt_ao_render's occlusion rays take: "would World::hit(ray, t_min, t_max) return
+ * a hit", answered at the first primitive whose own test accepts a t in the range (no record, no tie rule).
+ *   rays_host n*7 = {origin[3], direction[3], t_max} (every row its own t_max, +inf allowed); out_host n doubles, 1.0 = occluded, 0.0 = not.
+ *   kernel 1: the reference-order program, 2: the accel walk over the node array in global memory (nested chains where the scene has any).
+ * Checked on the host first: RT_ERR_ARG (a null pointer, n == 0, a kernel outside 1..2), RT_ERR_NOT_COMMITTED, RT_ERR_UNSUPPORTED (a
+ * scene with a ConstantMedium or moving spheres; kernel 2 on a scene without an accel, with t_min < 0 or with stacks that do not fit in
+ * LDS) -- then RT_ERR_NO_DEVICE without a GPU.  The accel walk is exact for origins within the scene's origin bound, as in a render (64
+ * times its extent). */
+int rt_debug_occluded_device(const rt_scene* s, int device, int kernel, size_t n, const double* rays_host, double t_min, double* out_host);
 /* SPPM photon gather diagnostics: ONE iteration of the render's own gather on explicit inputs (host buffers throughout) -- the grid
  * build and the sort of both photon maps, gather_kernel (four waves per block, one gather point per wave, caustic map first, then
  * global) and estimate_kernel, launched as rt_render_sppm launches them.  No scene is involved.

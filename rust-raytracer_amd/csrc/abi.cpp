@@ -15,6 +15,7 @@
 #include "common/rng.h"
 #include "common/schedule.h"
 #include "device/adaptive.h"
+#include "device/ao.h"
 #include "device/denoise.h"
 #include "device/device.h"
 #include "host/frame.h"
@@ -848,6 +849,47 @@ int rt_render_aov(const rt_scene* s, const rt_camera* cam, const rt_params* p, i
         return (int)RT_OK;
     });
 }
+// ---- ambient occlusion (device/ao.inc through the weak declarations of device/ao.h) ----
+void rt_default_ao_config(rt_ao_config* c) {
+    if (!c) return;
+    std::memset(c, 0, sizeof(*c));
+    c->ao_spp = 4;
+    c->rays_per_hit = 4;
+    c->max_distance = INFINITY;
+}
+// every refusal that needs no device comes before RT_ERR_NO_DEVICE
+static int ao_render_entry(const rt_scene* s, const rt_camera* cam, const rt_params* p, const rt_ao_config* cfg, double* out, bool on_device, void* hip_stream,
+                           rt_stats* stats) {
+    return guard([&] {
+        REQUIRE(s && cam && p && cfg && out, "null argument");
+        REQUIRE(p->width > 0 && p->height > 0, "width/height must be positive");
+        REQUIRE(p->world == 1 && p->rank == 0, "rt_ao_render renders whole frames: rank / world must be 0 / 1");
+        REQUIRE(cfg->ao_spp >= 1 && cfg->ao_spp <= 4096, "ao_spp must be 1..4096");
+        REQUIRE(cfg->rays_per_hit >= 1 && cfg->rays_per_hit <= 256, "rays_per_hit must be 1..256");
+        REQUIRE(cfg->max_distance > 0., "max_distance must be > 0 (+inf: no limit)");
+        for (int32_t r : cfg->reserved) REQUIRE(r == 0, "rt_ao_config.reserved must be 0");
+        REQUIRE(p->kernel >= 0 && p->kernel <= 2, "rt_ao_render walks with kernel 0 (auto), 1 or 2");
+        const CameraDev cd = make_camera(*cam);
+        ao_choose_walk(*s, cd, p->t_min, p->kernel);  // (the refusals; the launch picks the walk again with its device's LDS)
+        require_device(render_ao != nullptr && render_ao_device != nullptr);
+        const CallClock clock;
+        DeviceScope dev_scope(p->device);
+        rt_stats st{};
+        if (on_device)
+            render_ao_device(*s, cd, p->width, p->height, p->seed, p->t_min, p->kernel, *cfg, out, hip_stream, &st);
+        else
+            render_ao(*s, cd, p->width, p->height, p->seed, p->t_min, p->kernel, *cfg, out, &st);
+        clock.finish(stats, st);
+        return (int)RT_OK;
+    });
+}
+int rt_ao_render(const rt_scene* s, const rt_camera* cam, const rt_params* p, const rt_ao_config* cfg, double* out_ao, rt_stats* stats) {
+    return ao_render_entry(s, cam, p, cfg, out_ao, false, nullptr, stats);
+}
+int rt_ao_render_device(const rt_scene* s, const rt_camera* cam, const rt_params* p, const rt_ao_config* cfg, double* d_out_ao, void* hip_stream,
+                        rt_stats* stats) {
+    return ao_render_entry(s, cam, p, cfg, d_out_ao, true, hip_stream, stats);
+}
 void rt_default_denoise_config(rt_denoise_config* c) {
     if (!c) return;
     std::memset(c, 0, sizeof(*c));
@@ -1133,6 +1175,16 @@ int rt_debug_walk_device(const rt_scene* s, int device, int kernel, size_t n, co
         return RT_ERR_UNIT_ZERO;
     }
     return rc;
+}
+// the any-hit diagnostic likewise (the rays' origins are the caller's: the origin bound is stated in rtamd.h, not checked)
+int rt_debug_occluded_device(const rt_scene* s, int device, int kernel, size_t n, const double* rays_host, double t_min, double* out_host) {
+    return shade_debug(s, device, rtamd::debug_occluded_device != nullptr, [&] {
+        REQUIRE(n > 0 && rays_host && out_host, "bad argument");
+        REQUIRE(kernel == 1 || kernel == 2, "rt_debug_occluded_device: kernel 1 or 2");
+        aov_refuse(*s);
+        if (kernel == 2 && !ao_accel_usable(s->flat.view, 0., t_min))
+            throw RtError(RT_ERR_UNSUPPORTED, "kernel 2 needs an accel, t_min >= 0 (box32) and walk stacks that fit in LDS");
+    }, [&] { debug_occluded_device(*s, kernel, n, rays_host, t_min, out_host); });
 }
 // the SPPM gather diagnostic checks its arguments on the host, before it asks for a device (as shade_debug does)
 int rt_debug_sppm_gather_device(int device, rt_debug_sppm_gather* io) {

@@ -5318,3 +5318,5 @@ void debug_hit_device(const rt_scene& s, int kernel, size_t n, const double* ray
 #include "sppm_trace_debug.inc"
 // rt_debug_walk_device: closest hits of explicit rays with a ray time and a random stream (media, moving spheres)
 #include "walk_debug.inc"
+// rt_ao_render, rt_debug_occluded_device: the ambient-occlusion pass and the any-hit walks
+#include "ao.inc"

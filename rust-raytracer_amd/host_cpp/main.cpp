@@ -4,7 +4,7 @@
 //   rtamd_render [--scene cornell|FILE.json|FILE.yaml] [--cube data/mesh/cube.obj] [-w W] [-h H] [--spp N]
 //                [--depth D] [--seed S] [--aspect A] [--integrator 0|1] [--sppm ITERATIONS PHOTONS_PER_ITER]
 //                [--gpus N | --devices 0,1,...] [--background r,g,b | --sky] [--env-sampling] [--region x0,y0,x1,y1] [-o out.png]
-//                [--denoise [--aov-spp N] [--luma-mode M]] [--describe] [--vec3-selftest]
+//                [--denoise [--aov-spp N] [--luma-mode M]] [--ao FILE.png [--ao-rays K] [--ao-distance D]] [--describe] [--vec3-selftest]
 // --gpus N spreads the frame over N GPUs of this node inside ONE capture_image call (rt_render_multi: tiles dealt round-robin, RCCL
 // gather; 0 = all visible); --devices names the HIP ordinal of every rank (an ordinal may repeat).
 // `rtamd_render --cube data/mesh/cube.obj --sppm 50 500000` is the reference binary: SPPM pre-pass + 256 spp, output/test.png
@@ -16,7 +16,10 @@
 // --denoise renders the frame and filters it in one call (rt_denoised_render: --spp must be even) and writes the denoised PNG; --aov-spp N
 // guide rays per pixel (default 4; 0: none, for scenes with media or moving spheres), --luma-mode 1 (default) the energy-preserving
 // symmetric luminance stop, 0 rt_denoise's
+// --ao FILE.png writes the ambient-occlusion pass of the frame (rt_ao_render: 4 camera rays per pixel, --ao-rays K occlusion rays per hit,
+// default 4, that reach no farther than --ao-distance D, default unlimited) as the grey image visibility * coverage, and nothing else
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -64,6 +67,9 @@ int main(int argc, char** argv) {
     bool crop = false;
     bool denoise_frame = false;
     int aov_spp = 4, luma_mode = 1;
+    std::string ao_out;
+    int ao_rays = 4;
+    double ao_distance = INFINITY;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -99,6 +105,9 @@ int main(int argc, char** argv) {
         else if (a == "--denoise") denoise_frame = true;
         else if (a == "--aov-spp") aov_spp = std::atoi(next());
         else if (a == "--luma-mode") luma_mode = std::atoi(next());
+        else if (a == "--ao") ao_out = next();
+        else if (a == "--ao-rays") ao_rays = std::atoi(next());
+        else if (a == "--ao-distance") ao_distance = std::atof(next());
         else if (a == "-o") out = next();
         else if (a == "--checkpoint") { checkpoint = next(); }
         else if (a == "--run-samples") run_samples = std::atoi(next());
@@ -142,6 +151,21 @@ int main(int argc, char** argv) {
             img.save(out);
             std::printf("region (%d, %d, %d, %d): %llu samples traced, kernel %.1f ms, %.3fs\n", region.x0, region.y0, region.x1, region.y1,
                         (unsigned long long)st.samples, st.kernel_ms, std::chrono::duration<double>(std::chrono::steady_clock::now() - rt_start).count());
+            return 0;
+        }
+        if (!ao_out.empty()) {
+            const std::vector<double> ao = world->render_ao(cfg, 4, ao_rays, ao_distance, 0, &st);
+            const size_t npix = (size_t)cfg.width * cfg.height;
+            std::vector<double> grey(npix * 3);
+            for (size_t i = 0; i < npix; i++) grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = ao[8 * i] * ao[8 * i + 7];
+            RgbImage img;
+            img.width = cfg.width;
+            img.height = cfg.height;
+            img.data.resize(grey.size());
+            check(rt_tonemap_u8(grey.data(), grey.size(), img.data.data()));
+            img.save(ao_out);
+            std::printf("ambient occlusion (%d rays per hit): %llu camera rays, kernel %d, %.1f ms, %.3fs\n", ao_rays, (unsigned long long)st.samples,
+                        st.kernel_used, st.kernel_ms, st.seconds);
             return 0;
         }
         if (denoise_frame) {

@@ -535,6 +535,21 @@ class World {
         return aov;
     }
 
+    // Ambient occlusion (rt_ao_render): [height][width][8] = {visibility, bent normal[3], ambient[3], coverage} from ao_spp
+    // camera rays per pixel and rays_per_hit occlusion rays per hit that reach no farther than max_distance
+    std::vector<double> render_ao(const Config& cfg, int ao_spp = 4, int rays_per_hit = 4, double max_distance = INFINITY, int kernel = 0,
+                                  rt_stats* stats = nullptr) const {
+        rt_params p;
+        rt_default_params(&p);
+        p.width = cfg.width; p.height = cfg.height; p.t_min = cfg.t_min; p.seed = cfg.seed; p.kernel = kernel;
+        rt_ao_config ac;
+        rt_default_ao_config(&ac);
+        ac.ao_spp = ao_spp; ac.rays_per_hit = rays_per_hit; ac.max_distance = max_distance;
+        std::vector<double> ao((size_t)cfg.width * cfg.height * 8);
+        check(rt_ao_render(s_, &cam.c, &p, &ac, ao.data(), stats));
+        return ao;
+    }
+
     // One call from scene to clean frame (rt_denoised_render): cfg.sample_per_pixel (even) samples in two halves, their
     // variance, aov_spp guide rays per pixel (0: none -- scenes with media or moving spheres) and the a-trous filter, all on the device.
     // luma_mode 1 is the energy-preserving symmetric luminance stop (rt_denoise_sym), 0 rt_denoise's; dcfg NULL =

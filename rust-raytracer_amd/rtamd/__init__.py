@@ -95,6 +95,10 @@ class rt_denoise_config(C.Structure):
                 ("sigma_luma", C.c_double), ("eps", C.c_double), ("guides", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
+class rt_ao_config(C.Structure):
+    _fields_ = [("ao_spp", C.c_int32), ("rays_per_hit", C.c_int32), ("max_distance", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
 class rt_adaptive_config(C.Structure):
     _fields_ = [("min_spp", C.c_int32), ("reserved", C.c_int32), ("threshold", C.c_double)]
 
@@ -228,6 +232,10 @@ _SIGS = [
                                      _dp, _dp, _dp, _dp, C.POINTER(rt_stats)]),
     ("rt_denoised_render_device", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_denoise_config), C.c_int32,
                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(rt_stats)]),
+    ("rt_default_ao_config", None, [C.POINTER(rt_ao_config)]),
+    ("rt_ao_render", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_ao_config), _dp, C.POINTER(rt_stats)]),
+    ("rt_ao_render_device", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_ao_config), C.c_void_p, C.c_void_p,
+                                      C.POINTER(rt_stats)]),
     ("rt_default_adaptive_config", None, [C.POINTER(rt_adaptive_config)]),
     ("rt_render_adaptive", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_adaptive_config), _dp,
                                      C.POINTER(C.c_int32), C.POINTER(rt_stats)]),
@@ -267,6 +275,7 @@ _SIGS = [
     ("rt_debug_light_sample_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, C.POINTER(C.c_uint64), _dp]),
     ("rt_debug_light_pdf_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, _dp, _dp]),
     ("rt_debug_walk_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, _dp, C.POINTER(C.c_uint64), C.c_double, _dp]),
+    ("rt_debug_occluded_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, _dp, C.c_double, _dp]),
     ("rt_debug_sppm_gather_device", C.c_int, [C.c_int, C.POINTER(rt_debug_sppm_gather)]),
     ("rt_debug_sppm_trace_device", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.c_int, C.POINTER(rt_debug_sppm_trace)]),
     ("rt_debug_grid_shape", C.c_int, [_dp, _dp, C.c_uint64, _dp, C.POINTER(C.c_int32)]),
@@ -785,6 +794,32 @@ class World:
         _chk(self.L.rt_render_aov(self.h, C.byref(camera.c), C.byref(p), int(aov_spp), out.ctypes.data_as(_dp), C.byref(st)))
         return out, st.as_dict()
 
+    # --- ambient occlusion ---
+    def _ao_config(self, ao_spp, rays_per_hit, max_distance):
+        c = rt_ao_config()
+        self.L.rt_default_ao_config(C.byref(c))
+        c.ao_spp, c.rays_per_hit, c.max_distance = int(ao_spp), int(rays_per_hit), float(max_distance)
+        return c
+
+    def render_ao(self, camera, width, height, ao_spp=4, rays_per_hit=4, max_distance=float("inf"), seed=1, kernel=0, t_min=1e-3, device=-1):
+        """rt_ao_render: [H, W, 8] = {visibility, bent normal[3], ambient[3], coverage} from ao_spp camera rays per pixel (render()'s
+        first samples) and rays_per_hit cosine-distributed occlusion rays per hit, no farther than max_distance; returns (ao, stats dict)."""
+        p = default_params(width=width, height=height, seed=seed, kernel=kernel, t_min=t_min, device=device)
+        c = self._ao_config(ao_spp, rays_per_hit, max_distance)
+        out = np.zeros((height, width, 8), dtype=np.float64)
+        st = rt_stats()
+        _chk(self.L.rt_ao_render(self.h, C.byref(camera.c), C.byref(p), C.byref(c), out.ctypes.data_as(_dp), C.byref(st)))
+        return out, st.as_dict()
+
+    def render_ao_device(self, camera, params, d_out_ptr, ao_spp=4, rays_per_hit=4, max_distance=float("inf"), stream_ptr=None):
+        """rt_ao_render_device: the same into DEVICE memory at d_out_ptr ([H, W, 8] f64) on the HIP stream stream_ptr; returns the stats
+        dict after the work has completed on that stream."""
+        c = self._ao_config(ao_spp, rays_per_hit, max_distance)
+        st = rt_stats()
+        _chk(self.L.rt_ao_render_device(self.h, C.byref(camera.c), C.byref(params), C.byref(c), C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr or 0),
+                                        C.byref(st)))
+        return st.as_dict()
+
     def render_denoised(self, camera, width=800, height=800, spp=256, guides=True, aov_spp=4, max_depth=50, t_min=1e-3, seed=1,
                         kernel=0, device=-1, integrator=0, native=False, luma_mode=1, **cfg):
         """A frame, its variance and its guides, filtered by rt_denoise.  native=True: the one call rt_denoised_render, which keeps
@@ -902,6 +937,14 @@ class World:
         _chk(self.L.rt_debug_walk_device(self.h, int(device), int(kernel), r.shape[0], r.ctypes.data_as(_dp), k.ctypes.data_as(C.POINTER(C.c_uint64)),
                                          float(t_min), out.ctypes.data_as(_dp)))
         return out
+
+    def debug_occluded(self, rays7, t_min=1e-3, kernel=1, device=0):
+        """rt_debug_occluded_device: rays7 [n, 7] = origin, direction, t_max -> bool [n]: some surface lies within [t_min, t_max] of the
+        ray (the any-hit walk of render_ao's occlusion rays; kernel 1: reference order, 2: the accel)."""
+        r = np.ascontiguousarray(rays7, dtype=np.float64).reshape(-1, 7)
+        out = np.zeros(r.shape[0], dtype=np.float64)
+        _chk(self.L.rt_debug_occluded_device(self.h, int(device), int(kernel), r.shape[0], r.ctypes.data_as(_dp), float(t_min), out.ctypes.data_as(_dp)))
+        return out != 0.0
 
     def debug_sppm_trace(self, camera, width, height, iteration=0, photons_per_iter=1, max_bounces=4096, seed=1, capacity=(0, 0), rows=None,
                          photons=True, points=True, device=0):

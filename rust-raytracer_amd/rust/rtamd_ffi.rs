@@ -235,6 +235,16 @@ pub struct rt_area_tri {
     pub light: i32,
 }
 
+/// include/rtamd.h rt_ao_config (rt_default_ao_config fills it)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct rt_ao_config {
+    pub ao_spp: i32,
+    pub rays_per_hit: i32,
+    pub max_distance: c_double,
+    pub reserved: [i32; 4],
+}
+
 /// include/rtamd.h rt_adaptive_config (rt_default_adaptive_config fills it)
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -397,6 +407,9 @@ extern "C" {
     pub fn rt_region_tiles(p: *const rt_params, n_regions: c_int, regions: *const rt_region, capacity: i64, out_tiles: *mut i32) -> i64;
     pub fn rt_region_render(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, n_regions: c_int, regions: *const rt_region, out_rgb: *mut c_double, stats: *mut rt_stats) -> c_int;
     pub fn rt_region_render_device(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, n_regions: c_int, regions: *const rt_region, d_out_rgb: *mut c_double, hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
+    pub fn rt_default_ao_config(c: *mut rt_ao_config);
+    pub fn rt_ao_render(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, cfg: *const rt_ao_config, out_ao: *mut c_double, stats: *mut rt_stats) -> c_int;
+    pub fn rt_ao_render_device(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, cfg: *const rt_ao_config, d_out_ao: *mut c_double, hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
     pub fn rt_default_adaptive_config(c: *mut rt_adaptive_config);
     pub fn rt_render_adaptive(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, cfg: *const rt_adaptive_config, out_rgb: *mut c_double, out_tile_spp: *mut i32, stats: *mut rt_stats) -> c_int;
     pub fn rt_render_tiles_device(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, d_tiles: *mut c_double, hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
@@ -426,6 +439,7 @@ extern "C" {
     pub fn rt_debug_shade_device(s: *const rt_scene, device: c_int, n: usize, in_host: *const c_double, keys_host: *const u64, out_host: *mut c_double) -> c_int;
     pub fn rt_debug_light_sample_device(s: *const rt_scene, device: c_int, n: usize, in_host: *const c_double, keys_host: *const u64, out_host: *mut c_double) -> c_int;
     pub fn rt_debug_light_pdf_device(s: *const rt_scene, device: c_int, n: usize, rays_host: *const c_double, pdf_host: *mut c_double) -> c_int;
+    pub fn rt_debug_occluded_device(s: *const rt_scene, device: c_int, kernel: c_int, n: usize, rays_host: *const c_double, t_min: c_double, out_host: *mut c_double) -> c_int;
     pub fn rt_debug_walk_device(s: *const rt_scene, device: c_int, kernel: c_int, n: usize, rays_host: *const c_double, keys_host: *const u64, t_min: c_double, out_host: *mut c_double) -> c_int;
     pub fn rt_debug_sppm_gather_device(device: c_int, io: *mut rt_debug_sppm_gather) -> c_int;
     pub fn rt_debug_sppm_trace_device(s: *const rt_scene, cam: *const rt_camera, device: c_int, io: *mut rt_debug_sppm_trace) -> c_int;
@@ -785,6 +799,25 @@ impl Scene {
         let mut st = rt_stats::default();
         check(unsafe { rt_render_aov(self.raw, cam, p, aov_spp, out.as_mut_ptr(), &mut st) })?;
         Ok((out, st))
+    }
+    /// rt_ao_render: ambient occlusion, [height][width][8] = {visibility, bent normal[3], ambient[3], coverage}; cfg None = rt_default_ao_config
+    pub fn render_ao(&self, cam: &rt_camera, p: &rt_params, cfg: Option<&rt_ao_config>) -> Result<(Vec<f64>, rt_stats), RtError> {
+        let mut c = rt_ao_config::default();
+        unsafe { rt_default_ao_config(&mut c) };
+        if let Some(given) = cfg {
+            c = *given;
+        }
+        let mut out = vec![0.0f64; (p.width as usize) * (p.height as usize) * 8];
+        let mut st = rt_stats::default();
+        check(unsafe { rt_ao_render(self.raw, cam, p, &c, out.as_mut_ptr(), &mut st) })?;
+        Ok((out, st))
+    }
+    /// rt_debug_occluded_device: rays [n][7] = {origin, direction, t_max} -> true where a surface lies within [t_min, t_max] of the ray
+    pub fn debug_occluded(&self, device: i32, kernel: i32, rays: &[f64], t_min: f64) -> Result<Vec<bool>, RtError> {
+        let n = rays.len() / 7;
+        let mut out = vec![0.0f64; n];
+        check(unsafe { rt_debug_occluded_device(self.raw, device as c_int, kernel as c_int, n, rays.as_ptr(), t_min, out.as_mut_ptr()) })?;
+        Ok(out.iter().map(|&v| v != 0.0).collect())
     }
     /// rt_denoised_render: one call from scene to clean frame, everything but the results on the device.  p.spp even; luma_mode 1 = the
     /// energy-preserving symmetric luminance stop (rt_denoise_sym), 0 = rt_denoise's; aov_spp 0 = no guides (media, moving spheres);

@@ -23,6 +23,9 @@ usage (from the repository root, on a machine with an MI355X):
   python tools/launch_coverage.py --files tests/a.py tests/b.py --out part1.json     a subset -> a partial record
   python tools/launch_coverage.py --merge part1.json part2.json                      partial records -> the record (no device needed)
   python tools/launch_coverage.py --table                      the summary table of the committed record
+  python tools/launch_coverage.py --resource rust-raytracer_amd/csrc/device/ao.resource.txt --files tests/test_ao_gpu.py \
+         --out tests/golden/ao_launch_coverage.json            the record of another resource report (the kernels of csrc/device/ao.inc,
+                                                               whose rows `make asm` keeps apart): its kernels alone are the universe
 """
 import argparse
 import csv
@@ -93,14 +96,15 @@ def denoise_names():
         shutil.rmtree(tmp, ignore_errors=True)
 
 
-def universe():
-    """{mangled: {"source", "name"}} for kernels.hip (the committed resource report) and denoise.hip (compiled now)"""
-    with open(RESOURCE) as f:
+def universe(resource=None):
+    """{mangled: {"source", "name"}} for kernels.hip (the committed resource report) and denoise.hip (compiled now); resource: the rows
+    of that report alone (a part of kernels.hip kept in a file of its own)"""
+    with open(resource or RESOURCE) as f:
         k = resource_names(f.read())
-    d = denoise_names()
+    d = [] if resource else denoise_names()
     out = {}
     for src, names in (("kernels.hip", k), ("denoise.hip", d)):
-        for m, dm in zip(names, demangle(names)):
+        for m, dm in zip(names, demangle(names) if names else []):
             out[m] = {"source": src, "name": short_name(dm)}
     return out
 
@@ -298,6 +302,7 @@ def main():
     ap.add_argument("--merge", nargs="+", metavar="RECORD", help="join partial records instead of running anything")
     ap.add_argument("--table", action="store_true", help="print the summary table of --out and exit")
     ap.add_argument("--out", default=RECORD)
+    ap.add_argument("--resource", default=None, help="another resource report whose kernels alone are the universe (the record names it)")
     ap.add_argument("--timeout", type=int, default=600, help="time limit of one child, seconds")
     ap.add_argument("--logs", default=None, help="directory for the children's output, one file each")
     ap.add_argument("--pytest-args", default="", help="further arguments for every pytest child, e.g. '--durations=0'")
@@ -309,9 +314,11 @@ def main():
     if a.merge:
         write(merge(a.merge), a.out)
         return 0
-    uni = universe()
+    uni = universe(a.resource)
     rec = {"head": git_head(), "kernel_source_sha16": source_sha16(), "rocprofv3": tool_version(), "names": "mangled", "runs": {},
            "kernels": {m: dict(v) for m, v in uni.items()}}
+    if a.resource:
+        rec["resource"] = os.path.relpath(os.path.abspath(a.resource), ROOT)
     stopped = False
     for rel in (a.files or gpu_test_files()):
         rel = os.path.relpath(os.path.abspath(rel), ROOT)

@@ -92,7 +92,7 @@ typedef struct rt_params {
                             through mesh instances are queued per workgroup and served by full waves (auto when an
                             instance's object-space BVH has >= 64 nodes; needs 1..64 instances, at least one of f32-vertex triangles);
                             6 = the same service across the whole GPU and across launches (parked paths in HBM pools, a
-                            dedicated walk launch per cycle; 1..64 instances; by request only -- it is slower than
+                            dedicated walk launch per cycle; 1..64 instances, at least one of f32-vertex triangles, as kernel 5; by request only -- it is slower than
                             kernel 5; workspace within rt_tuning.wf_workspace_mb, default 1.9 GB).
                             All give bit-identical images (same f64 primitive tests, same tie rule: when two objects share the
                             closest t EXACTLY the later-visited one wins unless the reference's own BVHNode box test would have
@@ -174,7 +174,9 @@ int rt_texture_image(rt_scene* s, int width, int height, const uint8_t* rgb);
  * 0.5 (1 + sin(scale p.z + 10 turb(p))) over Perlin noise with 7 octaves of turbulence; the 256 gradient vectors and the three
  * permutations come from the RNG stream (seed, "perlin" key, 0); sin is the deterministic rtamd-sin-1 (csrc/common/detsin.h).
  * The lattice index of an octave's coordinate x is floor(x) mod 256 of the mathematical integer (0..255) for every finite x -- so 0 for
- * every |x| >= 2^60 -- and 0 for a non-finite x: defined at every coordinate a scene can hold (see "diagnostics", Noise). */
+ * every |x| >= 2^60 -- and 0 for a non-finite x: defined at every coordinate a scene can hold (see "diagnostics", Noise).
+ * A scene that holds a noise texture -- on a material or as its background -- is a book-2 scene, as one with moving spheres or an open
+ * shutter: it renders with kernels 1 and 2 and integrator 0; integrator 1 and kernels 5 / 6 are RT_ERR_UNSUPPORTED. */
 int rt_texture_noise(rt_scene* s, double scale, uint64_t seed);
 /* material.rs:88-212  Lambertian::new / Metal::new / Dielectric::new / DiffuseLight::new */
 int rt_material_lambertian(rt_scene* s, int albedo_tex);
@@ -189,7 +191,8 @@ int rt_material_isotropic(rt_scene* s, int albedo_tex);
 int rt_object_sphere(rt_scene* s, const double center[3], double radius, int material);
 /* Book-2 extension, no reference counterpart: moving_sphere(center0, center1, time0, time1, radius, material) -- Sphere::hit around
  * the centre center0 + (center1 - center0) (ray.time - time0) / (time1 - time0); box = the union of the boxes at both times.
- * Rendered by kernels 1 and 2 with integrator 0; needs rt_params.time1 > rt_params.time0 to move.  The shutter [rt_params.time0,
+ * Rendered by kernels 1 and 2 with integrator 0 (integrator 1 and kernels 5 / 6 are RT_ERR_UNSUPPORTED, also for any scene rendered with
+ * an open shutter); needs rt_params.time1 > rt_params.time0 to move.  The shutter [rt_params.time0,
  * rt_params.time1] must lie inside [time0, time1] of every moving sphere of the scene (their boxes are the union of the boxes at those two
  * times): a render with a shutter outside that range is refused with RT_ERR_ARG */
 int rt_object_moving_sphere(rt_scene* s, const double center0[3], const double center1[3], double time0, double time1, double radius, int material);
@@ -409,7 +412,15 @@ const char* rt_spec_version(void);
 /* ---- the hot path -------------------------------------------------------- */
 /* Camera::capture_image (camera.rs:66-128) minus the u8 conversion: linear radiance (sum/spp), f64 RGB,
  * row-major, y down, into caller-owned HOST memory out_rgb[height*width*3].  world > 1 renders only this
- * rank's tiles (others left 0). */
+ * rank's tiles (others left 0).
+ * Where a call meets several of the refusals documented with the builders above, the first of this list answers (p->kernel 0 picks a
+ * kernel that steps 1 to 4 accept, so only steps 5 to 7 can refuse it):
+ *   1. a background and kernel 5 / 6: RT_ERR_UNSUPPORTED;           2. area lights, integrator 1 and kernel 5 / 6: RT_ERR_UNSUPPORTED;
+ *   3. kernel 5 / 6 on a scene they cannot render (a ConstantMedium, a book-2 scene, nested Transforms, no instance of f32-vertex
+ *      triangles, more than 64 instances): RT_ERR_UNSUPPORTED;        4. kernel 2 without a usable accel (a ConstantMedium under a
+ *      Transform among the reasons): RT_ERR_UNSUPPORTED;
+ *   5. integrator 1 on a scene without object lights, area lights and a sampled environment: RT_ERR_ARG;
+ *   6. integrator 1 on a book-2 scene: RT_ERR_UNSUPPORTED;           7. integrator 1 on a scene with a ConstantMedium: RT_ERR_UNSUPPORTED. */
 int rt_render(const rt_scene* s, const rt_camera* cam, const rt_params* p, double* out_rgb, rt_stats* stats);
 /* the same for a host that owns a constructed Camera (its stored frame); rt_camera_frame_from = Camera::new (camera.rs:24-55) */
 int rt_render_camera_frame(const rt_scene* s, const rt_camera_frame* frame, const rt_params* p, double* out_rgb, rt_stats* stats);
@@ -694,7 +705,10 @@ int rt_debug_math_device(int op, size_t n, const double* a_host, const double* b
  * fallback of kernel 5) or over the compact NodeQ / Tri32 copies (6: what the serving waves of kernels 5 / 6 walk), with the exact-tie rule;
  * 7 = 3 with the table's boxes tightened as a render tightens them, for the origin bound 2 * max(scene extent, largest |origin coordinate| of
  * this batch); a scene with instances keeps the stored boxes, as in a render): rays n*6 (orig,dir);
- * out n*12 = {hit, t, p[3], normal[3], front_face, u, v, leaf index in the reference-order program} */
+ * out n*12 = {hit, t, p[3], normal[3], front_face, u, v, leaf index in the reference-order program}.
+ * RT_ERR_UNSUPPORTED: a scene with moving spheres or a ConstantMedium (rt_debug_walk_device asks those); a kernel other than 1 on a scene
+ * without an accel; kernels 5 / 6 on a scene without 1..64 instances of which one holds only f32-vertex triangles (so on every scene with
+ * nested Transforms). */
 int rt_debug_hit_device(const rt_scene* s, int kernel, size_t n, const double* rays_host, double t_min, double t_max, double* out_host);
 /* the per-tile job sequence of one launch over samples [s_begin, s_end) for a rank that owns `tiles_owned` tiles on a GPU with `n_waves`
  * resident waves (host logic only, no device needed): out[25] = 5 rows {first round, first unit, first sample, samples per unit, units per
@@ -760,7 +774,8 @@ int rt_debug_light_pdf_device(const rt_scene* s, int device, size_t n, const dou
 int rt_debug_walk_device(const rt_scene* s, int device, int kernel, size_t n, const double* rays_host, const uint64_t* keys_host, double t_min,
                          double* out_host);
 /* any-hit of explicit rays, through the device function rt_ao_render's occlusion rays take: "would World::hit(ray, t_min, t_max) return
- * a hit", answered at the first primitive whose own test accepts a t in the range (no record, no tie rule).
+ * a hit", answered at the first primitive whose own test accepts a t in the range (no record, no tie rule); an acceptance at an end of the
+ * range, where World::hit's own box tests may cull the primitive (t_max = the distance of a cube face), is settled by the reference-order walk.
  *   rays_host n*7 = {origin[3], direction[3], t_max} (every row its own t_max, +inf allowed); out_host n doubles, 1.0 = occluded, 0.0 = not.
  *   kernel 1: the reference-order program, 2: the accel walk over the node array in global memory (nested chains where the scene has any).
  * Checked on the host first: RT_ERR_ARG (a null pointer, n == 0, a kernel outside 1..2), RT_ERR_NOT_COMMITTED, RT_ERR_UNSUPPORTED (a

@@ -69,11 +69,28 @@ DEV bool occluded(const Acc& A, D3 wo, D3 wd, double t_min, double t_max) {
     return false;
 }
 
+// The accel walk met a primitive that accepts a t at an end of the range: the reference's own walk decides.  World::hit may still miss
+// there: BVHNode::hit culls a node whose box interval, clipped to [t_min, t_max], has shrunk to a point (aabb.rs:28-30) -- a cube face
+// that IS its box's near face, asked with t_max = its hit distance -- and its slab arithmetic rounds apart from the primitive's own t, so
+// the cull also happens a few ulps inside the range.  The accel's padded f32 boxes never cull such a hit; the reference-order walk
+// tests the reference's boxes.  Out of line: rare (an explicit t_max or max_distance that equals a surface's distance), and the walk
+// keeps its registers.
+template <int GENERAL>
+__device__ __noinline__ bool occluded_at_range_end(const Acc& A, D3 wo, D3 wd, double t_min, double t_max) {
+    return occluded<GENERAL>(A, wo, wd, t_min, t_max);
+}
+enum { OCC_NO = 0, OCC_YES = 1, OCC_AT_END = 2 };  // occluded2's answers: OCC_AT_END = a primitive accepts at an end of the range
+DEV bool at_range_end(double t, double t_min, double t_max) {  // within 2^-48 (relative) of either end; false for t_max = +inf
+    return t * (1.0 + 0x1p-48) >= t_max || t * (1.0 - 0x1p-48) <= t_min;
+}
+
 // Any-hit through the accel: traverse2's plain form (Node2 array in global memory, the lane's stack a column of LDS words `stride`
 // apart, first row 0, at most FlatView::stack2 - 2 entries: "The stack" above traverse2) with the range [t_min, t_max] fixed.  The f32
-// boxes are conservative for every t in the range (box32's proof), so a primitive that accepts is reached.
+// boxes are conservative for every t in the range (box32's proof), so a primitive that accepts is reached; one that accepts at an end of the range
+// ends the walk with OCC_AT_END and is settled by the reference-order walk (ray_occluded calls occluded_at_range_end), whose boxes may
+// cull it as World::hit's do.
 template <int GENERAL>
-DEV bool occluded2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, double t_min, double t_max) {
+DEV int occluded2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, double t_min, double t_max) {
     D3 o = wo, d = wd;
     double a = sqlen(d);
     int cur_xf = -1;
@@ -105,7 +122,7 @@ DEV bool occluded2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, 
                 cur = REF_DONE;
             }
         }
-        if (cur == REF_DONE) return false;
+        if (cur == REF_DONE) return OCC_NO;
         if ((cur >> REF_TAG_SHIFT) == 1u) {  // leaf: the reference's f64 tests
             const uint32_t first = cur & REF_LEAF_FIRST_MASK, cnt = ((cur >> REF_LEAF_COUNT_SHIFT) & 7u) + 1u;
             uint32_t enter = REF_DONE;
@@ -114,15 +131,15 @@ DEV bool occluded2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, 
                 const uint32_t kind = it.x & NK_MASK, pl = it.x >> NK_BITS;
                 double t;
                 if (kind == NK_SPHERE) {
-                    if (sphere_hit(A.spheres + 2 * pl, o, d, a, t_min, t_max, t)) return true;
+                    if (sphere_hit(A.spheres + 2 * pl, o, d, a, t_min, t_max, t)) return at_range_end(t, t_min, t_max) ? OCC_AT_END : OCC_YES;
                 } else if (kind == NK_RECT_YZ || kind == NK_RECT_XZ || kind == NK_RECT_XY) {
-                    if (rect_hit(A.rects + 3 * pl, (int)kind - (int)NK_RECT_YZ, o, d, t_min, t_max, t)) return true;
+                    if (rect_hit(A.rects + 3 * pl, (int)kind - (int)NK_RECT_YZ, o, d, t_min, t_max, t)) return at_range_end(t, t_min, t_max) ? OCC_AT_END : OCC_YES;
                 } else if (kind == NK_CUBE) {
                     uint32_t side;
-                    if (cube_hit(A.rects + 3 * (pl >> 3), o, d, t_min, t_max, t, side)) return true;
+                    if (cube_hit(A.rects + 3 * (pl >> 3), o, d, t_min, t_max, t, side)) return at_range_end(t, t_min, t_max) ? OCC_AT_END : OCC_YES;
                 } else if (kind == NK_TRI) {
                     double b1, b2;
-                    if (tri_hit(A.tripre2 + 5 * (first + i), o, d, t_min, t_max, t, b1, b2)) return true;
+                    if (tri_hit(A.tripre2 + 5 * (first + i), o, d, t_min, t_max, t, b1, b2)) return at_range_end(t, t_min, t_max) ? OCC_AT_END : OCC_YES;
                 } else {  // an instance: its object-space BVH after the remaining items
                     enter = pl;
                 }
@@ -175,7 +192,9 @@ DEV bool ray_occluded(const Acc& A, uint32_t* stk, const int stride, D3 o, D3 d,
     const Hit h = ACCEL ? traverse2<GENERAL, false, false>(A, stk, stride, o, d, t_min, t_max) : traverse<GENERAL>(A, o, d, t_min, t_max);
     return h.node >= 0;
 #else
-    return ACCEL ? occluded2<GENERAL>(A, stk, stride, o, d, t_min, t_max) : occluded<GENERAL>(A, o, d, t_min, t_max);
+    if (!ACCEL) return occluded<GENERAL>(A, o, d, t_min, t_max);
+    const int r = occluded2<GENERAL>(A, stk, stride, o, d, t_min, t_max);
+    return r == OCC_AT_END ? occluded_at_range_end<GENERAL>(A, o, d, t_min, t_max) : r == OCC_YES;  // (the call after the walk's loops, as tie_resolve's)
 #endif
 }
 

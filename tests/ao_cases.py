@@ -96,6 +96,39 @@ def tie_rows():
     return _WALK["tie"]
 
 
+def cube_pair():
+    """a lone Cube (the reference's BVH box of a cube IS the cube: its faces lie on the box's faces) beside a sphere"""
+    if "cube" not in _PAIRS:
+        import oracle
+        import rtamd
+
+        def build(B):
+            grey = B.Lambertian(B.ConstantTexture((0.5, 0.5, 0.5)))
+            return [B.Cube((-1.13, 0.21, -0.87), (0.94, 1.92, 1.06), grey), B.Sphere((3.1, 1.2, 0.4), 0.9, grey)]
+        w = rtamd.World()
+        w.new(build(w), bvh_seed=1)
+        o = oracle.Scene()
+        o.World(build(o), 1)
+        _PAIRS["cube"] = (w, None, o)
+    return _PAIRS["cube"]
+
+
+def cube_face_rows():
+    """-> (rays7, expected, t_min): rays from outside the cube at points of its faces, each also asked with t_max = the oracle's own hit
+    distance and its two neighbours.  At t_max = t the reference's box test culls the cube (aabb.rs:28-30: the box interval, clipped to the
+    range, is a point), so World::hit misses where the cube's own test accepts: a walk over other boxes has to miss there too."""
+    if "cube" not in _WALK:
+        rng = np.random.default_rng(23)
+        lo, hi = np.array((-1.13, 0.21, -0.87)), np.array((0.94, 1.92, 1.06))
+        tgt = rng.uniform(lo, hi, (96, 3))
+        axis, side = rng.integers(0, 3, 96), rng.integers(0, 2, 96)
+        tgt[np.arange(96), axis] = np.where(side == 1, hi[axis], lo[axis])
+        org = tgt + rng.uniform(-1.0, 1.0, (96, 3))
+        org[np.arange(96), axis] = tgt[np.arange(96), axis] + np.where(side == 1, 1.0, -1.0) * rng.uniform(0.5, 4.0, 96)
+        _WALK["cube"] = _rows(cube_pair()[2], np.concatenate([org, tgt - org], axis=1), T_MIN, INF) + (T_MIN,)
+    return _WALK["cube"]
+
+
 # ---- scenes the pass refuses ------------------------------------------------------------------------------------------------------------
 def media_world():
     import rtamd

@@ -34,6 +34,7 @@ _WF_SPPM = "rt_render_sppm with kernel 6 hung as the first render of a process a
 WITHHELD = {"pt_kernel_wf<2, false, false>": _WF_SPPM, "pt_kernel_wf<2, false, true>": _WF_SPPM,
             "pt_kernel_wf<2, true, false>": _WF_SPPM, "pt_kernel_wf<2, true, true>": _WF_SPPM}
 
+NONZERO_FLOOR = 0.1  # an oracle frame with fewer lit pixels than one in ten would make the comparison close to vacuous
 SMALL = (20, 12)  # partial tiles on both edges: 3 x 2 tiles
 SMALL_SPP = dict(render=16, sppm=2)  # (integrator 0 finds the lamps by chance: 16 spp light more than one pixel in ten)
 SPPM_SMALL = dict(iterations=2, photons_per_iter=2000, k_global=20, k_caustic=5)

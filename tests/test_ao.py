@@ -182,3 +182,13 @@ def test_debug_occluded_checks_its_arguments_before_the_device():
         with pytest.raises(rtamd.RtError) as e:
             w.debug_occluded(rays)
         assert e.value.code == NO_DEVICE
+
+
+def test_cube_face_rows_hold_both_answers_at_the_exact_distance():
+    """asked with t_max = its own hit distance, a cube face that lies on the reference's box is culled for some rays and kept for others
+    (the box's slab arithmetic rounds apart from the face's own t); one double below it always misses, one above always hits"""
+    rays7, exp, _ = ac.cube_face_rows()
+    n = len(rays7) // 4
+    assert exp[:n].all()
+    at, below, above = exp[n:].reshape(-1, 3).sum(axis=0)
+    assert 0 < at < n and below == 0 and above == n

@@ -111,6 +111,14 @@ def test_any_hit_walk_on_shared_face_ties():
     _assert_walk(ac.tie_pair()[0], rays7, exp, t_min, "shared-face ties")
 
 
+def test_any_hit_walk_at_the_exact_distance_of_a_cube_face():
+    """t_max = the hit distance of a cube face that is its box's near face: World::hit misses (the reference culls the box), and so must
+    both walks (found by tests/test_soup_gpu.py: the accel walk answered with the cube's own test alone)"""
+    rays7, exp, t_min = ac.cube_face_rows()
+    assert exp.any() and not exp.all()
+    _assert_walk(ac.cube_pair()[0], rays7, exp, t_min, "cube faces")
+
+
 # ---- refusals -----------------------------------------------------------------------------------------------------------------------------
 def test_refusals_with_a_device_present():
     import rtamd

@@ -22,7 +22,7 @@ from seeded_windows import seeded_windows
 pytestmark = pytest.mark.gpu
 
 _ORACLE = {}
-NONZERO_FLOOR = 0.1  # an oracle frame with fewer lit pixels than one in ten would make the comparison close to vacuous
+NONZERO_FLOOR = rs.NONZERO_FLOOR
 
 
 def _oracle(case, W, H, spp, seed, cfg):

@@ -430,7 +430,7 @@ int rt_camera_frame_from(const rt_camera* cam, rt_camera_frame* out);
  * {photons_per_iter photon paths -> global + caustic photon maps; one eye ray per pixel; progressive radius update}) followed
  * by capture_image with SPPMIntegrator::sample_ray (photon_mapper.rs:327-365: the first Diffuse hit adds the pixel's estimates
  * and ends the path).  Needs rt_scene_set_lights with lights made by rt_object_*_light.  One GPU, whole frame:
- * p->world != 1 is RT_ERR_ARG.
+ * p->world != 1 is RT_ERR_ARG.  Refusals, the first that applies: a background, area lights (RT_ERR_UNSUPPORTED), a scene without object lights: RT_ERR_ARG, the book-2 kinds, a light in a medium; the kernel's own (spp > 0) after the pre-pass.
  * stats_out (optional, HOST, height*width*10 f64): per pixel {global: flux[3], radius2, photons; caustic: flux[3], radius2, photons}.
  * spp == 0 runs the pre-pass only (out_rgb may be NULL).  rt_stats.reserved[0] = pre-pass time in microseconds. */
 typedef struct rt_sppm_config {

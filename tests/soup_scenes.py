@@ -17,7 +17,10 @@ header line it restates beside it.  Nothing here reads the library's own kernel 
 
 Replaced indices.  REPLACED: recipes whose HIP frame or record differed from the oracle's in a way DESIGN.md s2 documents as measure zero
 (shown from the oracle alone), at most two.  VACUOUS: recipes that failed a condition of tests/test_soup_scenes.py when the corpus was
-written (a frame too dark, a primitive kind no test ray reaches, ...).  CORPUS passes over both."""
+written (a frame too dark, a primitive kind no test ray reaches, ...).  CORPUS passes over both.
+
+SPPM.  The recipes rt_render_sppm renders have a sub-corpus of their own, SPPM_CORPUS, with its axes, cells, configuration and passed-over
+tables (the last section of this file; tests/test_soup_sppm_scenes.py, tests/test_soup_sppm_gpu.py)."""
 import hashlib
 
 import numpy as np
@@ -450,12 +453,14 @@ class _Side:
                 o = B.XZRectangle(d[2], d[3], d[4], B.DiffuseLight(B.ConstantTexture(d[5])))
             else:
                 o = B.XZRectLight(d[2], d[3], d[4], d[5], 1.0)
+            self.flux[o] = d[5]
             return self.note(o, group, ("light", ("const", d[5])))
         if kind == "spherelight":
             if self.oracle:
                 o = B.Sphere(d[2], d[3], B.DiffuseLight(B.ConstantTexture(d[4])))
             else:
                 o = B.SphereDiffuseLight(d[2], d[3], d[4], 1.0)
+            self.flux[o] = d[4]
             return self.note(o, group, ("light", ("const", d[4])))
         raise KeyError(kind)
 
@@ -733,7 +738,8 @@ def facts(rec):
     for d in r["items"]:
         _walk(d, see)
     f["noise"] = any(t[0] == "noise" for t in _textures(rec))
-    f["book2"] = f["moving"] or f["noise"] or r["shutter"] is not None
+    f["shutter"] = r["shutter"] is not None
+    f["book2"] = f["moving"] or f["noise"] or f["shutter"]
     f["background"] = r["background"] is not None
     f["env"] = r["env"] is not None
     f["lights"] = len(r["lights"])
@@ -762,12 +768,25 @@ RULES = (
     ("debug_hit", lambda f, k, i: k in (5, 6) and not (f["f32_instance"] and not f["nest"]), UNSUPPORTED, 710, "kernels 5 / 6 on a scene without 1..64 instances"),
     ("debug_occluded", lambda f, k, i: f["media"] or f["moving"], UNSUPPORTED, 782, "scene with a ConstantMedium or moving spheres"),
     ("debug_walk", lambda f, k, i: k in (2, 3) and f["media_xf"], UNSUPPORTED, 770, "kernel 2 or 3 on a scene without an accel"),
+    # rt_render_sppm: the first five rows in the order include/rtamd.h:433 gives (a background or area lights answer before the missing
+    # object lights do); the kernel's own refusals come after the pre-pass and share one code
+    ("render_sppm", lambda f, k, i: f["background"], UNSUPPORTED, 298, "rt_render_sppm* are RT_ERR_UNSUPPORTED for a scene with a"),
+    ("render_sppm", lambda f, k, i: f["area"], UNSUPPORTED, 374, "rt_render_sppm* (the photon pass has no emitter for them) are RT_ERR_UNSUPPORTED"),
+    ("render_sppm", lambda f, k, i: not f["lights"], ARG, 433, "a background, area lights (RT_ERR_UNSUPPORTED), a scene without object lights: RT_ERR_ARG, the book-2 kinds"),
+    ("render_sppm", lambda f, k, i: f["moving"] or f["shutter"], UNSUPPORTED, 855, "RT_ERR_UNSUPPORTED (a background, area lights, moving spheres, noise"),
+    ("render_sppm", lambda f, k, i: f["noise"], UNSUPPORTED, 856, "textures, a light inside a ConstantMedium), RT_ERR_ARG (no lights)"),
+    ("render_sppm", lambda f, k, i: k == 5 and not f["service"], UNSUPPORTED, 93, "needs 1..64 instances, at least one of f32-vertex triangles"),
+    ("render_sppm", lambda f, k, i: k == 2 and f["media_xf"], UNSUPPORTED, 228, "a ConstantMedium under a Transform, at any depth, renders through kernel 1 only"),
 )
+WITHHELD = "withheld"   # rt_render_sppm with kernel 6: not asked of any scene (reach_scenes.WITHHELD: the call hung on the device, cause not found)
 
 
 def expected(rec, entry, kernel, integrator=0, no_lds=0):
     """FRAME, or the rt_status the call must fail with.  entry: "render", "render_aov", "render_ao", "debug_hit", "debug_occluded",
-    "debug_walk".  no_lds changes where the scene lives, never what a call does (rt_tuning: `how (never what) it renders`)."""
+    "debug_walk", "render_sppm".  no_lds changes where the scene lives, never what a call does (rt_tuning: `how (never what) it renders`).
+    "render_sppm" with kernel 6 is WITHHELD for every recipe: never a frame, and no test makes that call."""
+    if entry == "render_sppm" and kernel == 6:
+        return WITHHELD
     f = facts(rec)
     for entries, cond, result, _, _ in RULES:
         if entry in entries.split() and cond(f, kernel, integrator):
@@ -775,16 +794,16 @@ def expected(rec, entry, kernel, integrator=0, no_lds=0):
     return FRAME
 
 
-def auto_kernel(rec, integrator):
+def auto_kernel(rec, integrator, entry="render"):
     """the kernel the automatic choice (kernel 0) must report, in rt_params.kernel's words: 5 `when an instance's object-space BVH has >= 64
     nodes` (the torus under one Transform; cube.obj has fewer) and kernel 5 renders the call, else 2 `whenever the scene has a usable
-    accel`, else 1; kernel 6 runs `by request only`"""
+    accel`, else 1; kernel 6 runs `by request only`.  entry: "render", or "render_sppm" (whose final pass chooses likewise)"""
     torus = []
     for d in dict(rec)["items"]:
         _walk(d, lambda x: torus.append(1) if x[0] == "xf" and len(x[2]) == 1 and x[3][0] == "torus" else None)
-    if torus and expected(rec, "render", 5, integrator) == FRAME:
+    if torus and expected(rec, entry, 5, integrator) == FRAME:
         return 5
-    return 2 if expected(rec, "render", 2, integrator) == FRAME else 1
+    return 2 if expected(rec, entry, 2, integrator) == FRAME else 1
 
 
 # What the corpus must reach beside the pairs: every cell of the render matrix, and every other entry point, gives a frame (records, rows)
@@ -813,3 +832,133 @@ def cells_of(rec):
 def allowed_kernels(rec, integrator):
     """the kernels an automatic choice (kernel 0) may report for a recipe: those the rules let render it"""
     return {k for k in (1, 2, 5, 6) if expected(rec, "render", k, integrator) == FRAME}
+
+
+# ---- SPPM on composed scenes (tests/test_soup_sppm_scenes.py without a device, tests/test_soup_sppm_gpu.py on one) --------------------------------------
+# rt_render_sppm renders a recipe without a background, area lights, moving spheres, an open shutter and noise textures that has an object
+# light (RULES).  SPPM_CORPUS walks the indices below SPPM_RANGE whose expected(rec, "render_sppm", 1) is FRAME, in increasing order, and keeps
+# an index when its recipe shows a pair of sppm_axes values no kept recipe showed, or fills a cell of SPPM_CELLS that fewer than MIN_SCENES
+# kept recipes fill; it ends when every pair that occurs among those indices (the ones passed over aside) has occurred and every cell is
+# full.  It is written down here, so that importing this module draws no 4000 recipes; sppm_corpus() computes it and
+# tests/test_soup_sppm_scenes.py holds the two equal.  No kernel 6: expected() answers WITHHELD for it.
+SPPM_CFG = dict(iterations=3, photons_per_iter=20000, k_global=20, k_caustic=5)
+SPPM_SPP = 2
+SPPM_RANGE = 4000
+SPPM_AXIS_NAMES = ("root",) + PRIMITIVE_AXES + ("depth", "special", "coplanar", "scale", "lights")
+SPPM_CELLS = (("render_sppm", 1), ("render_sppm", 2), ("render_sppm", 5), ("auto", 5))
+SPPM_REPLACED = {}   # index -> the measure-zero condition (DESIGN.md s2, RT_ERR_UNIT_ZERO) its recipe meets, shown from the oracle alone; at most two
+# index -> the condition of tests/test_soup_sppm_scenes.py its recipe failed when the corpus was written
+SPPM_VACUOUS = {94: "lit"}   # no specular surface: the caustic map stays empty, its radius^2 is 0 and the frame is NaN or black everywhere
+SPPM_CORPUS = (2, 13, 173, 184, 203, 221, 225, 246, 250, 256, 319, 340, 364, 370, 393, 472, 484, 494, 515, 520, 532, 539, 584, 587, 716, 732, 781, 913,
+               920, 1030, 1218, 1450)
+SPPM_CORPUS_LENGTH = 32   # len(SPPM_CORPUS) == len(sppm_corpus()[0]), written down
+
+
+def sppm_axes(rec):
+    """the axis values the SPPM sub-corpus crosses: root, the six primitive axes, depth, special (none / medium / medium_xf: a medium under
+    a Transform), coplanar, scale, and the kinds of the object lights (rect / sphere / both; none where the recipe has no object light)"""
+    ax, f, r = axes_of(rec), facts(rec), dict(rec)
+    out = {a: ax[a] for a in SPPM_AXIS_NAMES[:-1]}
+    out["special"] = "medium_xf" if f["media_xf"] else "medium" if f["media"] else ax["special"]
+    kinds = {r["items"][i][0] for i in r["lights"]}
+    out["lights"] = "both" if len(kinds) == 2 else "rect" if kinds == {"xzlight"} else "sphere" if kinds else "none"
+    return out
+
+
+def sppm_pairs_of(rec):
+    ax = sppm_axes(rec)
+    return {((a, ax[a]), (b, ax[b])) for i, a in enumerate(SPPM_AXIS_NAMES) for b in SPPM_AXIS_NAMES[i + 1:]}
+
+
+def sppm_cells(rec):
+    """the SPPM_CELLS a recipe fills: ("render_sppm", k) where kernel k answers with a frame, ("auto", 5) where the automatic choice is kernel 5"""
+    if expected(rec, "render_sppm", 1) != FRAME:
+        return set()
+    out = {("render_sppm", k) for k in (1, 2, 5) if expected(rec, "render_sppm", k) == FRAME}
+    return out | ({("auto", 5)} if auto_kernel(rec, 0, "render_sppm") == 5 else set())
+
+
+def sppm_eligible():
+    """the indices below SPPM_RANGE that rt_render_sppm renders (through kernel 1), in increasing order (computed once)"""
+    if not _SPPM:
+        _SPPM.append(tuple(i for i in range(SPPM_RANGE) if expected(recipe(i), "render_sppm", 1) == FRAME))
+    return _SPPM[0]
+
+
+def sppm_corpus():
+    """SPPM_CORPUS by its definition (computed once) -> (the kept indices, the pairs they must cover)"""
+    if len(_SPPM) < 2:
+        live = [i for i in sppm_eligible() if i not in SPPM_VACUOUS and i not in SPPM_REPLACED]
+        pairs = {i: sppm_pairs_of(recipe(i)) for i in live}
+        need = set().union(*pairs.values())
+        out, covered, count = [], set(), {c: 0 for c in SPPM_CELLS}
+        for i in live:
+            if covered == need and min(count.values()) >= MIN_SCENES:
+                break
+            c = sppm_cells(recipe(i))
+            if pairs[i] - covered or any(count[x] < MIN_SCENES for x in c):
+                out.append(i)
+                covered |= pairs[i]
+                for x in c:
+                    count[x] += 1
+        _SPPM.append((tuple(out), need))
+    return _SPPM[1]
+
+
+_SPPM = []
+
+
+def _medium_bounds(d, levels=()):
+    """(centre, radius) of a sphere around every medium boundary in or under d, in world space.  A level p -> T + S (R p) takes the sphere
+    (c, r) into the sphere (T, max(S) (|c| + r)) whatever R is"""
+    out = []
+    if d[0] == "medium":
+        b = d[3]
+        if b[0] == "sphere":
+            c, rad = np.array(b[2]), float(b[3])
+        else:
+            assert b[0] == "cube", b[0]
+            c, rad = 0.5 * (np.array(b[2]) + np.array(b[3])), 0.5 * float(np.linalg.norm(np.array(b[3]) - np.array(b[2])))
+        for _, sc, tr in levels:
+            c, rad = np.array(tr), max(abs(x) for x in sc) * (float(np.linalg.norm(c)) + rad)
+        out.append((c, rad))
+    elif d[0] == "xf":
+        out += _medium_bounds(d[3], tuple(d[2]) + tuple(levels))
+    elif d[0] == "leaf":
+        out += _medium_bounds(d[3], levels)
+    return out
+
+
+def lights_clear_of_media(rec):
+    """no object light of the recipe touches a sphere around any of its media, from the description alone: the least distance between a
+    light's box and a medium's bounding sphere, in units of the recipe's scale (inf without a medium); > 0 is clear"""
+    r = dict(rec)
+    gap = float("inf")
+    for i in r["lights"]:
+        d = r["items"][i]
+        if d[0] == "xzlight":
+            lo, hi = np.array([d[2][0], d[4], d[2][1]]), np.array([d[3][0], d[4], d[3][1]])
+        else:
+            lo, hi = np.array(d[2]) - d[3], np.array(d[2]) + d[3]
+        for item in r["items"]:
+            for c, rad in _medium_bounds(item):
+                gap = min(gap, (float(np.linalg.norm(np.maximum(np.maximum(lo - c, c - hi), 0.0))) - rad) / r["scale"])
+    return gap
+
+
+def build_oracle_sppm(rec):
+    """build_oracle with every object light's flux and scale set: under SPPM a photon's power is flux x scale (build_oracle leaves both
+    at the oracle's defaults, which path tracing never reads) -> the oracle's _Side"""
+    side = build_oracle(rec)
+    lights = [side.built[i] for i in dict(rec)["lights"]]
+    side.b.set_lights(lights, flux=[side.flux[i] for i in lights], scale=[1.0] * len(lights))
+    return side
+
+
+def build_pair_sppm(rec):
+    """-> (rtamd.World committed, rtamd.Camera, the oracle's _Side with flux and scale set)"""
+    import light_scenes as ls
+    import rtamd
+    w = _build_side(rec, _Side(ls.deferred_world(), False), False, False).b
+    rtamd.World.commit(w)
+    return w, ls._camera(dict(rec)["camera"]), build_oracle_sppm(rec)

@@ -8,7 +8,9 @@ tests/test_soup_scenes.py shows without a device that the scenes and rays reach 
 
 A failure names the recipe index, the call and the first differing pixel or ray: soup_scenes.build(soup_scenes.recipe(index)) rebuilds
 the scene.  Scenes with a medium or moving spheres, whose closest hit needs a random stream and a ray time (rt_debug_hit_device refuses
-them), have their test rays asked through rt_debug_walk_device instead.  No test runs rt_render_sppm (reach_scenes.WITHHELD)."""
+them), have their test rays asked through rt_debug_walk_device instead.  rt_render_sppm runs on composed scenes too, never through
+kernel 6 (soup_scenes.WITHHELD): here every call of it the header refuses, on the smallest configuration; tests/test_soup_sppm_gpu.py
+holds the frames of the recipes it renders."""
 import numpy as np
 import pytest
 
@@ -54,7 +56,7 @@ def test_soup(index, tuning):
     rec = ss.recipe(index)
     w, cam, side, kw = ss.build_pair(rec)
     o = side.b
-    counts = dict(frames=0, refusals=0, hit_records=0, occlusion_rows=0, guides=0, ao=0)
+    counts = dict(frames=0, refusals=0, hit_records=0, occlusion_rows=0, guides=0, ao=0, sppm_refusals=0)
     frames, by_kernel = {}, {}
 
     def oracle_frame(integ):
@@ -149,5 +151,14 @@ def test_soup(index, tuning):
             assert st["kernel_used"] == kernel, what
             _same_frame(got, ao, what)
             counts["ao"] += 1
+
+    # ---- what rt_render_sppm refuses (its frames: tests/test_soup_sppm_gpu.py) ----
+    for kernel in (0, 1, 2, 5):
+        exp = ss.expected(rec, "render_sppm", kernel)
+        if exp != ss.FRAME:
+            what = "recipe %d: render_sppm(kernel=%d)" % (index, kernel)
+            _refused(exp, what, lambda: w.render_sppm(cam, width=8, height=8, spp=1, seed=ss.SEED, t_min=ss.T_MIN, kernel=kernel, iterations=1, photons_per_iter=500))
+            counts["refusals"] += 1
+            counts["sppm_refusals"] += 1
     assert counts["frames"] >= 3, "recipe %d: kernel 1 renders every recipe with integrator 0, in and out of LDS, and so does the automatic choice -- %s" % (index, counts)
     print("recipe %d: %s frames by (kernel, integrator): %s" % (index, " ".join("%s=%d" % kv for kv in counts.items()), sorted(by_kernel.items())))

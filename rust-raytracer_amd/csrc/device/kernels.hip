@@ -2448,10 +2448,10 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
                 }
             }
             PH_END(0, ph_it0);
-            if (__ballot(alive) == 0ull) {
-                if (next >= pool && finished) break;
-                continue;
-            }
+            // (no lane alive and work left: the segment below is skipped as a whole.  Not a `continue` of its own: a second way back to the
+            // loop head, on which the path state is not written, keeps the compiler from holding that state in one set of registers, and it
+            // then copies all of it around the walk three times per iteration -- DESIGN.md s5-r13)
+            if (__ballot(alive) == 0ull && next >= pool && finished) break;
             // ---- one path segment: sample_ray's loop body, photon_mapper.rs:335-362 ----
             if (alive) {
                 PH_EV(13);
@@ -2467,7 +2467,9 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
                     PH_BEGIN(ph_m0);
                     Rec rec = materialize<GENERAL>(A, h, o, d, err);
                     PH_END(2, ph_m0);
-                    D3 emitted, att, ndir;
+                    // (ndir starts from a value: shade() leaves it unwritten where a Metal absorbs, and a variable that one path leaves
+                    // unwritten keeps last iteration's value as far as the compiler can tell -- three more register pairs of loop state)
+                    D3 emitted, att, ndir = d;
                     bool diffuse;
                     PH_BEGIN(ph_s0);
                     bool scattered = shade<GENERAL>(A, rec, d, rng, emitted, att, ndir, diffuse, err);

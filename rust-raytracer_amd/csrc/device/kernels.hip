@@ -1073,9 +1073,14 @@ DEV Hit traverse2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, d
                 cur = REF_DONE;
             }
         }
-        if (cur == REF_DONE) break;
+        // WIDE: the loop is left at its bottom only.  With this exit in the middle the compiler's unified latch has a way in
+        // -- that of the lanes that leave here -- on which the hit is not written, and it then keeps `h` in two register sets, copied at the
+        // loop header and in front of the leaf section and the pop (the rule of s5-r13: no way back to a loop's head on which loop state is
+        // undefined).  A lane that is through skips the leaf section and the pop instead and meets the test below.
+        if (!WIDE && cur == REF_DONE) break;
         PH_BEGIN(ph_leaf0);
-        if ((cur >> REF_TAG_SHIFT) == 1u) {  // leaf: test its items with the reference's f64 routines
+        if (WIDE && cur == REF_DONE) {
+        } else if ((cur >> REF_TAG_SHIFT) == 1u) {  // leaf: test its items with the reference's f64 routines
             uint32_t first = cur & REF_LEAF_FIRST_MASK, cnt = ((cur >> REF_LEAF_COUNT_SHIFT) & 7u) + 1u;
             uint32_t enter = REF_DONE;
             for (uint32_t i = 0; i < cnt; i++) {
@@ -1182,8 +1187,10 @@ DEV Hit traverse2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, d
             if (WIDE) ray32_wide_addr(r, A.n2w_lds);
         }
         if (WIDE) {
-            spw -= spw_step;
-            cur = *(const AS_L uint32_t*)(uintptr_t)spw;
+            if (cur != REF_DONE) {
+                spw -= spw_step;
+                cur = *(const AS_L uint32_t*)(uintptr_t)spw;
+            }
         } else if (sp > 0) {
             sp -= stride;
             cur = stk[sp];
@@ -1191,6 +1198,11 @@ DEV Hit traverse2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, d
             cur = REF_DONE;
         }
         PH_END(9, ph_leaf0);
+        if (WIDE) {
+            // (no instruction: it keeps the compiler from carrying the test above down here, which would restore the exit in the middle)
+            asm("" : "+v"(cur));
+            if (cur == REF_DONE) break;  // through before the leaf section, or the pop gave the sentinel
+        }
     }
     // the last exact tie noted, if its later party is still the hit: would the reference have visited that object at all?
     if (TIE && RESOLVE && tie_flagged(h.xf)) h = tie_resolve<GENERAL>(A, wo, wd, t_min, t_max, h);
@@ -1501,7 +1513,9 @@ DEV Rec materialize(const Acc& A, const Hit& h, D3 wo, D3 wd, int* err) {
     rec.u = 0.;
     rec.v = 0.;
     bool want_uv = false;
-    if (kind == NK_SPHERE) {  // sphere.rs:45-53
+    // (GENERAL == 0: the host picks the sphere-only variants for blobs that hold nothing else (scene_variant), and their walks accept no
+    // other kind; without the test the record's zero initialisation for "some other kind" leaves the hot loop -- DESIGN.md s5-r14)
+    if (GENERAL == 0 || kind == NK_SPHERE) {  // sphere.rs:45-53
         double2 c0 = A.spheres[2 * pl], c1 = A.spheres[2 * pl + 1];
         rec.mat = A.sphere_mat[pl];
         D3 p = add(o, muls(d, h.t));
@@ -1589,8 +1603,13 @@ DEV Rec materialize(const Acc& A, const Hit& h, D3 wo, D3 wd, int* err) {
 // branches: the texture lookup (every type reads its texture exactly once), the unit-sphere sample that Lambertian,
 // DiffuseLight and Metal all draw first, and the one normalisation each type performs (of that sample for the diffuse
 // types, of the incoming direction for Metal and Dielectric).  Per lane the operations and their order are unchanged.
-template <int GENERAL = 1>
-DEV bool shade(const Acc& A, const Rec& rec, D3 rdir, Rng& rng, D3& emitted, D3& att, D3& out_dir, bool& diffuse, int* err) {
+struct NoEmitHook {
+    DEV void operator()(const D3&) const {}
+};
+// on_emitted(emitted) is called as soon as the emitted radiance is known, in front of the material branches: pt_kernel adds it to its
+// path's radiance there; every other caller reads `emitted` afterwards, as before.
+template <int GENERAL = 1, class EMIT = NoEmitHook>
+DEV bool shade(const Acc& A, const Rec& rec, D3 rdir, Rng& rng, D3& emitted, D3& att, D3& out_dir, bool& diffuse, int* err, EMIT on_emitted = EMIT()) {
     const MatDev mt = A.mats[rec.mat];
     const int type = mt.type;
     const bool lamb = (type == 0 || type == 3);  // Lambertian / DiffuseLight: Interaction::Diffuse (material.rs:111,207)
@@ -1599,6 +1618,7 @@ DEV bool shade(const Acc& A, const Rec& rec, D3 rdir, Rng& rng, D3& emitted, D3&
     const double FRAC_1_PI = 0.318309886183790671537767526745028724;
     emitted = (type == 3) ? tc : mk(0., 0., 0.);                                         // material.rs:209-211 (no face test)
     att = (type == 3) ? mk(1. * FRAC_1_PI, 1. * FRAC_1_PI, 1. * FRAC_1_PI) : tc;         // material.rs:201-203
+    on_emitted(emitted);
     D3 rs = mk(0., 0., 0.);
     if (type != 2) rs = random_in_unit_sphere(rng);  // Metal draws its fuzz sample even when fuzz == 0 (Q4)
     const D3 u = unit(lamb ? rs : rdir, err);
@@ -2465,35 +2485,53 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
                 if (h.node >= 0 && depth > 0) {  // Q12: depth test after the hit, before emission
                     depth -= 1;
                     PH_BEGIN(ph_m0);
-                    Rec rec = materialize<GENERAL>(A, h, o, d, err);
+                    const Rec rec = materialize<GENERAL>(A, h, o, d, err);
                     PH_END(2, ph_m0);
-                    // (ndir starts from a value: shade() leaves it unwritten where a Metal absorbs, and a variable that one path leaves
-                    // unwritten keeps last iteration's value as far as the compiler can tell -- three more register pairs of loop state)
-                    D3 emitted, att, ndir = d;
-                    bool diffuse;
+                    // The next segment's ray is written where it is computed: the hit point IS the next origin (no path
+                    // that goes on reads the old one again), and shade() writes the scattered direction into `d` itself, after its one
+                    // read of the incoming direction (its own copy, by value).  A path that ends here -- absorbed, or at a diffuse hit of
+                    // the SPPM pass -- never reads `o` / `d` again, and where a Metal absorbs shade() leaves `d` as it came in.  Held as
+                    // `rec.p` / a local `ndir` and assigned at the end, both rays were live through all of shade() and copied there.
+                    // (SEG_IN_PLACE is false for the two instantiations that this form costs 16 B of scratch: they keep round 13's.)
+                    constexpr bool SEG_IN_PLACE = !(GENERAL == 1 && !LDS && ACCEL == 2 && INTEG == INTEG_BG && MEDIA) &&
+                                                  !(GENERAL == 3 && LDS && ACCEL == 1 && INTEG == (INTEG_BG | 1));
+                    if (SEG_IN_PLACE) o = rec.p;
+                    D3 emitted, att, ndir = d;  // (ndir: only where !SEG_IN_PLACE; it starts from a value -- s5-r13)
+                    D3& nd = SEG_IN_PLACE ? d : ndir;
+                    bool diffuse, scattered;
                     PH_BEGIN(ph_s0);
-                    bool scattered = shade<GENERAL>(A, rec, d, rng, emitted, att, ndir, diffuse, err);
+                    if constexpr (GENERAL == 0) {
+                        // radiance += throughput * Le, in front of shade()'s material branches: behind them the old throughput is read after
+                        // the branch that scatters has written the new one, and the compiler keeps two copies of it.  (The empty asm holds
+                        // the sum where it is written; left alone the compiler moves it down to the end of the segment again.  Sphere-only
+                        // variants only: the general ones pay for the earlier sum with 16 B of scratch.)
+                        const auto add_emitted = [&](const D3& le) {
+                            L = add(L, elemul(beta, le));
+                            asm volatile("" : "+v"(L.x), "+v"(L.y), "+v"(L.z));
+                        };
+                        scattered = shade<GENERAL>(A, rec, d, rng, emitted, att, nd, diffuse, err, add_emitted);
+                    } else {
+                        scattered = shade<GENERAL>(A, rec, d, rng, emitted, att, nd, diffuse, err);
+                        L = add(L, elemul(beta, emitted));  // radiance += throughput * Le
+                    }
                     PH_END(3, ph_s0);
-                    L = add(L, elemul(beta, emitted));  // radiance += throughput * Le
                     if (scattered) {  // Diffuse continues like Specular/Reflect/Refract (photon_mapper.rs:346-347)
-                        bool go = true;
                         if ((INTEG & 3) == 2 && diffuse) {
                             const double* e = rk.sppm_est + 6 * (size_t)pix_id;
                             L = add(L, elemul(beta, mk(e[0], e[1], e[2])));  // caustic estimate
                             L = add(L, elemul(beta, mk(e[3], e[4], e[5])));  // global estimate
-                            go = false;
-                        } else if ((INTEG & 3) == 1 && diffuse) {
+                        } else if ((INTEG & 3) == 1 && diffuse) {  // (the mixture step ends the path where its weight is not > 0)
                             PH_EV(14);
-                            if (INTEG & INTEG_AREA) go = mixture_step_area(A, sv.base + sv.off_area, area_env, rec, rng, att, beta, ndir, err);
-                            else if (INTEG & INTEG_ENV) go = mixture_step_env(A, sv.base + sv.total_bytes, rec, rng, att, beta, ndir, err);
-                            else go = mixture_step(A, rec, rng, att, beta, ndir, err);
+                            if (INTEG & INTEG_AREA) done = !mixture_step_area(A, sv.base + sv.off_area, area_env, rec, rng, att, beta, nd, err);
+                            else if (INTEG & INTEG_ENV) done = !mixture_step_env(A, sv.base + sv.total_bytes, rec, rng, att, beta, nd, err);
+                            else done = !mixture_step(A, rec, rng, att, beta, nd, err);
                         } else {
                             beta = elemul(beta, att);
+                            done = false;
                         }
-                        if (go) {
+                        if (!SEG_IN_PLACE && !done) {
                             o = rec.p;
                             d = ndir;
-                            done = false;
                         }
                     }
                 } else if ((INTEG & INTEG_BG) && h.node < 0 && (!(INTEG & INTEG_AREA) || sv.off_bg != 0u)) {  // a miss sees the background: L += beta (x) B(d), then the path ends

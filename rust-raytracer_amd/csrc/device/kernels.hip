@@ -54,15 +54,17 @@ namespace rtamd {
     } while (0)
 
 // ---- phase statistics (tools-only build: tools/build_variant.sh phase -DRTAMD_PHASE_STATS; the product carries none of it) ----
-// Per workgroup in LDS, flushed to g_phase at the end of pt_kernel: [0..15] wave clocks (s_memtime) spent in a phase, [16..31] how
-// often a WAVE executed the phase's block, [32..47] how many LANES took part.  A phase is timed by its own clock pair, read by the
-// lanes that execute it (the clock is scalar: one value per wave), and booked by the first active lane.
+// Per workgroup in LDS, flushed to g_phase at the end of pt_kernel, PH_N rows of three: [0..PH_N) wave clocks (s_memtime) spent in a
+// phase, [PH_N..2 PH_N) how often a WAVE executed the phase's block, [2 PH_N..3 PH_N) how many LANES took part.  A phase is timed
+// by its own clock pair, read by the lanes that execute it (the clock is scalar: one value per wave), and booked by the first active lane.
 // phases: 0 regeneration, 1 traverse (all of it), 2 materialize, 3 shade (all of it), 4 Lambertian / DiffuseLight branch, 5 Isotropic,
 // 6 Metal, 7 Dielectric, 8 what follows traverse in a segment (materialize + shade + radiance + mixture / store), 9 leaf sections of
-// the traversal; events only: 10 inner-node steps, 11 leaf items, 12 cube tests, 13 segments (alive lanes), 14 mixture step, 15 inner-node steps inside an instance
+// the traversal; events only: 10 inner-node steps, 11 leaf items, 12 cube tests, 13 segments (alive lanes), 14 mixture step, 15 inner-node steps inside an instance,
+// 16 executions of the regeneration block (lanes: those that take a path)
 #ifdef RTAMD_PHASE_STATS
-__shared__ unsigned long long s_ph[48];
-__device__ unsigned long long g_phase[48];
+#define PH_N 17
+__shared__ unsigned long long s_ph[3 * PH_N];
+__device__ unsigned long long g_phase[3 * PH_N];
 __device__ __forceinline__ bool ph_first() { return (int)(__ffsll((long long)__ballot(1)) - 1) == (int)(threadIdx.x & 63); }
 #define PH_CLK() __builtin_amdgcn_s_memtime()
 #define PH_ADD(i, dt)                                                         \
@@ -73,8 +75,8 @@ __device__ __forceinline__ bool ph_first() { return (int)(__ffsll((long long)__b
     do {                                                                      \
         const unsigned long long _m = __ballot(1);                            \
         if (ph_first()) {                                                     \
-            atomicAdd(&s_ph[16 + (i)], 1ull);                                 \
-            atomicAdd(&s_ph[32 + (i)], (unsigned long long)__popcll(_m));     \
+            atomicAdd(&s_ph[PH_N + (i)], 1ull);                                \
+            atomicAdd(&s_ph[2 * PH_N + (i)], (unsigned long long)__popcll(_m));    \
         }                                                                     \
     } while (0)
 #define PH_BEGIN(v) const unsigned long long v = PH_CLK()
@@ -1864,6 +1866,15 @@ DEV bool mixture_step_area(const Acc& A, const char* area, const char* env, cons
 // with the smallest index is at the head of its wave's ring and its predecessor is folded.
 // Accumulator and ticket cross waves on different XCDs (L2s are not coherent): both are accessed ONLY with 8-/4-byte agent-scope
 // atomics (served at the memory side), the folding wave drains its stores (s_waitcnt vmcnt(0)) before it advances the ticket.
+//
+// Where the camera rays come from.  A lane whose path ended takes the pool's next (pixel, sample) once REGEN_MIN lanes are free.  The
+// general variants build that path's camera ray in the lane itself: seed_stream, the jitter, the lens sample's rejection loop and two
+// f64 divisions, some 300 VALU for the whole wave however few lanes run them (on the headline scene 19 lanes per execution, an execution
+// every second iteration).  The sphere-only LDS variants (CAM_BATCH in pt_kernel) run that code for 64 lanes at a time instead: the
+// paths k = 64 b + l of a unit are pixel l of the tile at sample index s0 + b, so when `next` reaches 64 b the whole wave generates
+// batch b into its 4 KB of global memory (BATCH_DOUBLES) and the free lanes pick up origin, direction and the stream's state after the
+// camera draws.  The stream is keyed by (seed, pixel, sample) and every lane's operations and their order are the ones above, so a
+// path starts from the same bits whichever lane generated its ray.
 #ifndef REGEN_MIN
 #define REGEN_MIN 8
 #endif
@@ -1891,6 +1902,10 @@ static const int UNIT_SPP = UNIT_SPP_N;                     // sample indices pe
 #endif
 static const int UNIT_DOUBLES = UNIT_SPP * TILE_PIX * 3;    // 12 KB per unit
 static_assert(RING_UNITS * 4 <= 64, "a wave clears its ring bookkeeping with one store per lane");
+// Camera-ray batches (the CAM_BATCH variants of pt_kernel): per wave the 64 camera rays of one (tile, sample index),
+// 4 x double2 per ray, component-major -- pair c of entry l at double2 index c * 64 + l, so that a wave's store and a pick-up are
+// coalesced 16-byte accesses.  The batches of all waves lie behind the unit buffers of all waves (LaunchLayout::ring_bytes).
+static const int BATCH_DOUBLES = 4 * 2 * TILE_PIX;            // 4 KB per wave
 #ifndef SINGLE_UNITS_BELOW_WAVES
 #define SINGLE_UNITS_BELOW_WAVES 1                           // jobs of single units when the rank owns fewer tiles than the GPU has waves (render_tiles)
 #endif
@@ -2370,6 +2385,11 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
     if (GENERAL >= 2 && rk.time_slots) A.time_lds = (uint32_t)(uintptr_t)(AS_L char*)(cfg + CFG_WORDS);  // (8-aligned: every section before it is)
     __syncthreads();
     double* wring = ring + ((size_t)blockIdx.x * (PT_BLOCK / 64) + (size_t)wave) * RING_UNITS * UNIT_DOUBLES;
+    // CAM_BATCH: camera rays are generated 64 at a time by the whole wave and picked up by the lanes whose paths ended (below).  The
+    // sphere-only LDS variants -- the whole-frame kernel, its POOL twin and their background twins; the others generate per lane
+    constexpr bool CAM_BATCH = LDS && GENERAL == 0 && ACCEL == 2 && !MEDIA;
+    double2* wbatch = (double2*)(ring + (size_t)gridDim.x * (PT_BLOCK / 64) * RING_UNITS * UNIT_DOUBLES +
+                                 ((size_t)blockIdx.x * (PT_BLOCK / 64) + (size_t)wave) * BATCH_DOUBLES);
 
     // current work unit (wave-uniform); `pool` paths, of which `next` have been handed out.  A wave does not drain a unit
     // before it takes the next one: as soon as the pool is empty and a lane is free the next unit is started, so the lanes
@@ -2390,7 +2410,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
 #endif
     int fold_wait = 0;  // iterations until the head of the ring is looked at again (wave-uniform)
 #ifdef RTAMD_PHASE_STATS
-    if (threadIdx.x < 48) s_ph[threadIdx.x] = 0ull;
+    if (threadIdx.x < 3 * PH_N) s_ph[threadIdx.x] = 0ull;
     __syncthreads();
 #endif
     {
@@ -2399,7 +2419,8 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
             // ---- regeneration: dead lanes pull the next (pixel, sample) of the pool ----
             uint64_t dead = __ballot(!alive);
             // the regeneration code runs for the whole wave however few lanes need it: wait until REGEN_MIN lanes are free
-            // (measured: 1 -> 2142, 4 -> 2174, 8 -> 2228, 12 -> 2210, 16 -> 2189, 24 -> 2094 Msamples/s)
+            // (measured again with the camera-ray batches, round 15, the headline scene at 500 spp by kernel time, three renders each:
+            // 1 -> 3047, 2 -> 3056, 4 -> 3078, 8 -> 3106, 12 -> 3070 Msamples/s: the cheaper pick-up did not move the optimum)
             if ((int)__popcll(dead) < REGEN_MIN && dead != ~0ull) dead = 0ull;
             // ---- pool exhausted: fold what is complete, start the next unit (next_unit, out of line) ----
             // A complete unit at the head of the ring is folded at once, through the same call (take = false: fold only; one call
@@ -2437,35 +2458,94 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
                 }
             }
             if (dead != 0ull && next < pool) {
-                int k = next + __popcll(dead & lanemask_lt);
-                next = min(next + (int)__popcll(dead), pool);
-                if (!alive && k < pool) {
-                    int pix = k & (TILE_PIX - 1), s = s0 + (k >> 6);
-                    int x = tx * TILE_W + (pix & (TILE_W - 1)), y = ty * TILE_H + (pix >> 3);
-                    if (x < rk.width && y < rk.height) {
-                        // camera.rs:97-99 + Camera::get_ray camera.rs:57-64
-                        rng.seed_stream(rk.seed, (uint64_t)y * (uint64_t)rk.width + (uint64_t)x, (uint64_t)s);
-                        double u = ((double)x + rng.gen_f64()) / (double)(rk.width - 1);
-                        double v = ((double)y + rng.gen_f64()) / (double)(rk.height - 1);
-                        double st = 1.0 - v;
-                        D3 rd = muls(random_in_unit_disk(rng), cam.lens_radius);  // drawn even for aperture 0 (Q4)
-                        if (GENERAL >= 2 && rk.time1 > rk.time0) {  // D9: ray(origin + offset, .., random_double(time0, time1)), after the lens sample
-                            const double tm = rng.gen_range(rk.time0, rk.time1);
-                            if (A.time_lds) *(AS_L double*)(uintptr_t)(A.time_lds + 8u * threadIdx.x) = tm;
-                        } else if (GENERAL >= 2 && A.time_lds) {
-                            *(AS_L double*)(uintptr_t)(A.time_lds + 8u * threadIdx.x) = rk.time0;
+                const int k = next + __popcll(dead & lanemask_lt);
+                const int next_end = min(next + (int)__popcll(dead), pool);
+                if constexpr (CAM_BATCH) {
+                    // The pool's paths k = 64 b + l are pixel l of the tile at sample index s0 + b: batch b.  The paths are handed out in
+                    // order, so batch b is due exactly when `next` stands at 64 b; the whole wave then generates it -- lane l the ray of
+                    // pixel l, with the code and in the order the lane that took path k used to run, so stream and ray are the same
+                    // bits -- and the free lanes take their entries.  A regeneration that crosses into the next batch generates that one
+                    // too and serves the rest in a second pass (at most two: it hands out at most 64 paths).
+                    // The buffer is the wave's own: program order and a drained store count (s_waitcnt vmcnt(0): the stores have reached
+                    // the CU's L1 / L2, where this wave's loads are served) between writing and reading are all the ordering it needs; the
+                    // same wait in front of the stores keeps them behind the previous pass's pick-up loads.
+                    int b = next >> 6;
+                    bool due = (next & 63) == 0;
+#pragma nounroll
+                    for (;;) {
+                        if (due) {
+                            const int gx = tx * TILE_W + (lane & (TILE_W - 1)), gy = ty * TILE_H + (lane >> 3);
+                            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                            if (gx < rk.width && gy < rk.height) {  // (a pixel of an edge tile outside the image gets no entry)
+                                // camera.rs:97-99 + Camera::get_ray camera.rs:57-64
+                                Rng g;
+                                g.seed_stream(rk.seed, (uint64_t)gy * (uint64_t)rk.width + (uint64_t)gx, (uint64_t)(s0 + b));
+                                const double u = ((double)gx + g.gen_f64()) / (double)(rk.width - 1);
+                                const double v = ((double)gy + g.gen_f64()) / (double)(rk.height - 1);
+                                const double st = 1.0 - v;
+                                const D3 rd = muls(random_in_unit_disk(g), cam.lens_radius);  // drawn even for aperture 0 (Q4)
+                                const D3 offset = add(muls(cam.u, rd.x), muls(cam.v, rd.y));
+                                const D3 go = add(cam.origin, offset);
+                                const D3 gd = sub(sub(add(add(cam.llc, muls(cam.horizontal, u)), muls(cam.vertical, st)), cam.origin), offset);
+                                wbatch[lane] = make_double2(go.x, go.y);
+                                wbatch[TILE_PIX + lane] = make_double2(go.z, gd.x);
+                                wbatch[2 * TILE_PIX + lane] = make_double2(gd.y, gd.z);
+                                wbatch[3 * TILE_PIX + lane] = make_double2(__longlong_as_double((long long)g.s), 0.);
+                            }
+                            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                         }
-                        D3 offset = add(muls(cam.u, rd.x), muls(cam.v, rd.y));
-                        o = add(cam.origin, offset);
-                        d = sub(sub(add(add(cam.llc, muls(cam.horizontal, u)), muls(cam.vertical, st)), cam.origin), offset);
-                        beta = mk(1., 1., 1.);
-                        L = mk(0., 0., 0.);
-                        depth = rk.max_depth;
-                        pix_id = y * rk.width + x;
-                        out_slot = ((uint32_t)cur_slot * (uint32_t)UNIT_SPP + (uint32_t)(k >> 6)) * (uint32_t)TILE_PIX + (uint32_t)pix;
-                        alive = true;
-                    }  // (a pixel of an edge tile outside the image gets no path; finalize_kernel zeroes it whatever the fold adds)
+                        if (!alive && k < pool && (k >> 6) == b) {
+                            PH_EV(16);
+                            const int pix = k & (TILE_PIX - 1);
+                            const int x = tx * TILE_W + (pix & (TILE_W - 1)), y = ty * TILE_H + (pix >> 3);
+                            if (x < rk.width && y < rk.height) {
+                                const double2 e0 = wbatch[pix], e1 = wbatch[TILE_PIX + pix], e2 = wbatch[2 * TILE_PIX + pix], e3 = wbatch[3 * TILE_PIX + pix];
+                                o = mk(e0.x, e0.y, e1.x);
+                                d = mk(e1.y, e2.x, e2.y);
+                                rng.s = (uint64_t)__double_as_longlong(e3.x);
+                                beta = mk(1., 1., 1.);
+                                L = mk(0., 0., 0.);
+                                depth = rk.max_depth;
+                                pix_id = y * rk.width + x;
+                                out_slot = ((uint32_t)cur_slot * (uint32_t)UNIT_SPP + (uint32_t)b) * (uint32_t)TILE_PIX + (uint32_t)pix;
+                                alive = true;
+                            }  // (finalize_kernel zeroes a pixel outside the image whatever the fold adds)
+                        }
+                        b += 1;
+                        due = true;
+                        if ((b << 6) >= next_end) break;
+                    }
+                } else {
+                    if (!alive && k < pool) {
+                        PH_EV(16);
+                        int pix = k & (TILE_PIX - 1), s = s0 + (k >> 6);
+                        int x = tx * TILE_W + (pix & (TILE_W - 1)), y = ty * TILE_H + (pix >> 3);
+                        if (x < rk.width && y < rk.height) {
+                            // camera.rs:97-99 + Camera::get_ray camera.rs:57-64
+                            rng.seed_stream(rk.seed, (uint64_t)y * (uint64_t)rk.width + (uint64_t)x, (uint64_t)s);
+                            double u = ((double)x + rng.gen_f64()) / (double)(rk.width - 1);
+                            double v = ((double)y + rng.gen_f64()) / (double)(rk.height - 1);
+                            double st = 1.0 - v;
+                            D3 rd = muls(random_in_unit_disk(rng), cam.lens_radius);  // drawn even for aperture 0 (Q4)
+                            if (GENERAL >= 2 && rk.time1 > rk.time0) {  // D9: ray(origin + offset, .., random_double(time0, time1)), after the lens sample
+                                const double tm = rng.gen_range(rk.time0, rk.time1);
+                                if (A.time_lds) *(AS_L double*)(uintptr_t)(A.time_lds + 8u * threadIdx.x) = tm;
+                            } else if (GENERAL >= 2 && A.time_lds) {
+                                *(AS_L double*)(uintptr_t)(A.time_lds + 8u * threadIdx.x) = rk.time0;
+                            }
+                            D3 offset = add(muls(cam.u, rd.x), muls(cam.v, rd.y));
+                            o = add(cam.origin, offset);
+                            d = sub(sub(add(add(cam.llc, muls(cam.horizontal, u)), muls(cam.vertical, st)), cam.origin), offset);
+                            beta = mk(1., 1., 1.);
+                            L = mk(0., 0., 0.);
+                            depth = rk.max_depth;
+                            pix_id = y * rk.width + x;
+                            out_slot = ((uint32_t)cur_slot * (uint32_t)UNIT_SPP + (uint32_t)(k >> 6)) * (uint32_t)TILE_PIX + (uint32_t)pix;
+                            alive = true;
+                        }  // (a pixel of an edge tile outside the image gets no path; finalize_kernel zeroes it whatever the fold adds)
+                    }
                 }
+                next = next_end;
             }
             PH_END(0, ph_it0);
             // (no lane alive and work left: the segment below is skipped as a whole.  Not a `continue` of its own: a second way back to the
@@ -2551,7 +2631,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
     }
 #ifdef RTAMD_PHASE_STATS
     __syncthreads();
-    if (threadIdx.x < 48) atomicAdd(&g_phase[threadIdx.x], s_ph[threadIdx.x]);
+    if (threadIdx.x < 3 * PH_N) atomicAdd(&g_phase[threadIdx.x], s_ph[threadIdx.x]);
 #endif
 #ifdef RT_TAIL_STATS
     if (lane == 0) {
@@ -4462,8 +4542,10 @@ static LaunchLayout launch_layout(const FlatView& view, const RenderPlan& plan, 
     // passes, resumable ranges and the ranks of rt_render_multi all launch from here, with the camera of their frame.
     L.node_shrink = (RT_TIGHTEN_BOXES && kernel == 2 && c.lds) ? box_shrink(view.origin_limit2, render_origin_bound(view.origin_limit2, c.cam_abs), view.n_inst2 == 0u) : 0.f;
     L.n_pix = plan.tiles_owned * TILE_PIX;
-    // workspace: RING_UNITS unit buffers (12 KB) per resident wave -- independent of the image -- plus accumulator and tickets
+    // workspace: RING_UNITS unit buffers (12 KB) per resident wave -- independent of the image -- plus accumulator and tickets; behind
+    // the unit buffers of all waves one camera-ray batch (4 KB) per wave, for the pt_kernel variants that generate in batches
     L.ring_bytes = (size_t)grid * (PT_BLOCK / 64) * RING_UNITS * UNIT_DOUBLES * sizeof(double);
+    if (kernel == 2 && c.lds && pt_key(c, integ, false).general == 0 && !v.media) L.ring_bytes += (size_t)grid * (PT_BLOCK / 64) * BATCH_DOUBLES * sizeof(double);
     L.accum_bytes = std::max<size_t>(16, (size_t)L.n_pix * 3 * sizeof(double));
     L.ticket_bytes = std::max<size_t>(16, (size_t)plan.tiles_owned * sizeof(unsigned int));
     L.coop_bytes = (kernel == 5) ? (size_t)grid * COOP_POOL * COOP_REC * sizeof(uint64_t) : 0;
@@ -4520,23 +4602,23 @@ static void print_tool_stats(int kernel, bool lds, int grid, const rt_stats* st,
 #endif
 #ifdef RTAMD_PHASE_STATS
     if (kernel != 5) {
-        unsigned long long hp[48], z[48] = {0};
+        unsigned long long hp[3 * PH_N], z[3 * PH_N] = {0};
         HIP_CHECK(hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_phase), sizeof(hp)));
         HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_phase), z, sizeof(z)));
+        const unsigned long long *hw = hp + PH_N, *hl = hp + 2 * PH_N;  // wave executions, lanes
         const double tot = (double)(hp[0] + hp[1] + hp[8]);
-        const char* nm[16] = {"regeneration", "traverse (all)", "materialize", "shade (all)", "  Lambertian / light branch", "  Isotropic branch", "  Metal branch",
-                              "  Dielectric branch", "after traverse (all)", "  leaf sections of traverse", "inner-node steps", "leaf items", "cube tests",
-                              "segments", "mixture steps", "  node steps inside an instance"};
-        fprintf(stderr, "[phase] kernel %d lds %d  wave clocks per segment-iteration %.0f (iterations %llu)\n", kernel, lds ? 1 : 0, hp[16] ? tot / (double)hp[16] : 0.,
-                hp[16]);
-        for (int i = 0; i < 16; i++)
+        const char* nm[PH_N] = {"regeneration", "traverse (all)", "materialize", "shade (all)", "  Lambertian / light branch", "  Isotropic branch", "  Metal branch",
+                                "  Dielectric branch", "after traverse (all)", "  leaf sections of traverse", "inner-node steps", "leaf items", "cube tests",
+                                "segments", "mixture steps", "  node steps inside an instance", "regeneration block (paths taken)"};
+        fprintf(stderr, "[phase] kernel %d lds %d  wave clocks per segment-iteration %.0f (iterations %llu)\n", kernel, lds ? 1 : 0, hw[0] ? tot / (double)hw[0] : 0.,
+                hw[0]);
+        for (int i = 0; i < PH_N; i++)
             fprintf(stderr, "[phase] %-30s time %6.3f  wave-exec/iter %8.3f  lanes/exec %5.1f  (util %.3f)\n", nm[i], i < 10 ? (double)hp[i] / tot : 0.,
-                    hp[16] ? (double)hp[16 + i] / (double)hp[16] : 0., hp[16 + i] ? (double)hp[32 + i] / (double)hp[16 + i] : 0.,
-                    hp[16 + i] ? (double)hp[32 + i] / (64. * (double)hp[16 + i]) : 0.);
+                    hw[0] ? (double)hw[i] / (double)hw[0] : 0., hw[i] ? (double)hl[i] / (double)hw[i] : 0., hw[i] ? (double)hl[i] / (64. * (double)hw[i]) : 0.);
         // what material-pure waves could return at most: every branch at full lanes instead of its measured share
         double save = 0.;
         for (int i = 4; i <= 7; i++)
-            if (hp[16 + i]) save += (double)hp[i] * (1. - (double)hp[32 + i] / (64. * (double)hp[16 + i]));
+            if (hw[i]) save += (double)hp[i] * (1. - (double)hl[i] / (64. * (double)hw[i]));
         fprintf(stderr, "[phase] material branches: %.4f of wave time; re-binned to full waves they would return at most %.4f\n",
                 (double)(hp[4] + hp[5] + hp[6] + hp[7]) / tot, save / tot);
     }

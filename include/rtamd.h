@@ -697,7 +697,7 @@ int rt_debug_rng_host(uint64_t seed, uint64_t pixel, uint64_t sample, int n, uin
  * out_range[i] = the i-th gen_range(lo..hi) of another fresh stream of the same key; on_device != 0 computes them in a kernel */
 int rt_debug_rng_floats(uint64_t seed, uint64_t pixel, uint64_t sample, int n, double lo, double hi, int on_device, double* out_gen,
                         double* out_range);
-/* device f64 sqrt / divide / rtamd-ln-1 / rtamd-sin-1, element-wise: op 0 = sqrt(a), 1 = a/b, 2 = det_ln(a), 3 = det_sin(a) */
+/* device f64 sqrt / divide / rtamd-ln-1 / rtamd-sin-1, element-wise: op 0 = sqrt(a), 1 = a/b, 2 = det_ln(a), 3 = det_sin(a), 4 = sqrt_hot(a) (the item step's sqrt, 64 consecutive elements a wave; op 0's bits) */
 int rt_debug_math_device(int op, size_t n, const double* a_host, const double* b_host, double* out_host);
 /* closest hit of explicit world-space rays through device traversal `kernel` (1, 2, or 3 = kernel 2's LDS node table "NodeW" with
  * its own box test, which pt_kernel uses when the scene is LDS-resident; 5 / 6 = the walks of the instance service in one lane: the

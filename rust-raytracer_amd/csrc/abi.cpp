@@ -1044,7 +1044,7 @@ int rt_debug_rng_floats(uint64_t seed, uint64_t pixel, uint64_t sample, int n, d
 }
 int rt_debug_math_device(int op, size_t n, const double* a_host, const double* b_host, double* out_host) {
     return guard([&] {
-        REQUIRE(n > 0 && a_host && out_host && (op == 0 || op == 2 || op == 3 || (op == 1 && b_host)), "bad argument");
+        REQUIRE(n > 0 && a_host && out_host && (op == 0 || op == 2 || op == 3 || op == 4 || (op == 1 && b_host)), "bad argument");
         if (device_count() < 1) throw RtError(RT_ERR_NO_DEVICE, "no HIP device");
         debug_math_device(op, n, a_host, b_host, out_host);
         return (int)RT_OK;

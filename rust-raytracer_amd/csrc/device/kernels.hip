@@ -172,6 +172,8 @@ DEV D3 xf_dir(const double* t, D3 p) {  // vec3.rs:180-184 (w = 0)
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));  // (uint2 / double2 read through an LDS-qualified pointer: the HIP vector
+typedef double f64x2 __attribute__((ext_vector_type(2)));        // structs' copy constructors take generic references only)
 struct Acc {  // typed views into the blob (LDS or global; the address space is inferred per instantiation)
     const uint2* meta;
     const double2* boxes;    // 3 x double2 per box: (minx,miny) (minz,maxx) (maxy,maxz)
@@ -212,6 +214,8 @@ struct Acc {  // typed views into the blob (LDS or global; the address space is 
     const uint4* tri32;      // 3 x uint4 per Tri32
     const double* qgrid;     // 8 per instance
 };
+// the LDS byte address of a table that the instantiation holds in LDS (the ITEMA walks: the staged items and spheres)
+DEV uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)(const AS_L char*)(const char*)p; }
 template <class P>
 DEV Acc make_acc(P hot, const char* gbase, const FlatView& v) {  // hot: LDS copy or the global blob; cold part always global
     Acc a;
@@ -303,6 +307,25 @@ DEV bool aabb_hit(const double2* b, D3 o, D3 inv, double t_min, double t_max) {
     }
     return !(mx <= mn);
 }
+// sqrt for the hot item step (part C).  The compiler expands an f64 sqrt into v_rsq_f64, nine multiplies / fmas and eight
+// instructions that only matter at the ends of the range: the operand is scaled by 2^256 when it is below 2^-767 and the result by
+// 2^-128 (a compare, two selects, two v_ldexp_f64 -- by 0 for every ordinary operand), and +-0 / +inf are passed through (v_cmp_class,
+// two selects).  When NO active lane of the wave holds an operand outside [2^-767, +inf) -- negative, NaN, +inf, zero, denormal or
+// tiny: one ballot of a test of the high word -- those eight are the identity, and the core alone, the compiler's own sequence
+// operation for operation, gives the same bits.  Otherwise the whole wave takes sqrt().
+DEV double sqrt_hot(double x) {
+    const uint32_t hi = (uint32_t)((uint64_t)__double_as_longlong(x) >> 32);
+    // [2^-767, +inf) as high words: [0x10000000, 0x7FF00000); a sign bit, a NaN, +inf and everything below 2^-767 fall outside
+    if (__ballot(hi - 0x10000000u >= 0x7FF00000u - 0x10000000u) != 0ull) return sqrt(x);
+    const double y = __builtin_amdgcn_rsq(x);
+    double g = x * y, h = y * 0.5;
+    const double r = __builtin_fma(-h, g, 0.5);
+    g = __builtin_fma(g, r, g);
+    h = __builtin_fma(h, r, h);
+    g = __builtin_fma(__builtin_fma(-g, g, x), h, g);
+    g = __builtin_fma(__builtin_fma(-g, g, x), h, g);
+    return g;
+}
 // Sphere::hit's root selection, sphere.rs:24-43 ; a = |dir|^2 hoisted per ray
 // RT_SPHERE_F32_REJECT (A/B switch, off; round 5's experiment for the headline scene): the sign of the discriminant decided in f32 where it is
 // certain.  oc comes from the f64 subtraction the reference makes anyway; with oc32, d32 = its and the direction's f32 roundings (relative
@@ -314,8 +337,13 @@ DEV bool aabb_hit(const double2* b, D3 o, D3 inv, double t_min, double t_max) {
 #ifndef RT_SPHERE_F32_REJECT
 #define RT_SPHERE_F32_REJECT 0
 #endif
-DEV bool sphere_hit(const double2* s, D3 o, D3 d, double a, double t_min, double t_max, double& t_out) {
-    double2 c0 = s[0], c1 = s[1];
+// sphere_root: the one place that holds the selection.  An admissible root goes to `accept` where it is found, so a caller whose use of
+// it is written there (the ITEMA item step) joins it with nothing; sphere_hit is the form that hands it back.
+// SP: const double2*, or const AS_L f64x2* where the caller holds the row's LDS address.
+// HOT: the square root through sqrt_hot (the ITEMA item step).
+template <bool HOT = false, class SP, class F>
+DEV bool sphere_root(SP s, D3 o, D3 d, double a, double t_min, double t_max, F&& accept) {
+    const auto c0 = s[0], c1 = s[1];
     D3 oc = mk(o.x - c0.x, o.y - c0.y, o.z - c1.x);
     double radius = c1.y;
     if (RT_SPHERE_F32_REJECT) {
@@ -332,12 +360,15 @@ DEV bool sphere_hit(const double2* s, D3 o, D3 d, double a, double t_min, double
     double c = sqlen(oc) - radius * radius;
     double disc = half_b * half_b - a * c;
     if (disc < 0.) return false;
-    double sq = sqrt(disc);
+    double sq = HOT ? sqrt_hot(disc) : sqrt(disc);
     double root = (-half_b - sq) / a;
     if (!(root >= t_min && root <= t_max)) root = (-half_b + sq) / a;
     if (!(root >= t_min && root <= t_max)) return false;
-    t_out = root;
+    accept(root);
     return true;
+}
+DEV bool sphere_hit(const double2* s, D3 o, D3 d, double a, double t_min, double t_max, double& t_out) {
+    return sphere_root(s, o, d, a, t_min, t_max, [&](double root) __attribute__((always_inline)) { t_out = root; });
 }
 // XY/XZ/YZRectangle::hit, rectangle.rs:15-34,53-72,90-109 (axis = constant axis).
 // No zero-direction guard: NaN/inf t falls through the rejects exactly as in the reference.
@@ -966,8 +997,40 @@ DEV double track_bound(const MediaTrack& K, double best) {
 // walking, the others re-enter with cur and their stack untouched; two ballots' bit counts and a scalar compare per node step -- and
 // rejected it: headline 2 564-2 566 Msamples/s against the parent's 2 877-2 879, -10.9 %, where tools/walk_model.cpp had priced the
 // saved wave-steps at +1..2 %.  DESIGN.md s5-r7, profiles/r07/README.md.  It is not in the tree.)
+// The item step of an ITEMA walk (traverse2, below): the leaf's `cnt` >= 1 items from LDS address `ia`, each {LDS address of the
+// sphere's row, reference-order index}.  One way back to the loop's head, and nothing that a path through the body leaves unwritten
+// (DESIGN.md s5-r13 / r14): the root is used where sphere_root found it, the items run from an address to its end.
+#ifndef ITEM_SQRT_HOT
+#define ITEM_SQRT_HOT true  // (A/B builds: -DITEM_SQRT_HOT=false leaves the item step the compiler's sqrt)
+#endif
+DEV void leaf_items_addr(uint32_t ia, uint32_t cnt, D3 o, D3 d, double a, double t_min, Hit& h, Ray32& r) {
+    const uint32_t ie = ia + 8u * cnt;
+    do {
+        PH_EV(11);
+        const u32x2 it = *(const AS_L u32x2*)(uintptr_t)ia;
+        ia += 8u;
+        // (no instruction: left to itself the compiler counts the items down beside the address, a third instruction per step)
+        asm("" : "+v"(ia));
+        sphere_root<ITEM_SQRT_HOT>((const AS_L f64x2*)(uintptr_t)it.x, o, d, a, t_min, h.t, [&](double t) __attribute__((always_inline)) {
+            // candidates satisfy t <= h.t; an exact tie goes to the later one in reference order (the rule of traverse2's general step)
+            // (three compares and two scalar ORs: with `||` the compiler branches around the second and third)
+            if ((t < h.t) | ((int)it.y > h.node) | !(t == t)) {
+                h.t = t;
+                h.node = (int)it.y;
+                h.kp = it.x;
+                r.best = ray32_best(t);
+            }
+        });
+    } while (ia != ie);
+}
+// ITEMA (pt_kernel's sphere-only LDS variants; with WIDE and GENERAL == 0 only): the staged item table's first words
+// are not `kind | payload << 4` but the LDS byte address of the item's 32-byte sphere row (pt_kernel's staging rewrites them in the LDS copy; the
+// blob keeps its words, and so does every other kernel).  The item step then reads the sphere through that word as it comes, has no
+// kind test (the host picks these variants for blobs that hold spheres alone: scene_variant), runs its items from an address to an
+// end address, and joins nothing with the root: it is used where sphere_root accepted it.  Hit::kp of such a walk is that address;
+// materialize<0, .., true> reads the row through it and takes the sphere's index from its distance to the table.
 template <int GENERAL, bool DEFER = false, bool TOP = true, bool WIDE = false, class PEND = uint32_t, bool LIMIT = false, bool ENTER = !DEFER, bool TRACK = false, bool RESOLVE = true,
-          bool TIEDEF = false>
+          bool TIEDEF = false, bool ITEMA = false>
 DEV Hit traverse2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, double t_min, double t_max, PEND* pend = nullptr, uint32_t order_limit = 0xFFFFFFFFu,
                   MediaTrack* track = nullptr) {
     D3 o = wo, d = wd;
@@ -1085,7 +1148,9 @@ DEV Hit traverse2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, d
         } else if ((cur >> REF_TAG_SHIFT) == 1u) {  // leaf: test its items with the reference's f64 routines
             uint32_t first = cur & REF_LEAF_FIRST_MASK, cnt = ((cur >> REF_LEAF_COUNT_SHIFT) & 7u) + 1u;
             uint32_t enter = REF_DONE;
-            for (uint32_t i = 0; i < cnt; i++) {
+            static_assert(!ITEMA || (WIDE && GENERAL == 0 && !DEFER && !LIMIT && !TRACK), "ITEMA: the sphere-only LDS walk");
+            if constexpr (ITEMA) leaf_items_addr(lds_addr(A.items2) + 8u * first, cnt, o, d, a, t_min, h, r);
+            for (uint32_t i = 0; !ITEMA && i < cnt; i++) {
                 PH_EV(11);
                 uint2 it = A.items2[first + i];
                 uint32_t kind = it.x & NK_MASK, pl = it.x >> NK_BITS;
@@ -1499,10 +1564,11 @@ __device__ __attribute__((noinline)) double env_pdf(const char* tab, D3 d, int* 
 }
 // Build the HitRecord of the winning leaf only (the reference builds one per candidate).  uv is computed only where an ImageTexture
 // reads it, unless ALL_UV (the closest-hit diagnostic, which returns the whole record).
-template <int GENERAL, bool ALL_UV = false>
+// ITEMA: the hit comes from an ITEMA walk (traverse2): h.kp is the LDS address of the winning sphere's row.
+template <int GENERAL, bool ALL_UV = false, bool ITEMA = false>
 DEV Rec materialize(const Acc& A, const Hit& h, D3 wo, D3 wd, int* err) {
     Rec rec;
-    uint32_t kind = h.kp & NK_MASK, pl = h.kp >> NK_BITS;
+    uint32_t kind = h.kp & NK_MASK, pl = ITEMA ? (h.kp - lds_addr(A.spheres)) >> 5 : h.kp >> NK_BITS;
     D3 o = wo, d = wd;
     if (GENERAL == 3 && h.xf >= 0) {
         chain_ray(A, (uint32_t)h.xf, CHAIN_ALL, o, d);  // the innermost level's object-space ray
@@ -1518,7 +1584,17 @@ DEV Rec materialize(const Acc& A, const Hit& h, D3 wo, D3 wd, int* err) {
     // (GENERAL == 0: the host picks the sphere-only variants for blobs that hold nothing else (scene_variant), and their walks accept no
     // other kind; without the test the record's zero initialisation for "some other kind" leaves the hot loop -- DESIGN.md s5-r14)
     if (GENERAL == 0 || kind == NK_SPHERE) {  // sphere.rs:45-53
-        double2 c0 = A.spheres[2 * pl], c1 = A.spheres[2 * pl + 1];
+        double2 c0, c1;
+        if constexpr (ITEMA) {
+            static_assert(!ITEMA || GENERAL == 0, "ITEMA: the sphere-only LDS walk");
+            const AS_L f64x2* s = (const AS_L f64x2*)(uintptr_t)h.kp;
+            const f64x2 s0 = s[0], s1 = s[1];
+            c0 = make_double2(s0.x, s0.y);
+            c1 = make_double2(s1.x, s1.y);
+        } else {
+            c0 = A.spheres[2 * pl];
+            c1 = A.spheres[2 * pl + 1];
+        }
         rec.mat = A.sphere_mat[pl];
         D3 p = add(o, muls(d, h.t));
         outward = divs(sub(p, mk(c0.x, c0.y, c1.x)), c1.y);
@@ -2316,11 +2392,30 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
     const uint32_t st_end = (ACCEL == 2) ? sv.stage2_end : sv.stage_bytes;
     uint32_t staged = 0;  // bytes of LDS in front of the stacks
     Acc A;
+    // ITEMA: the staged items hold their spheres' LDS addresses, for the walk and for materialize (traverse2).  The
+    // sphere-only LDS variants, the family of CAM_BATCH below
+    constexpr bool ITEMA = LDS && GENERAL == 0 && ACCEL == 2 && !MEDIA;
     if (LDS && ACCEL == 2) {
         // [spheres .. n2) as it is (the Node2 array is the last staged section, flatten.cpp); the Node2 array itself is EXPANDED
         // into the NodeW form behind it
         const uint32_t lo_bytes = sv.off_n2 - st_begin;
-        {
+        if constexpr (ITEMA) {
+            // ... and of the item section [items2, inst2) every item's first word, `NK_SPHERE | index << 4`, becomes the LDS address of
+            // that sphere's 32-byte row (two items per 16 bytes; the section's padding is never read).  In the LDS copy only, as
+            // stage_nodew rewrites the nodes: the blob keeps its words
+            const uint32_t sph_lds = lds_addr(smem) + (sv.off_spheres - st_begin);
+            const uint32_t it0 = (sv.off_items2 - st_begin) / 16, it1 = (sv.off_inst2 - st_begin) / 16;
+            const uint4* src = (const uint4*)(sv.base + st_begin);
+            uint4* dst = (uint4*)smem;
+            for (uint32_t i = threadIdx.x; i < lo_bytes / 16; i += blockDim.x) {
+                uint4 w = src[i];
+                if (i >= it0 && i < it1) {
+                    w.x = sph_lds + ((w.x >> NK_BITS) << 5);
+                    w.z = sph_lds + ((w.z >> NK_BITS) << 5);
+                }
+                dst[i] = w;
+            }
+        } else {
             const uint4* src = (const uint4*)(sv.base + st_begin);
             uint4* dst = (uint4*)smem;
             for (uint32_t i = threadIdx.x; i < lo_bytes / 16; i += blockDim.x) dst[i] = src[i];
@@ -2557,7 +2652,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
                 PH_EV(13);
                 PH_BEGIN(ph_t0);
                 Hit h = (ACCEL == 2) ? (MEDIA ? traverse2_media<GENERAL, !LDS, LDS>(A, sv.n_media, stk, stk_stride, o, d, rk.t_min, rng)
-                                              : traverse2<GENERAL, false, !LDS, LDS>(A, stk, stk_stride, o, d, rk.t_min, INFINITY))
+                                              : traverse2<GENERAL, false, !LDS, LDS, uint32_t, false, true, false, true, false, ITEMA>(A, stk, stk_stride, o, d, rk.t_min, INFINITY))
                                      : traverse<GENERAL, MEDIA>(A, o, d, rk.t_min, INFINITY, &rng);
                 PH_END(1, ph_t0);
                 PH_BEGIN(ph_p0);
@@ -2565,7 +2660,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
                 if (h.node >= 0 && depth > 0) {  // Q12: depth test after the hit, before emission
                     depth -= 1;
                     PH_BEGIN(ph_m0);
-                    const Rec rec = materialize<GENERAL>(A, h, o, d, err);
+                    const Rec rec = materialize<GENERAL, false, ITEMA>(A, h, o, d, err);
                     PH_END(2, ph_m0);
                     // The next segment's ray is written where it is computed: the hit point IS the next origin (no path
                     // that goes on reads the old one again), and shade() writes the scattered direction into `d` itself, after its one
@@ -3781,7 +3876,7 @@ __global__ void rng_floats_kernel(uint64_t seed, uint64_t pixel, uint64_t sample
 __global__ void math_kernel(int op, size_t n, const double* a, const double* b, double* out) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    out[i] = (op == 0) ? sqrt(a[i]) : (op == 2) ? det_ln(a[i]) : (op == 3) ? det_sin(a[i]) : a[i] / b[i];
+    out[i] = (op == 0) ? sqrt(a[i]) : (op == 2) ? det_ln(a[i]) : (op == 3) ? det_sin(a[i]) : (op == 4) ? sqrt_hot(a[i]) : a[i] / b[i];
 }
 // one row of rt_debug_hit_device's output: {hit, t, p, normal, front_face, u, v, node}
 DEV void hit_row(double* q, const Hit& h, const Rec& rec) {

@@ -870,7 +870,7 @@ static int ao_render_entry(const rt_scene* s, const rt_camera* cam, const rt_par
         for (int32_t r : cfg->reserved) REQUIRE(r == 0, "rt_ao_config.reserved must be 0");
         REQUIRE(p->kernel >= 0 && p->kernel <= 2, "rt_ao_render walks with kernel 0 (auto), 1 or 2");
         const CameraDev cd = make_camera(*cam);
-        ao_choose_walk(*s, cd, p->t_min, p->kernel);  // (the refusals; the launch picks the walk again with its device's LDS)
+        choose_pixel_walk(*s, cd, p->t_min, p->kernel, AO_LDS_MAX);  // (the refusals; the launch picks the walk again with its device's LDS)
         require_device(render_ao != nullptr && render_ao_device != nullptr);
         const CallClock clock;
         DeviceScope dev_scope(p->device);
@@ -1182,7 +1182,7 @@ int rt_debug_occluded_device(const rt_scene* s, int device, int kernel, size_t n
         REQUIRE(n > 0 && rays_host && out_host, "bad argument");
         REQUIRE(kernel == 1 || kernel == 2, "rt_debug_occluded_device: kernel 1 or 2");
         aov_refuse(*s);
-        if (kernel == 2 && !ao_accel_usable(s->flat.view, 0., t_min))
+        if (kernel == 2 && !accel2_usable(s->flat.view, 0., t_min, 64, AO_LDS_MAX))
             throw RtError(RT_ERR_UNSUPPORTED, "kernel 2 needs an accel, t_min >= 0 (box32) and walk stacks that fit in LDS");
     }, [&] { debug_occluded_device(*s, kernel, n, rays_host, t_min, out_host); });
 }

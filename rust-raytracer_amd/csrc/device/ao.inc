@@ -266,56 +266,21 @@ __global__ void __launch_bounds__(64) occluded_kernel(FlatView sv, size_t n, con
     out[i] = ray_occluded<ACCEL, GENERAL>(A, stk, (int)blockDim.x, o, d, t_min, rays[7 * i + 6]) ? 1. : 0.;
 }
 
-// the stacks of a 64-lane workgroup (walk 2; the caller has checked that they fit)
-static size_t ao_stack_bytes(const FlatView& view, int walk, const void* fn) {
-    if (walk != 2) return 0;
-    const size_t smem = walk_stack_bytes(view.stack2, 64);
-    if (smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    return smem;
-}
-
 void render_ao_device(const rt_scene& s, const CameraDev& cam, int width, int height, uint64_t seed, double t_min, int kernel, const rt_ao_config& cfg,
                       double* d_out, void* stream_, rt_stats* st) {
     hipStream_t stream = (hipStream_t)stream_;
     int dev = 0;
     HIP_CHECK(hipGetDevice(&dev));
-    const int walk = ao_choose_walk(s, cam, t_min, kernel, dev_info(dev).lds_max);
-    FlatView view = s.flat.view;
+    const int walk = choose_pixel_walk(s, cam, t_min, kernel, dev_info(dev).lds_max);  // (before the upload: a refused call touches no device)
     double upload_ms = 0.;
-    view.base = device_blob(s, dev, &upload_ms);
-    const bool nest = s.flat.xf_nest != 0u;  // nested Transforms: the chain walk (GENERAL == 3)
+    const FlatView view = device_view(s, &upload_ms).view;
     typedef void (*ao_fn)(FlatView, CamK, int, int, uint64_t, double, int, int, double, double*, int*);
-    const ao_fn fn = (walk == 2) ? (nest ? ao_kernel<true, 3> : ao_kernel<true, 1>) : (nest ? ao_kernel<false, 3> : ao_kernel<false, 1>);
-    const size_t smem = ao_stack_bytes(view, walk, (const void*)fn);
-    const size_t npix = (size_t)width * (size_t)height;
-    DevBuf err;
-    err.alloc(4);
-    HIP_CHECK(hipMemsetAsync(err.p, 0, 4, stream));
-    Events events;
-    hipEvent_t e0 = events.make(), e1 = events.make();
-    const unsigned blocks = (unsigned)((npix + 63) / 64);
-    HIP_CHECK(hipEventRecord(e0, stream));
-    hipLaunchKernelGGL(fn, dim3(blocks), dim3(64), smem, stream, view, to_camk(cam), width, height, seed, t_min, (int)cfg.ao_spp, (int)cfg.rays_per_hit,
-                       cfg.max_distance, d_out, (int*)err.p);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(e1, stream));
-    HIP_CHECK(hipEventSynchronize(e1));
-    int h_err = 0;
-    HIP_CHECK(hipMemcpy(&h_err, err.p, 4, hipMemcpyDeviceToHost));
-    if (h_err & 1) throw RtError(RT_ERR_UNIT_ZERO, "unitizing zero vector (device, rt_ao_render)");
-    if (h_err & ~1) throw RtError(RT_ERR_INTERNAL, "device invariant failed in rt_ao_render (error bits " + std::to_string(h_err) + ")");
-    if (st) {
-        float ms = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        st->kernel_ms = ms;
-        st->upload_ms = upload_ms;
-        st->samples = (uint64_t)npix * (uint64_t)cfg.ao_spp;
-        st->launches = 1;
-        st->kernel_used = walk;
-        st->block_threads = 64;
-        st->grid_blocks = (int32_t)blocks;
-        st->scene_bytes = s.flat.info.bytes;
-    }
+    const ao_fn fn = WALK_PASS_KERNEL(ao_kernel, walk == 2, s.flat.xf_nest != 0u);
+    const size_t smem = walk_pass_lds(view, walk, (const void*)fn);
+    run_pixel_pass(s, "rt_ao_render", width, height, (int)cfg.ao_spp, walk, upload_ms, stream, st, [&](unsigned blocks, int* err) {
+        hipLaunchKernelGGL(fn, dim3(blocks), dim3(64), smem, stream, view, to_camk(cam), width, height, seed, t_min, (int)cfg.ao_spp, (int)cfg.rays_per_hit,
+                           cfg.max_distance, d_out, err);
+    });
 }
 
 void render_ao(const rt_scene& s, const CameraDev& cam, int width, int height, uint64_t seed, double t_min, int kernel, const rt_ao_config& cfg,
@@ -324,27 +289,23 @@ void render_ao(const rt_scene& s, const CameraDev& cam, int width, int height, u
     DevBuf dout;
     dout.alloc(npix * 8 * sizeof(double));
     render_ao_device(s, cam, width, height, seed, t_min, kernel, cfg, (double*)dout.p, nullptr, st);
-    HIP_CHECK(hipMemcpy(out_host, dout.p, npix * 8 * sizeof(double), hipMemcpyDeviceToHost));
+    dout.download(out_host, npix * 8 * sizeof(double));
 }
 
 void debug_occluded_device(const rt_scene& s, int walk, size_t n, const double* rays, double t_min, double* out) {
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    FlatView view = s.flat.view;
-    view.base = device_blob(s, dev);
-    const bool nest = s.flat.xf_nest != 0u;
+    const DeviceView dv = device_view(s);
+    const FlatView& view = dv.view;
     typedef void (*occ_fn)(FlatView, size_t, const double*, double, double*);
-    const occ_fn fn = (walk == 2) ? (nest ? occluded_kernel<true, 3> : occluded_kernel<true, 1>) : (nest ? occluded_kernel<false, 3> : occluded_kernel<false, 1>);
-    if (walk == 2 && !ao_accel_usable(view, 0., t_min, dev_info(dev).lds_max))
+    const occ_fn fn = WALK_PASS_KERNEL(occluded_kernel, walk == 2, s.flat.xf_nest != 0u);
+    if (walk == 2 && !accel2_usable(view, 0., t_min, 64, dv.di.lds_max))
         throw RtError(RT_ERR_UNSUPPORTED, "the walk stacks of this scene do not fit in this device's LDS; use kernel 1");
-    const size_t smem = ao_stack_bytes(view, walk, (const void*)fn);
+    const size_t smem = walk_pass_lds(view, walk, (const void*)fn);
     DevBuf dr, dout;
-    dr.alloc(n * 7 * sizeof(double));
     dout.alloc(n * sizeof(double));
-    HIP_CHECK(hipMemcpy(dr.p, rays, n * 7 * sizeof(double), hipMemcpyHostToDevice));
+    dr.upload(rays, n * 7 * sizeof(double));
     hipLaunchKernelGGL(fn, dim3((unsigned)((n + 63) / 64)), dim3(64), smem, 0, view, n, (const double*)dr.p, t_min, (double*)dout.p);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpy(out, dout.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    dout.download(out, n * sizeof(double));
 }
 
 }  // namespace rtamd

@@ -58,57 +58,18 @@ __global__ void __launch_bounds__(64) aov_kernel(FlatView sv, CamK cam, int widt
 void render_aov_device(const rt_scene& s, const CameraDev& cam, int width, int height, uint64_t seed, double t_min, int kernel, int aov_spp, double* d_out,
                        void* stream_, rt_stats* st) {
     hipStream_t stream = (hipStream_t)stream_;
-    aov_refuse(s);
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    const DevInfo& di = dev_info(dev);
-    FlatView view = s.flat.view;
+    aov_refuse(s);  // (before the upload: a refused scene touches no device)
     double upload_ms = 0.;
-    view.base = device_blob(s, dev, &upload_ms);
-    // kernel 2's walk under render_tiles' conditions: a usable accel, the camera inside the region the f32 boxes were padded for,
-    // t_min >= 0, and the per-lane stacks in LDS
-    const double cam_abs = std::fmax(std::fmax(std::fabs(cam.origin[0]), std::fabs(cam.origin[1])), std::fabs(cam.origin[2])) + std::fabs(cam.lens_radius);
-    const bool camera_ok = cam_abs <= view.origin_limit2 && std::isfinite(cam_abs) && t_min >= 0.;
-    const size_t stack_bytes = walk_stack_bytes(view.stack2, 64);
-    const bool accel_usable = view.accel_ok && camera_ok && stack_bytes <= di.lds_max;
-    if (kernel == 0) kernel = accel_usable ? 2 : 1;
-    if (kernel == 2 && !accel_usable)
-        throw RtError(RT_ERR_UNSUPPORTED, "kernel 2 requested but no usable accel for this scene/camera (unbounded item, depth overflow, stacks "
-                                          "larger than LDS, negative t_min, or camera farther than 64x the scene extent); use kernel 0/1");
-    if (kernel != 1 && kernel != 2) throw RtError(RT_ERR_ARG, "rt_render_aov walks with kernel 1 or 2");
-    const bool nest = s.flat.xf_nest != 0u;  // nested Transforms: the chain walk (GENERAL == 3)
+    const DeviceView dv = device_view(s, &upload_ms);
+    const FlatView& view = dv.view;
+    const int walk = choose_pixel_walk(s, cam, t_min, kernel, dv.di.lds_max);  // (denoise.h: rt_ao_render's chooser)
+    if (walk != 1 && walk != 2) throw RtError(RT_ERR_ARG, "rt_render_aov walks with kernel 1 or 2");
     typedef void (*aov_fn)(FlatView, CamK, int, int, uint64_t, double, int, double*, int*);
-    const aov_fn fn = (kernel == 2) ? (nest ? aov_kernel<true, 3> : aov_kernel<true, 1>) : (nest ? aov_kernel<false, 3> : aov_kernel<false, 1>);
-    const size_t smem = (kernel == 2) ? stack_bytes : 0;
-    if (smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    const size_t npix = (size_t)width * (size_t)height;
-    DevBuf err;
-    err.alloc(4);
-    HIP_CHECK(hipMemsetAsync(err.p, 0, 4, stream));
-    Events events;
-    hipEvent_t e0 = events.make(), e1 = events.make();
-    const unsigned blocks = (unsigned)((npix + 63) / 64);
-    HIP_CHECK(hipEventRecord(e0, stream));
-    hipLaunchKernelGGL(fn, dim3(blocks), dim3(64), smem, stream, view, to_camk(cam), width, height, seed, t_min, aov_spp, d_out, (int*)err.p);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(e1, stream));
-    HIP_CHECK(hipEventSynchronize(e1));
-    int h_err = 0;
-    HIP_CHECK(hipMemcpy(&h_err, err.p, 4, hipMemcpyDeviceToHost));
-    if (h_err & 1) throw RtError(RT_ERR_UNIT_ZERO, "unitizing zero vector (device, rt_render_aov)");
-    if (h_err & ~1) throw RtError(RT_ERR_INTERNAL, "device invariant failed in rt_render_aov (error bits " + std::to_string(h_err) + ")");
-    if (st) {
-        float ms = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        st->kernel_ms = ms;
-        st->upload_ms = upload_ms;
-        st->samples = (uint64_t)npix * (uint64_t)aov_spp;
-        st->launches = 1;
-        st->kernel_used = kernel;
-        st->block_threads = 64;
-        st->grid_blocks = (int32_t)blocks;
-        st->scene_bytes = s.flat.info.bytes;
-    }
+    const aov_fn fn = WALK_PASS_KERNEL(aov_kernel, walk == 2, s.flat.xf_nest != 0u);
+    const size_t smem = walk_pass_lds(view, walk, (const void*)fn);
+    run_pixel_pass(s, "rt_render_aov", width, height, aov_spp, walk, upload_ms, stream, st, [&](unsigned blocks, int* err) {
+        hipLaunchKernelGGL(fn, dim3(blocks), dim3(64), smem, stream, view, to_camk(cam), width, height, seed, t_min, aov_spp, d_out, err);
+    });
 }
 
 void render_aov(const rt_scene& s, const CameraDev& cam, int width, int height, uint64_t seed, double t_min, int kernel, int aov_spp, double* out_host,
@@ -118,7 +79,7 @@ void render_aov(const rt_scene& s, const CameraDev& cam, int width, int height, 
     DevBuf dout;
     dout.alloc(npix * 8 * sizeof(double));
     render_aov_device(s, cam, width, height, seed, t_min, kernel, aov_spp, (double*)dout.p, nullptr, st);
-    HIP_CHECK(hipMemcpy(out_host, dout.p, npix * 8 * sizeof(double), hipMemcpyDeviceToHost));
+    dout.download(out_host, npix * 8 * sizeof(double));
 }
 
 }  // namespace rtamd

@@ -19,6 +19,16 @@ inline void aov_refuse(const rt_scene& s) {
     if (s.flat.view.kinds_mask & (1u << NK_MEDIUM_BEGIN))
         throw RtError(RT_ERR_UNSUPPORTED, "rt_render_aov: the first hit in a scene with a ConstantMedium depends on the path's random stream (no guides through media)");
 }
+// The one place that picks the walk of the one-launch pixel passes (rt_render_aov, rt_ao_render; 64-lane workgroups).  kernel: 0
+// (automatic), 1 or 2; any other value is handed back for the caller to refuse.  Refuses rt_render_aov's scenes (aov_refuse) and kernel 2
+// without a usable accel (device.h: accel2_usable); kernel 0 becomes 2 where the accel is usable, else 1.  abi.cpp calls it with
+// AO_LDS_MAX before it asks for a device, the launches again with that device's LDS.
+inline int choose_pixel_walk(const rt_scene& s, const CameraDev& cam, double t_min, int kernel, size_t lds_max) {
+    aov_refuse(s);
+    const bool usable = accel2_usable(s.flat.view, camera_reach(cam), t_min, 64, lds_max);
+    if (kernel == 2 && !usable) refuse_kernel2();
+    return kernel == 0 ? (usable ? 2 : 1) : kernel;
+}
 
 // rt_render_aov on the current device: out_host[height][width][8] (HOST).  kernel: 0 auto, 1 reference-order walk, 2 accel walk.
 __attribute__((weak)) void render_aov(const rt_scene& s, const CameraDev& cam, int width, int height, uint64_t seed, double t_min, int kernel,

@@ -1,5 +1,6 @@
 // Host-callable launch interface of the HIP kernels (device/kernels.hip).
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <vector>
 
@@ -80,13 +81,41 @@ bool debug_sppm_trace_device(const rt_scene& s, const CameraDev& cam, rt_debug_s
 // closest-hit diagnostic with a ray time and a random stream per row, on the current device (device/walk_debug.inc; the arguments, the
 // scene, the times and debug_walk_lds_bytes were checked by the caller): rays n*7, keys n*3, out n*14.  true: a unit() met a zero vector
 bool debug_walk_device(const rt_scene& s, int kernel, size_t n, const double* rays, const uint64_t* keys, double t_min, double* out);
-// dynamic LDS of debug_walk_device's launch (blocks of 64): kernel 3's NodeW table (kernels.hip: nodew_bytes), the stack columns of
-// kernels 2 / 3, and 64 ray times where the scene has moving spheres (walk_debug.inc has the map)
+// ---- what the launch drivers and abi.cpp size and decide alike ----
+// the stack columns of a workgroup's walks: the one place the launches, the kernels and abi.cpp size them from (kernels.hip "the stack
+// discipline" has the capacity proof; host and device for the HIP compiler, plain C++ elsewhere)
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+inline size_t walk_stack_bytes(uint32_t rows, uint32_t threads) { return (size_t)rows * threads * sizeof(uint32_t); }
+// kernel 2's LDS node table: chunks of NODEW_CHUNK = 129 nodes, three planes of NODEW_FAR = 4128 bytes each (kernels.hip "NodeW";
+// walk_debug.inc asserts the two numbers)
+inline size_t nodew_bytes(const FlatView& v) { return ((size_t)v.n_nodes2 + 128) / 129 * 3 * 4128; }
+
+// The one rule for "kernel 2's walk is usable" (DESIGN.md s4 "Kernel selection"): a usable accel, every ray origin inside the region the
+// f32 boxes were padded for (flatten.cpp: origin_limit2; o_abs is the largest |coordinate| of an origin), t_min >= 0 (box32's proof), and
+// the per-lane stacks of a workgroup of `lanes` threads within lds_max bytes.  abi.cpp decides with it before it touches a device, the
+// launches again with the LDS of the device at hand.
+inline bool accel2_usable(const FlatView& v, double o_abs, double t_min, uint32_t lanes, size_t lds_max) {
+    const bool origin_ok = o_abs <= v.origin_limit2 && std::isfinite(o_abs) && t_min >= 0.;
+    return v.accel_ok && origin_ok && walk_stack_bytes(v.stack2, lanes) <= lds_max;
+}
+// o_abs of a camera: the largest |coordinate| of a point on the lens (|lens offset| <= lens_radius on every axis)
+inline double camera_reach(const CameraDev& cam) {
+    return std::fmax(std::fmax(std::fabs(cam.origin[0]), std::fabs(cam.origin[1])), std::fabs(cam.origin[2])) + std::fabs(cam.lens_radius);
+}
+[[noreturn]] inline void refuse_kernel2() {
+    throw RtError(RT_ERR_UNSUPPORTED, "kernel 2 requested but no usable accel for this scene/camera (unbounded item, depth overflow, stacks "
+                                      "larger than LDS, negative t_min, or camera farther than 64x the scene extent); use kernel 0/1");
+}
+
+// dynamic LDS of debug_walk_device's launch (blocks of 64): kernel 3's NodeW table, the stack columns of kernels 2 / 3, and 64 ray times
+// where the scene has moving spheres (walk_debug.inc has the map)
 static const size_t DEBUG_WALK_LDS_MAX = 160 * 1024;
 inline size_t debug_walk_lds_bytes(const FlatView& v, int kernel) {
     size_t b = 0;
-    if (kernel == 3) b += ((size_t)v.n_nodes2 + 128) / 129 * 3 * 4128;
-    if (kernel == 2 || kernel == 3) b += (size_t)v.stack2 * 64 * sizeof(uint32_t);
+    if (kernel == 3) b += nodew_bytes(v);
+    if (kernel == 2 || kernel == 3) b += walk_stack_bytes(v.stack2, 64);
     if (v.kinds_mask & (1u << NK_MSPHERE)) b += 64 * sizeof(double) + (kernel == 1 ? 8 : 0);  // (kernel 1: the slots must not start at LDS address 0)
     return b;
 }

@@ -969,7 +969,7 @@ DEV bool box32(float lox, float loy, float loz, float hix, float hiy, float hiz,
 //     instances part; kernels 5 / 6 take the larger of that and world_depth2 + 2): the sentinel fits with a row to spare and
 //     no size changed with it.  One row too few would not reach a neighbour's column but the ring / job bookkeeping behind the stacks.
 // walk_stack_bytes / coop_stack_rows: the one place the launches and the kernels size these columns from.
-__host__ __device__ inline size_t walk_stack_bytes(uint32_t rows, uint32_t threads) { return (size_t)rows * threads * sizeof(uint32_t); }
+// (walk_stack_bytes itself lives in device.h since round 17: abi.cpp sizes the same columns before it touches a device)
 __host__ __device__ inline uint32_t coop_stack_rows(const FlatView& v) {  // kernel 5 (its two walks never share a stack) and the hit queries of kernels 5 / 6
     const uint32_t d = (v.world_depth2 > v.inst_depth2 ? v.world_depth2 : v.inst_depth2) + 2u;
     return d > v.stack2_inline ? d : v.stack2_inline;
@@ -4246,6 +4246,16 @@ struct DevBuf {
         reset();
         HIP_CHECK(hipMalloc(&p, n ? n : 16));
     }
+    // what the diagnostics do with their buffers: n bytes from the host, n zero bytes, n bytes back (synchronous, the null stream)
+    void upload(const void* src, size_t n) {
+        alloc(n);
+        HIP_CHECK(hipMemcpy(p, src, n, hipMemcpyHostToDevice));
+    }
+    void zeros(size_t n) {
+        alloc(n);
+        HIP_CHECK(hipMemset(p, 0, n));
+    }
+    void download(void* dst, size_t n, size_t from = 0) const { HIP_CHECK(hipMemcpy(dst, (const char*)p + from, n, hipMemcpyDeviceToHost)); }
 };
 struct Events {
     std::vector<hipEvent_t> ev;
@@ -4282,6 +4292,81 @@ static const DevInfo& dev_info(int dev) {
     di.lds_max -= 1024;  // the statistics build keeps 48 counters in static LDS
 #endif
     return g_devinfo.emplace(dev, di).first->second;
+}
+
+// ---- the launch scaffold: one copy of each step that every driver below (and in the .inc files) takes ----
+// the current device, its properties, and the scene's view with this device's copy of the blob as its base
+struct DeviceView {
+    int dev;
+    const DevInfo& di;
+    FlatView view;
+};
+static DeviceView device_view(const rt_scene& s, double* upload_ms = nullptr, uint64_t* env_total = nullptr) {
+    int dev = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    DeviceView d{dev, dev_info(dev), s.flat.view};
+    d.view.base = device_blob(s, dev, upload_ms, env_total);
+    return d;
+}
+// a launch with more than 48 KB of dynamic LDS has to say so first
+static void set_dynamic_lds(const void* fn, size_t bytes) {
+    if (bytes > 48 * 1024) HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+}
+// waits for `stream` and returns the error word its launches wrote
+static int wait_error_word(const void* d_err, hipStream_t stream) {
+    int h_err = 0;
+    HIP_CHECK(hipMemcpyAsync(&h_err, d_err, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    return h_err;
+}
+// the error word of a launch: bit 0 is unit() of a zero vector, every other bit a broken invariant.  entry: "" or the entry point's name;
+// bits_note: "" or what the bits mean, behind the number
+static void throw_device_error(int h_err, const std::string& entry = "", const char* bits_note = "") {
+    if (h_err & 1) throw RtError(RT_ERR_UNIT_ZERO, "unitizing zero vector (device" + (entry.empty() ? "" : ", " + entry) + ")");
+    if (h_err & ~1)
+        throw RtError(RT_ERR_INTERNAL, "device invariant failed" + (entry.empty() ? "" : " in " + entry) + " (error bits " + std::to_string(h_err) + bits_note + ")");
+}
+// the four <ACCEL, GENERAL> instantiations of a walk-pass kernel (aov_kernel, ao_kernel, occluded_kernel): the accel walk or the
+// reference-order one, the chain walk (GENERAL == 3) for nested Transforms
+#define WALK_PASS_KERNEL(K, accel, nest) ((accel) ? ((nest) ? K<true, 3> : K<true, 1>) : ((nest) ? K<false, 3> : K<false, 1>))
+// their dynamic LDS, announced to the launch: the stacks of a 64-lane workgroup (walk 2; the caller has checked that they fit)
+static size_t walk_pass_lds(const FlatView& view, int walk, const void* fn) {
+    const size_t smem = (walk == 2) ? walk_stack_bytes(view.stack2, 64) : 0;
+    set_dynamic_lds(fn, smem);
+    return smem;
+}
+// A one-launch pixel pass (rt_render_aov, rt_ao_render): one lane per pixel in blocks of 64 on `stream`, spp camera samples each.  The
+// error word, the two events around launch(blocks, err), the wait, the word's verdict and what the call reports.
+template <class Launch>
+static void run_pixel_pass(const rt_scene& s, const char* entry, int width, int height, int spp, int walk, double upload_ms, hipStream_t stream, rt_stats* st,
+                           Launch launch) {
+    const size_t npix = (size_t)width * (size_t)height;
+    DevBuf err;
+    err.alloc(4);
+    HIP_CHECK(hipMemsetAsync(err.p, 0, 4, stream));
+    Events events;
+    hipEvent_t e0 = events.make(), e1 = events.make();
+    const unsigned blocks = (unsigned)((npix + 63) / 64);
+    HIP_CHECK(hipEventRecord(e0, stream));
+    launch(blocks, (int*)err.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(e1, stream));
+    HIP_CHECK(hipEventSynchronize(e1));
+    int h_err = 0;
+    err.download(&h_err, 4);
+    throw_device_error(h_err, entry);
+    if (st) {
+        float ms = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+        st->kernel_ms = ms;
+        st->upload_ms = upload_ms;
+        st->samples = (uint64_t)npix * (uint64_t)spp;
+        st->launches = 1;
+        st->kernel_used = walk;
+        st->block_threads = 64;
+        st->grid_blocks = (int32_t)blocks;
+        st->scene_bytes = s.flat.info.bytes;
+    }
 }
 // A workspace = the waves' unit rings, the accumulator, the per-tile tickets and a small block {work counter, error flag}.
 // Kept for the life of the process and reused by later calls on the same device (grown when a call needs more);
@@ -4434,6 +4519,70 @@ static pt_coop_fn coop_variant(const CoopKey& k) {
                                        (k.wide ? "uint64_t" : "uint32_t") + ", " + std::to_string(k.tie) + "> is compiled (COOP_VARIANTS)");
 }
 
+// ---- the pt_kernel_wf variants (kernel 6), likewise: <INTEG, MIXED, TIE>, every combination of the three integrators ----
+// (the rows of this table and of the two below stand in the order in which the nested ?: they replace named their kernels: the compiler
+// emits instantiations in the order it meets them, and a fresh resource report (`make asm`) keeps the order of its rows that way)
+typedef void (*pt_wf_fn)(FlatView, CamK, RenderK, double*, double*, unsigned int*, unsigned int*, int*, WfArgs);
+#define WF_ROW(X, M, T) X(2, M, T) X(0, M, T) X(1, M, T)
+#define WF_VARIANTS(X) WF_ROW(X, true, true) WF_ROW(X, false, true) WF_ROW(X, true, false) WF_ROW(X, false, false)
+struct WfKey {
+    int integ;
+    bool mixed, tie;
+    bool operator==(const WfKey& o) const { return integ == o.integ && mixed == o.mixed && tie == o.tie; }
+};
+struct WfVariant {
+    WfKey key;
+    pt_wf_fn fn;
+};
+#define WF_ENTRY(I, M, T) {{I, M, T}, pt_kernel_wf<I, M, T>},
+static const WfVariant WF_TABLE[] = {WF_VARIANTS(WF_ENTRY)};
+#undef WF_ENTRY
+static_assert(sizeof(WF_TABLE) / sizeof(WF_TABLE[0]) == 12, "WF_VARIANTS: 4 rows x 3");
+static pt_wf_fn wf_variant(const WfKey& k) {
+    for (const WfVariant& v : WF_TABLE)
+        if (v.key == k) return v.fn;
+    throw RtError(RT_ERR_INTERNAL, "no pt_kernel_wf<" + std::to_string(k.integ) + ", " + std::to_string(k.mixed) + ", " + std::to_string(k.tie) + "> is compiled (WF_VARIANTS)");
+}
+typedef void (*wf_walk_fn)(FlatView, WfWalkK);
+static wf_walk_fn wf_walk_variant(bool tie) { return tie ? wf_walk_kernel<true> : wf_walk_kernel<false>; }  // the walk launch: <TIE>
+
+// ---- the photon and eye kernels of the SPPM passes (sppm.inc), likewise ----
+// ACCEL: kernel 2's walk; LDS (photon pass, with ACCEL only): the accel's hot tables staged; NEST (never with ACCEL: nested scenes have no
+// accel walk in these passes): the chain-walk kernels; MEDIA: the scene has a ConstantMedium.  X(media, accel, lds, nest, kernel)
+#define PHOTON_VARIANTS(X)                                                                                                      \
+    X(true, true, true, false, (photon_kernel_media<true, true>)) X(false, true, true, false, (photon_kernel<true, true>))      \
+    X(true, true, false, false, (photon_kernel_media<true, false>)) X(true, false, false, true, photon_kernel_nest_media)       \
+    X(true, false, false, false, (photon_kernel_media<false, false>)) X(false, true, false, false, (photon_kernel<true, false>)) \
+    X(false, false, false, true, photon_kernel_nest) X(false, false, false, false, (photon_kernel<false, false>))
+#define EYE_VARIANTS(X)                                                                                                 \
+    X(true, true, false, false, eye_kernel_media<true>) X(true, false, false, true, eye_kernel_nest_media)              \
+    X(true, false, false, false, eye_kernel_media<false>) X(false, true, false, false, eye_kernel<true>)                \
+    X(false, false, false, true, eye_kernel_nest) X(false, false, false, false, eye_kernel<false>)
+typedef void (*photon_fn)(FlatView, SppmK, LightK, PhotonBuf, PhotonBuf, unsigned int*, int*);
+typedef void (*eye_fn)(FlatView, const CamK*, SppmK, double*, int*);
+struct SppmKey {
+    bool media, accel, lds, nest;
+    bool operator==(const SppmKey& o) const { return media == o.media && accel == o.accel && lds == o.lds && nest == o.nest; }
+};
+template <class Fn>
+struct SppmVariant {
+    SppmKey key;
+    Fn fn;
+};
+#define SPPM_ENTRY(M, A, L, N, K) {{M, A, L, N}, K},
+static const SppmVariant<photon_fn> PHOTON_TABLE[] = {PHOTON_VARIANTS(SPPM_ENTRY)};
+static const SppmVariant<eye_fn> EYE_TABLE[] = {EYE_VARIANTS(SPPM_ENTRY)};
+#undef SPPM_ENTRY
+static_assert(sizeof(PHOTON_TABLE) / sizeof(PHOTON_TABLE[0]) == 8, "PHOTON_VARIANTS: {accel + LDS, accel, nest, neither} x MEDIA or not");
+static_assert(sizeof(EYE_TABLE) / sizeof(EYE_TABLE[0]) == 6, "EYE_VARIANTS: {accel, nest, neither} x MEDIA or not");
+template <class Fn, size_t N>
+static Fn sppm_variant(const SppmVariant<Fn> (&table)[N], const SppmKey& k, const char* what) {
+    for (const SppmVariant<Fn>& v : table)
+        if (v.key == k) return v.fn;
+    throw RtError(RT_ERR_INTERNAL, std::string("no ") + what + " kernel for media " + std::to_string(k.media) + ", accel " + std::to_string(k.accel) + ", lds " +
+                                       std::to_string(k.lds) + ", nest " + std::to_string(k.nest) + " is compiled (PHOTON_VARIANTS / EYE_VARIANTS)");
+}
+
 // Kernels 5 / 6 run their TIE variants ("EXACT ties" above traverse<>) for every scene that holds a rectangle or a cube: only those have
 // boxes that can BEGIN exactly where another surface lies (bvh.rs:88 + aabb.rs:28-30).  Scenes of spheres and triangle meshes alone keep the
 // variants without the flag (as the sphere-only variants of kernels 1 / 2 carry no tie code).
@@ -4498,21 +4647,19 @@ static KernelChoice choose_kernel(const rt_scene& s, const FlatView& view, const
                                           std::to_string(s.flat.msph_t0_max) + ", " + std::to_string(s.flat.msph_t1_min) + "] for this scene): their boxes are built for that range");
     }
     const size_t lds_max = c.lds_max = di.lds_max - (moving ? (size_t)PT_BLOCK * sizeof(double) : 0);
-    // The accel kernels need the camera inside the region the f32 boxes were padded for (flatten.cpp: origin_limit2) and
-    // t_min >= 0 (box32's proof); otherwise kernel 1 (reference order) renders.
-    const double cam_abs = c.cam_abs =
-        std::fmax(std::fmax(std::fabs(cam.origin[0]), std::fabs(cam.origin[1])), std::fabs(cam.origin[2])) + std::fabs(cam.lens_radius);
-    const bool camera_ok = cam_abs <= view.origin_limit2 && std::isfinite(cam_abs) && plan.t_min >= 0.;
+    // The accel kernels run where kernel 2's walk does (device.h: accel2_usable; the per-lane stacks live in LDS); otherwise kernel 1
+    // (reference order) renders.
+    c.cam_abs = camera_reach(cam);
     const size_t stack2_bytes = walk_stack_bytes(view.stack2, PT_BLOCK);
     const size_t hot1 = (size_t)view.stage_bytes, hot2 = (size_t)(view.stage2_end - view.stage2_begin);
-    const bool accel2_usable = view.accel_ok && camera_ok && stack2_bytes <= lds_max;  // per-lane stacks live in LDS
+    const bool accel2_ok = accel2_usable(view, c.cam_abs, plan.t_min, PT_BLOCK, lds_max);
     // kernel 5 = kernel 2's BVH with the cooperative instance service (pt_kernel_coop): for scenes with LARGE mesh instances
     // the two walks of kernel 5 never share a stack; the world-space walk includes the instances it enters in the lane (NK_INSTANCE_INLINE)
     c.stack5 = coop_stack_rows(view);
     const size_t stack5_bytes = walk_stack_bytes(c.stack5, PT_BLOCK);
     const size_t coop_world = coop_world_bytes(view);  // world-level tables, always in LDS for this kernel
     const size_t coop_lds = (size_t)3 * COOP_RING * sizeof(uint16_t) + 8 * sizeof(uint32_t) + ((sizeof(CoopArgs) + 15) & ~size_t(15)) + coop_world;  // + three rings of pool-slot ids, counters, argument block
-    const bool coop_usable = accel2_usable && general && !media && !book2 && view.coop_data_ok != 0 && view.n_inst2 >= 1 && view.n_inst2 <= (uint32_t)COOP_MAX_INST &&
+    const bool coop_usable = accel2_ok && general && !media && !book2 && view.coop_data_ok != 0 && view.n_inst2 >= 1 && view.n_inst2 <= (uint32_t)COOP_MAX_INST &&
                              view.inst_depth2 <= (uint32_t)COOP_STACK_MAX && coop_world <= 32768 && stack5_bytes + coop_lds <= lds_max && plan.max_depth < (1 << 24);
     // kernel 6 = the same instance service across the whole GPU and across launches (wavefront.inc)
     c.stack6 = std::max<uint32_t>(std::max(view.world_depth2 + 2u, view.stack2_inline), (uint32_t)WF_ENTRY_STACK + 1u);
@@ -4522,7 +4669,7 @@ static KernelChoice choose_kernel(const rt_scene& s, const FlatView& view, const
     c.stack6w = view.inst_depth2 + 2u;
     c.wf_tables_w = coop_a16(view.stage_bytes - view.off_xforms) + coop_a16(8u * view.n_inst2) + coop_a16((uint32_t)sizeof(QGrid) * view.n_inst2);
     const size_t wf_lds_walk_min = c.wf_tables_w + walk_stack_bytes(c.stack6w, WF_WALK_BLOCK);
-    const bool wf_usable = accel2_usable && general && !media && !book2 && view.coop_data_ok != 0 && view.n_inst2 >= 1 && view.n_inst2 <= (uint32_t)WF_MAX_INST &&
+    const bool wf_usable = accel2_ok && general && !media && !book2 && view.coop_data_ok != 0 && view.n_inst2 >= 1 && view.n_inst2 <= (uint32_t)WF_MAX_INST &&
                            coop_world <= 32768 && c.wf_lds_pt <= lds_max && wf_lds_walk_min <= lds_max && plan.max_depth < (1 << 24);
     // a background (rt_scene_set_background): kernels 1 and 2 only (kernels 5 / 6 have no background variants), never the SPPM pass
     const bool bg = c.bg = view.off_bg != 0u;
@@ -4542,16 +4689,14 @@ static KernelChoice choose_kernel(const rt_scene& s, const FlatView& view, const
     // (kernel 6, the wavefront form of the same service, reaches 766 Msamples/s on C4 where kernel 5 reaches 891 and kernel 2 469: it is
     // since round 4 kernel 5 takes up to 64 instances too, so kernel 6 runs by request only)
     if (kernel == 0 && (bg || area))
-        kernel = accel2_usable ? 2 : 1;
+        kernel = accel2_ok ? 2 : 1;
     if (kernel == 0)
-        kernel = accel2_usable ? ((coop_usable && view.max_inst_nodes2 >= 64u) ? 5 : (wf_usable && !coop_usable && view.max_inst_nodes2 >= 64u) ? 6 : 2) : 1;
+        kernel = accel2_ok ? ((coop_usable && view.max_inst_nodes2 >= 64u) ? 5 : (wf_usable && !coop_usable && view.max_inst_nodes2 >= 64u) ? 6 : 2) : 1;
     if (kernel == 5 && !coop_usable)
         throw RtError(RT_ERR_UNSUPPORTED, "kernel 5 (cooperative instance service) needs a usable accel, 1..64 instances of which at least one holds only triangles with f32 vertices (an OBJ mesh), of BVH depth <= 40");
     if (kernel == 6 && !wf_usable)
         throw RtError(RT_ERR_UNSUPPORTED, "kernel 6 (wavefront instance service) needs a usable accel and 1..64 instances of which at least one holds only triangles with f32 vertices (an OBJ mesh)");
-    if ((kernel == 2 || kernel == 5) && !accel2_usable)
-        throw RtError(RT_ERR_UNSUPPORTED, "kernel 2 requested but no usable accel for this scene/camera (unbounded item, depth overflow, stacks "
-                                          "larger than LDS, negative t_min, or camera farther than 64x the scene extent); use kernel 0/1");
+    if ((kernel == 2 || kernel == 5) && !accel2_ok) refuse_kernel2();
     c.kernel = kernel;
     const size_t ring_meta = ((size_t)(PT_BLOCK / 64) * (RING_UNITS * 4 + 8) + CFG_WORDS) * sizeof(uint32_t);  // ring / job bookkeeping, behind the stacks
     c.stack_bytes = ((kernel == 2) ? stack2_bytes : (kernel == 5) ? stack5_bytes : 0) + ring_meta + ((kernel == 5) ? coop_lds : 0);
@@ -4564,8 +4709,7 @@ static KernelChoice choose_kernel(const rt_scene& s, const FlatView& view, const
     if (integ == 2 && !plan.sppm_est) throw RtError(RT_ERR_ARG, "integrator 2 (SPPM) is reached through rt_render_sppm");
     if (kernel == 6) return c;  // (scene in L2 / HBM always; media and the book-2 kinds made it unusable above)
     // kernel 2 expands the Node2 array (64 B per node) into the NodeW form (96 B) while staging it
-    const size_t nodew = ((size_t)(view.n_nodes2 + NODEW_CHUNK - 1) / NODEW_CHUNK) * 3 * NODEW_FAR;
-    c.hot_bytes = (kernel == 2 || kernel == 5) ? hot2 - (size_t)view.n_nodes2 * sizeof(Node2) + nodew : hot1;
+    c.hot_bytes = (kernel == 2 || kernel == 5) ? hot2 - (size_t)view.n_nodes2 * sizeof(Node2) + nodew_bytes(view) : hot1;
     c.lds = c.hot_bytes > 0 && c.hot_bytes + c.stack_bytes <= lds_max && !tun.no_lds && kernel != 5;  // kernel 5: scene in L2/HBM always
     if (integ != 0 && book2)
         throw RtError(RT_ERR_UNSUPPORTED, "the book-2 extensions (moving spheres, noise textures, an open shutter) render with integrator 0 (kernels 1 and 2)");
@@ -4617,7 +4761,7 @@ static LaunchLayout launch_layout(const FlatView& view, const RenderPlan& plan, 
     else
         L.fn = pt_variant(pt_key(c, integ, false));
     const void* fptr = (kernel == 5) ? (const void*)L.fn_coop : (const void*)L.fn;
-    if (smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute(fptr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    set_dynamic_lds(fptr, smem);
     int blocks_per_cu = 0;
     HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, fptr, PT_BLOCK, smem));
     if (blocks_per_cu < 1) blocks_per_cu = 1;
@@ -4628,10 +4772,10 @@ static LaunchLayout launch_layout(const FlatView& view, const RenderPlan& plan, 
              ((kernel == 2 && !v.media && !v.book2 && !v.nest && !c.bg && !c.area) || (kernel == 5 && early));
     if (L.pool && kernel == 2) {
         L.fn = pt_variant(pt_key(c, integ, true));  // (same resources as the variant the occupancy was asked for)
-        if (smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)L.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        set_dynamic_lds((const void*)L.fn, smem);
     }
     // The LDS node table of kernel 2 is padded for THIS render's ray origins (common/tighten.h): the lens (cam_abs, the
-    // quantity camera_ok was tested with: |lens offset| <= lens_radius on every axis) and points on the scene's items or inside its
+    // quantity accel2_usable was asked with: |lens offset| <= lens_radius on every axis) and points on the scene's items or inside its
     // media (their extent is part of origin_limit2 / 64: build_bvhs starts ew from media_extent).  A scene with any instance keeps the
     // stored pads: the table then holds object-space BVHs too, whose pads come from the instances' own origin bounds.  Regions, adaptive
     // passes, resumable ranges and the ranks of rt_render_multi all launch from here, with the camera of their frame.
@@ -4646,6 +4790,32 @@ static LaunchLayout launch_layout(const FlatView& view, const RenderPlan& plan, 
     L.coop_bytes = (kernel == 5) ? (size_t)grid * COOP_POOL * COOP_REC * sizeof(uint64_t) : 0;
     L.workspace_bytes = L.ring_bytes + (size_t)L.n_pix * 3 * sizeof(double) + (size_t)plan.tiles_owned * sizeof(unsigned int) + L.coop_bytes;
     return L;
+}
+
+// ---- stage 3's launch constants: the fields that kernels 1 / 2 / 5 and kernel 6 set alike for the samples [s0, s1) of a plan; each driver
+// adds its own (job sizes, unit counts, LDS node counts, stacks) ----
+static RenderK make_renderk(const RenderPlan& plan, int s0, int s1) {
+    RenderK rk = {};
+    rk.width = plan.width; rk.height = plan.height; rk.max_depth = plan.max_depth;
+    rk.t_min = plan.t_min; rk.seed = plan.seed;
+    rk.s_begin = s0; rk.s_end = s1;
+    rk.sub_spp = plan.sub_spp;
+    rk.subs_per_tile = (s1 - s0 + plan.sub_spp - 1) / plan.sub_spp;
+    rk.tiles_owned = (int)std::max<int64_t>(1, plan.tiles_owned);
+    rk.tiles_x = plan.tiles_x; rk.rank = plan.rank; rk.world = plan.world;
+    rk.sppm_est = plan.sppm_est;
+    rk.time0 = plan.time0;
+    rk.time1 = plan.time1;
+    return rk;
+}
+
+// pixel_color /= spp over the rank's tiles (render_tiles, render_tiles_wf, finalize_tiles)
+static void launch_finalize(const RenderPlan& plan, const double* d_accum, double* d_tiles, hipStream_t stream) {
+    const int64_t n_pix = plan.tiles_owned * TILE_PIX;
+    if (n_pix <= 0) return;
+    hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((n_pix + 255) / 256)), dim3(256), 0, stream, d_accum, d_tiles, n_pix, plan.spp, plan.width, plan.height,
+                       plan.tiles_x, plan.rank, plan.world);
+    HIP_CHECK(hipGetLastError());
 }
 
 // ---- stage 4: what a call reports (kernels 1 / 2 / 5 and 6; the callers add their own reserved[] words) ----
@@ -4772,14 +4942,12 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
     if (!s.committed) throw RtError(RT_ERR_NOT_COMMITTED, "scene not committed");
     const Tuning tun = tuning();  // one snapshot per call
     hipStream_t stream = (hipStream_t)stream_;
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    const DevInfo& di = dev_info(dev);
-
-    FlatView view = s.flat.view;
     double upload_ms = 0.;
     uint64_t env_total = 0;
-    view.base = device_blob(s, dev, &upload_ms, &env_total);
+    const DeviceView dv = device_view(s, &upload_ms, &env_total);
+    const int dev = dv.dev;
+    const DevInfo& di = dv.di;
+    const FlatView& view = dv.view;
     if (st) st->upload_ms = upload_ms;
     const KernelChoice c = choose_kernel(s, view, cam, plan, tun, di, env_total);
     const int kernel = c.kernel;
@@ -4803,12 +4971,7 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
     int launches = 0;
     for (int s0 = s_first; s0 < s_last; s0 += plan.spp_chunk) {
         const int s1 = std::min(s0 + plan.spp_chunk, s_last);
-        RenderK rk = {};
-        rk.width = plan.width; rk.height = plan.height; rk.max_depth = plan.max_depth;
-        rk.t_min = plan.t_min; rk.seed = plan.seed;
-        rk.s_begin = s0; rk.s_end = s1;
-        rk.sub_spp = plan.sub_spp;
-        rk.subs_per_tile = (s1 - s0 + plan.sub_spp - 1) / plan.sub_spp;
+        RenderK rk = make_renderk(plan, s0, s1);
         // jobs of JOB_UNITS units halve the cross-wave hand-offs; small launches keep single units for load balance
         // (measured: headline 592 ms with 2, 606 with 1 and a 4-slot ring, 593 with 4; 9 M-sample frame 7.0 ms with 1 or 2, 9.3 with 4)
         const bool many_units = plan.tiles_owned * (int64_t)rk.subs_per_tile >= (int64_t)64 * grid * (PT_BLOCK / 64);
@@ -4816,7 +4979,6 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
         // tile's ticket on sooner -- 1/8 of the headline frame 68.2 -> 66.6 ms, while the whole frame loses 1.2 % with single units)
         const bool tiles_cover_waves = !SINGLE_UNITS_BELOW_WAVES || plan.tiles_owned >= (int64_t)grid * (PT_BLOCK / 64);
         rk.job_units = std::max(1, std::min(many_units && tiles_cover_waves ? JOB_UNITS : 1, rk.subs_per_tile));
-        rk.tiles_owned = (int)std::max<int64_t>(1, plan.tiles_owned);
         rk.pool_mode = lay.pool ? 1 : 0;  // (job_units is 1: the rank's tiles do not cover the waves)
         Schedule sch;
         const int jobs_per_tile = make_schedule(sch, rk.tiles_owned, grid * (PT_BLOCK / 64), rk.s_begin, rk.s_end, rk.sub_spp, rk.job_units);  // host/schedule.cpp
@@ -4826,10 +4988,6 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
         int64_t units = plan.tiles_owned * (int64_t)jobs_per_tile;
         if (units > 0x7FFFFFFF) throw RtError(RT_ERR_UNSUPPORTED, "too many work units per launch");
         rk.n_units = (int)units;
-        rk.tiles_x = plan.tiles_x; rk.rank = plan.rank; rk.world = plan.world;
-        rk.sppm_est = plan.sppm_est;
-        rk.time0 = plan.time0;
-        rk.time1 = plan.time1;
         rk.time_slots = c.variant.moving ? 1 : 0;
         rk.tile_list = plan.tile_list;
         rk.box_shrink = lay.node_shrink;
@@ -4855,14 +5013,8 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
         pt_ev.emplace_back(e0, e1);
         launches++;
     }
-    if (lay.n_pix > 0 && !plan.ext_accum) {
-        hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((lay.n_pix + 255) / 256)), dim3(256), 0, stream, (const double*)accum.p, d_tiles,
-                           lay.n_pix, plan.spp, plan.width, plan.height, plan.tiles_x, plan.rank, plan.world);
-        HIP_CHECK(hipGetLastError());
-    }
-    int h_err = 0;
-    HIP_CHECK(hipMemcpyAsync(&h_err, err.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
+    if (!plan.ext_accum) launch_finalize(plan, (const double*)accum.p, d_tiles, stream);
+    const int h_err = wait_error_word(err.p, stream);
     if (st) {
         double kms = 0;
         for (auto& p : pt_ev) {
@@ -4876,9 +5028,7 @@ void render_tiles(const rt_scene& s, const CameraDev& cam, const RenderPlan& pla
         st->reserved[3] = shrink_bits;  // (rt_render_multi overwrites entry 0's with its own count afterwards)
     }
     print_tool_stats(kernel, c.lds, grid, st);
-    if (h_err & 1) throw RtError(RT_ERR_UNIT_ZERO, "unitizing zero vector (device)");
-    if (h_err & ~1) throw RtError(RT_ERR_INTERNAL, "device invariant failed (error bits " + std::to_string(h_err) + ": 2 = an instance below an instance "
-                                                   "reached an object-space walk, 4 = a kernel 5 ring entry was not published in time)");
+    throw_device_error(h_err, "", ": 2 = an instance below an instance reached an object-space walk, 4 = a kernel 5 ring entry was not published in time");
 }
 
 // ---------------------------------------------------------------- kernel 6 driver ----
@@ -4891,14 +5041,10 @@ static void render_tiles_wf(const rt_scene& s, const FlatView& view, const Camer
     const size_t lds_max = di.lds_max, lds_pt = c.wf_lds_pt, tables_w = c.wf_tables_w;
     const uint32_t stack6 = c.stack6, n_entry6 = c.n_entry6, stack6w = c.stack6w;
     const int integ = plan.integrator;
-    typedef void (*pt_wf_fn)(FlatView, CamK, RenderK, double*, double*, unsigned int*, unsigned int*, int*, WfArgs);
     const bool tie = tie_scene(view);  // the TIE variants of both launches ("EXACT ties" above traverse<>)
-    pt_wf_fn fn = tie ? ((view.n_inline2 != 0u) ? ((integ == 1) ? pt_kernel_wf<1, true, true> : (integ == 2) ? pt_kernel_wf<2, true, true> : pt_kernel_wf<0, true, true>)
-                                                : ((integ == 1) ? pt_kernel_wf<1, false, true> : (integ == 2) ? pt_kernel_wf<2, false, true> : pt_kernel_wf<0, false, true>))
-                      : ((view.n_inline2 != 0u) ? ((integ == 1) ? pt_kernel_wf<1, true> : (integ == 2) ? pt_kernel_wf<2, true> : pt_kernel_wf<0, true>)
-                                                : ((integ == 1) ? pt_kernel_wf<1> : (integ == 2) ? pt_kernel_wf<2> : pt_kernel_wf<0>));
-    void (*fn_walk)(FlatView, WfWalkK) = tie ? wf_walk_kernel<true> : wf_walk_kernel<false>;
-    if (lds_pt > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pt));
+    const pt_wf_fn fn = wf_variant(WfKey{integ, view.n_inline2 != 0u, tie});
+    const wf_walk_fn fn_walk = wf_walk_variant(tie);
+    set_dynamic_lds((const void*)fn, lds_pt);
     int bpc = 0;
     HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, (const void*)fn, PT_BLOCK, lds_pt));
     if (bpc < 1) bpc = 1;
@@ -4910,7 +5056,7 @@ static void render_tiles_wf(const rt_scene& s, const FlatView& view, const Camer
     uint32_t n_topq_w = (uint32_t)std::min<size_t>((share - tables_w - stacks_w) / sizeof(NodeQ), view.n_nodes2);
     if (tun.n_top >= 0) n_topq_w = std::min<uint32_t>(n_topq_w, (uint32_t)tun.n_top);
     const size_t lds_walk = tables_w + coop_a16(n_topq_w * (uint32_t)sizeof(NodeQ)) + stacks_w;
-    if (lds_walk > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)fn_walk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_walk));
+    set_dynamic_lds((const void*)fn_walk, lds_walk);
     int bpc_w = 0;
     HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc_w, (const void*)fn_walk, WF_WALK_BLOCK, lds_walk));
     if (bpc_w < 1) bpc_w = 1;
@@ -4949,21 +5095,11 @@ static void render_tiles_wf(const rt_scene& s, const FlatView& view, const Camer
     double kms = 0.;
     for (int s0 = 0; s0 < plan.spp; s0 += plan.spp_chunk) {
         const int s1 = std::min(s0 + plan.spp_chunk, plan.spp);
-        RenderK rk = {};
-        rk.width = plan.width; rk.height = plan.height; rk.max_depth = plan.max_depth;
-        rk.t_min = plan.t_min; rk.seed = plan.seed;
-        rk.s_begin = s0; rk.s_end = s1;
-        rk.sub_spp = plan.sub_spp;
-        rk.subs_per_tile = (s1 - s0 + plan.sub_spp - 1) / plan.sub_spp;
+        RenderK rk = make_renderk(plan, s0, s1);
         rk.job_units = 1;  // kernel 6 deals single units (next_unit_wf)
         int64_t units = plan.tiles_owned * (int64_t)rk.subs_per_tile;
         if (units > 0x7FFFFFFF) throw RtError(RT_ERR_UNSUPPORTED, "too many work units per launch");
         rk.n_units = (int)units;
-        rk.tiles_x = plan.tiles_x; rk.rank = plan.rank; rk.world = plan.world;
-        rk.tiles_owned = (int)std::max<int64_t>(1, plan.tiles_owned);
-        rk.sppm_est = plan.sppm_est;
-        rk.time0 = plan.time0;
-        rk.time1 = plan.time1;
         rk.n_top = (int)std::min<uint32_t>(128u, view.world_top2);
         rk.n_topq = (int)n_entry6;
         rk.coop_stack = (int)stack6;
@@ -5016,19 +5152,12 @@ static void render_tiles_wf(const rt_scene& s, const FlatView& view, const Camer
         HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
         kms += ms;
     }
-    if (n_pix > 0) {
-        hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((n_pix + 255) / 256)), dim3(256), 0, stream, (const double*)lease.w->accum, d_tiles,
-                           n_pix, plan.spp, plan.width, plan.height, plan.tiles_x, plan.rank, plan.world);
-        HIP_CHECK(hipGetLastError());
-    }
-    int h_err = 0;
-    HIP_CHECK(hipMemcpyAsync(&h_err, err, sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
+    launch_finalize(plan, (const double*)lease.w->accum, d_tiles, stream);
+    const int h_err = wait_error_word(err, stream);
     fill_stats(st, s, plan, 6, false, grid, kms, launches, ring_bytes + (size_t)n_pix * 3 * sizeof(double) + (size_t)plan.tiles_owned * sizeof(unsigned int) + wf_bytes);
     if (st) st->reserved[2] = (uint64_t)grid_w | ((uint64_t)n_topq_w << 32);
     print_tool_stats(6, false, grid, st, launches, grid_w, seg, n_topq_w);
-    if (h_err & 1) throw RtError(RT_ERR_UNIT_ZERO, "unitizing zero vector (device)");
-    if (h_err & ~1) throw RtError(RT_ERR_INTERNAL, "device invariant failed (error bits " + std::to_string(h_err) + ")");
+    throw_device_error(h_err);
 }
 
 // ---------------------------------------------------------------- SPPM driver ----
@@ -5148,10 +5277,9 @@ struct SppmLights {
             S = 40 - e;
             S = S < 0 ? 0 : (S > 60 ? 60 : S);
         }
-        d_flux.alloc(h_flux.size() * 8); d_scale.alloc(nl * 8); d_cum.alloc(nl * 8);
-        HIP_CHECK(hipMemcpy(d_flux.p, h_flux.data(), h_flux.size() * 8, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(d_scale.p, h_scale.data(), nl * 8, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(d_cum.p, h_cum.data(), nl * 8, hipMemcpyHostToDevice));
+        d_flux.upload(h_flux.data(), h_flux.size() * 8);
+        d_scale.upload(h_scale.data(), nl * 8);
+        d_cum.upload(h_cum.data(), nl * 8);
         lk = LightK{nl, total, (const double*)d_cum.p, (const double*)d_flux.p, (const double*)d_scale.p};
     }
 };
@@ -5161,6 +5289,8 @@ struct SppmLaunch {
     bool accel = false, photon_lds = false, nest = false, media = false;
     size_t smem = 0, smem_photon = 0;
     int pblocks = 1, eblocks = 1;
+    photon_fn photon = nullptr;  // PHOTON_VARIANTS / EYE_VARIANTS: the two kernels of these flags
+    eye_fn eye = nullptr;
     // rt_debug_sppm_trace's variant word
     unsigned int word() const { return (accel ? 1u : 0u) | (photon_lds ? 2u : 0u) | (nest ? 4u : 0u) | (media ? 8u : 0u); }
 };
@@ -5168,14 +5298,12 @@ SppmLaunch sppm_choose(const rt_scene& s, const CameraDev& cam, const Tuning& tu
     SppmLaunch L;
     // ConstantMedium (D8): a volume event is a pass-through interaction in all three passes; the photon and eye walks take their path's stream
     L.media = (s.flat.view.kinds_mask & (1u << NK_MEDIUM_BEGIN)) != 0;
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    const DevInfo& di = dev_info(dev);
-    L.view = s.flat.view;
-    FlatView& view = L.view;
-    view.base = device_blob(s, dev);
-    double cam_abs = std::fmax(std::fmax(std::fabs(cam.origin[0]), std::fabs(cam.origin[1])), std::fabs(cam.origin[2])) + std::fabs(cam.lens_radius);
-    L.accel = view.accel_ok && cam_abs <= view.origin_limit2 && std::isfinite(cam_abs) && walk_stack_bytes(view.stack2, 256) <= di.lds_max;
+    const DeviceView dv = device_view(s);
+    const DevInfo& di = dv.di;
+    const FlatView& view = L.view = dv.view;
+    // (the rule's t_min term is always met here: the photon and eye walks start at the reference's constants, 0.0001 and 0.001 (sppm.inc),
+    // not at the caller's t_min, which reaches only the final render_tiles call and is judged there)
+    L.accel = accel2_usable(view, camera_reach(cam), 0.0001, 256, di.lds_max);
     L.nest = s.flat.xf_nest != 0u;  // nested Transforms: the photon / eye passes take kernel 1's chain walk (their accel walks have none)
     if (L.nest) L.accel = false;
     // per-lane accel stacks: stack2 entries, as render_tiles gives kernel 2 and its MEDIA variants (traverse2_media's walks take the
@@ -5185,9 +5313,9 @@ SppmLaunch sppm_choose(const rt_scene& s, const CameraDev& cam, const Tuning& tu
     const size_t hot2 = (size_t)(view.stage2_end - view.stage2_begin);
     L.smem_photon = hot2 + L.smem;
     L.photon_lds = L.accel && hot2 > 0 && 2 * L.smem_photon <= di.lds_max && !tun.no_lds;
-    if (L.photon_lds && L.smem_photon > 48 * 1024)
-        HIP_CHECK(hipFuncSetAttribute(L.media ? (const void*)photon_kernel_media<true, true> : (const void*)photon_kernel<true, true>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.smem_photon));
+    L.photon = sppm_variant(PHOTON_TABLE, SppmKey{L.media, L.accel, L.photon_lds, L.nest}, "photon");
+    L.eye = sppm_variant(EYE_TABLE, SppmKey{L.media, L.accel, false, L.nest}, "eye");
+    if (L.photon_lds) set_dynamic_lds((const void*)L.photon, L.smem_photon);
     // persistent photon waves: enough 256-thread blocks to fill every CU at 4 waves per SIMD, never more waves than chunks
     L.pblocks = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)photons_per_iter + 4 * PHOTON_CHUNK - 1) / (4 * PHOTON_CHUNK), (int64_t)di.cus * 4));
     L.eblocks = (int)std::min<size_t>((npix + 255) / 256, (size_t)di.cus * 8);
@@ -5202,29 +5330,10 @@ void sppm_capacities(int photons_per_iter, const Tuning& tun, unsigned int& cap_
 // one photon pass (iteration skp.iteration) on `ps`, into the stores g and c
 void sppm_launch_photons(const SppmLaunch& L, const SppmK& skp, const LightK& lk, PhotonStore& g, PhotonStore& c, unsigned int* d_cursor, int* d_err_p,
                          hipStream_t ps) {
-    const FlatView& view = L.view;
-    const int pblocks = L.pblocks;
-    const size_t smem = L.smem, smem_photon = L.smem_photon;
     HIP_CHECK(hipMemsetAsync(g.count.p, 0, 4, ps));
     HIP_CHECK(hipMemsetAsync(c.count.p, 0, 4, ps));
     HIP_CHECK(hipMemsetAsync(d_cursor, 0, 4, ps));
-    if (L.media) {  // the same four choices, MEDIA variants
-        if (L.accel && L.photon_lds)
-            hipLaunchKernelGGL((photon_kernel_media<true, true>), dim3(pblocks), dim3(256), smem_photon, ps, view, skp, lk, g.b, c.b, d_cursor, d_err_p);
-        else if (L.accel)
-            hipLaunchKernelGGL((photon_kernel_media<true, false>), dim3(pblocks), dim3(256), smem, ps, view, skp, lk, g.b, c.b, d_cursor, d_err_p);
-        else if (L.nest)
-            hipLaunchKernelGGL(photon_kernel_nest_media, dim3(pblocks), dim3(256), 0, ps, view, skp, lk, g.b, c.b, d_cursor, d_err_p);
-        else
-            hipLaunchKernelGGL((photon_kernel_media<false, false>), dim3(pblocks), dim3(256), 0, ps, view, skp, lk, g.b, c.b, d_cursor, d_err_p);
-    } else if (L.accel && L.photon_lds)
-        hipLaunchKernelGGL((photon_kernel<true, true>), dim3(pblocks), dim3(256), smem_photon, ps, view, skp, lk, g.b, c.b, d_cursor, d_err_p);
-    else if (L.accel)
-        hipLaunchKernelGGL((photon_kernel<true, false>), dim3(pblocks), dim3(256), smem, ps, view, skp, lk, g.b, c.b, d_cursor, d_err_p);
-    else if (L.nest)  // nested Transforms: the chain walk (such scenes have no accel)
-        hipLaunchKernelGGL(photon_kernel_nest, dim3(pblocks), dim3(256), 0, ps, view, skp, lk, g.b, c.b, d_cursor, d_err_p);
-    else
-        hipLaunchKernelGGL((photon_kernel<false, false>), dim3(pblocks), dim3(256), 0, ps, view, skp, lk, g.b, c.b, d_cursor, d_err_p);
+    hipLaunchKernelGGL(L.photon, dim3(L.pblocks), dim3(256), L.photon_lds ? L.smem_photon : L.smem, ps, L.view, skp, lk, g.b, c.b, d_cursor, d_err_p);
     HIP_CHECK(hipGetLastError());
 }
 // waits for the photon pass on `ps`; it is repeated (relaunch()) with larger stores if one overflowed (the pass is deterministic).
@@ -5238,7 +5347,7 @@ int sppm_collect_photons(PhotonStore& sg, PhotonStore& sc, int* d_err_p, hipStre
         HIP_CHECK(hipMemcpyAsync(&nc, sc.count.p, 4, hipMemcpyDeviceToHost, ps));
         HIP_CHECK(hipMemcpyAsync(&h_err, d_err_p, 4, hipMemcpyDeviceToHost, ps));
         HIP_CHECK(hipStreamSynchronize(ps));
-        if (h_err & 1) throw RtError(RT_ERR_UNIT_ZERO, "unitizing zero vector (device, photon pass)");
+        throw_device_error(h_err & 1, "photon pass");  // (bit 1 is the stores' overflow, handled below)
         if (!(h_err & 2)) break;
         HIP_CHECK(hipMemsetAsync(d_err_p, 0, 4, ps));
         if (ng > sg.b.cap) {
@@ -5256,15 +5365,7 @@ int sppm_collect_photons(PhotonStore& sg, PhotonStore& sc, int* d_err_p, hipStre
 }
 // the eye pass of iteration sk.iteration on `stream`: gp = width * height x {valid, p, bsdf}
 void sppm_launch_eye(const SppmLaunch& L, const CamK* d_cam, const SppmK& sk, double* d_gp, int* d_err, hipStream_t stream) {
-    const FlatView& view = L.view;
-    const int eblocks = L.eblocks;
-    if (L.media) {
-        if (L.accel) hipLaunchKernelGGL(eye_kernel_media<true>, dim3(eblocks), dim3(256), L.smem, stream, view, d_cam, sk, d_gp, d_err);
-        else if (L.nest) hipLaunchKernelGGL(eye_kernel_nest_media, dim3(eblocks), dim3(256), 0, stream, view, d_cam, sk, d_gp, d_err);
-        else hipLaunchKernelGGL(eye_kernel_media<false>, dim3(eblocks), dim3(256), 0, stream, view, d_cam, sk, d_gp, d_err);
-    } else if (L.accel) hipLaunchKernelGGL(eye_kernel<true>, dim3(eblocks), dim3(256), L.smem, stream, view, d_cam, sk, d_gp, d_err);
-    else if (L.nest) hipLaunchKernelGGL(eye_kernel_nest, dim3(eblocks), dim3(256), 0, stream, view, d_cam, sk, d_gp, d_err);
-    else hipLaunchKernelGGL(eye_kernel<false>, dim3(eblocks), dim3(256), 0, stream, view, d_cam, sk, d_gp, d_err);
+    hipLaunchKernelGGL(L.eye, dim3(L.eblocks), dim3(256), L.smem, stream, L.view, d_cam, sk, d_gp, d_err);
 }
 }  // namespace
 
@@ -5282,15 +5383,12 @@ void render_sppm(const rt_scene& s, const CameraDev& cam, RenderPlan plan, const
     DevBuf d_cam, d_err, d_gp, d_stats, d_est, d_cursor;
     d_cursor.alloc(4);
     CamK ck = to_camk(cam);
-    d_cam.alloc(sizeof(CamK));
-    HIP_CHECK(hipMemcpy(d_cam.p, &ck, sizeof(CamK), hipMemcpyHostToDevice));
-    d_err.alloc(4);
-    HIP_CHECK(hipMemset(d_err.p, 0, 4));
+    d_cam.upload(&ck, sizeof(CamK));
+    d_err.zeros(4);
     const size_t npix = (size_t)plan.width * plan.height;
     d_gp.alloc(npix * 7 * 8);
-    d_stats.alloc(npix * 10 * 8);
+    d_stats.zeros(npix * 10 * 8);
     d_est.alloc(npix * 6 * 8);
-    HIP_CHECK(hipMemset(d_stats.p, 0, npix * 10 * 8));
 
     // Two streams: the photon pass of iteration i+1 (stream P) runs beside the grid build + eye pass + gather of iteration i
     // (the caller's stream), on double-buffered photon stores.  Both are latency-bound on their own (paths of 1..max_bounces
@@ -5311,8 +5409,7 @@ void render_sppm(const rt_scene& s, const CameraDev& cam, RenderPlan plan, const
         pc[j].alloc(cap_c);
     }
     DevBuf d_err_p;  // error flags of the photon pass (its own word: the retry below clears it while the other stream runs)
-    d_err_p.alloc(4);
-    HIP_CHECK(hipMemset(d_err_p.p, 0, 4));
+    d_err_p.zeros(4);
     Grid gg, gc;
     SppmK sk;
     sk.width = plan.width; sk.height = plan.height; sk.photons_per_iter = cfg.photons_per_iter;
@@ -5355,12 +5452,9 @@ void render_sppm(const rt_scene& s, const CameraDev& cam, RenderPlan plan, const
     }
     hipLaunchKernelGGL(estimate_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, (const double*)d_stats.p, npix,
                        (double)cfg.iterations * (double)cfg.photons_per_iter, (double*)d_est.p);
-    int h_err = 0;
-    HIP_CHECK(hipMemcpyAsync(&h_err, d_err.p, 4, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
-    if (h_err & 1) throw RtError(RT_ERR_UNIT_ZERO, "unitizing zero vector (device, SPPM pre-pass)");
+    throw_device_error(wait_error_word(d_err.p, stream) & 1, "SPPM pre-pass");
     const double prepass_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (stats_host) HIP_CHECK(hipMemcpy(stats_host, d_stats.p, npix * 10 * 8, hipMemcpyDeviceToHost));
+    if (stats_host) d_stats.download(stats_host, npix * 10 * 8);
     if (totals2) {
         totals2[0] = tg;
         totals2[1] = tc;
@@ -5375,12 +5469,7 @@ void render_sppm(const rt_scene& s, const CameraDev& cam, RenderPlan plan, const
 
 void finalize_tiles(const RenderPlan& plan, const double* d_accum, double* d_tiles, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    const int64_t n_pix = plan.tiles_owned * TILE_PIX;
-    if (n_pix > 0) {
-        hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((n_pix + 255) / 256)), dim3(256), 0, stream, d_accum, d_tiles, n_pix, plan.spp, plan.width,
-                           plan.height, plan.tiles_x, plan.rank, plan.world);
-        HIP_CHECK(hipGetLastError());
-    }
+    launch_finalize(plan, d_accum, d_tiles, stream);
     HIP_CHECK(hipStreamSynchronize(stream));
 }
 
@@ -5398,34 +5487,31 @@ void debug_rng_device(uint64_t seed, uint64_t pixel, uint64_t sample, int n, uin
     b.alloc((size_t)n * 8);
     hipLaunchKernelGGL(rng_kernel, dim3(1), dim3(64), 0, 0, seed, pixel, sample, n, (uint64_t*)b.p);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpy(out_host, b.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    b.download(out_host, (size_t)n * 8);
 }
 void debug_rng_floats_device(uint64_t seed, uint64_t pixel, uint64_t sample, int n, double lo, double hi, double* out_gen, double* out_range) {
     DevBuf b;
     b.alloc((size_t)n * 16);
     hipLaunchKernelGGL(rng_floats_kernel, dim3(1), dim3(64), 0, 0, seed, pixel, sample, n, lo, hi, (double*)b.p);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpy(out_gen, b.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(out_range, (const char*)b.p + (size_t)n * 8, (size_t)n * 8, hipMemcpyDeviceToHost));
+    b.download(out_gen, (size_t)n * 8);
+    b.download(out_range, (size_t)n * 8, (size_t)n * 8);
 }
 void debug_math_device(int op, size_t n, const double* a, const double* bb, double* out) {
     DevBuf da, db, dc;
-    da.alloc(n * 8);
-    db.alloc(n * 8);
+    da.upload(a, n * 8);
+    if (bb) db.upload(bb, n * 8);
+    else db.alloc(n * 8);
     dc.alloc(n * 8);
-    HIP_CHECK(hipMemcpy(da.p, a, n * 8, hipMemcpyHostToDevice));
-    if (bb) HIP_CHECK(hipMemcpy(db.p, bb, n * 8, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(math_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, n, (const double*)da.p, (const double*)db.p,
                        (double*)dc.p);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpy(out, dc.p, n * 8, hipMemcpyDeviceToHost));
+    dc.download(out, n * 8);
 }
 static const char* env_debug_blob(const rt_scene& s, uint32_t* w, uint32_t* h) {
     if (!s.committed) throw RtError(RT_ERR_NOT_COMMITTED, "scene not committed");
     if (env_table_bytes(s, w, h) == 0) throw RtError(RT_ERR_ARG, "the scene has no env sampling (rt_scene_set_env_sampling)");
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    return device_blob(s, dev);
+    return device_view(s).view.base;
 }
 void debug_env_table_device(const rt_scene& s, int* w, int* h, uint32_t* q_host) {
     uint32_t W = 0, H = 0;
@@ -5443,44 +5529,33 @@ void debug_env_eval_device(const rt_scene& s, int mode, size_t n, const double* 
     view.base = env_debug_blob(s, nullptr, nullptr);
     const size_t n_in = n * (mode == 0 ? 4 : 3) * sizeof(double), n_out = n * (mode == 0 ? 4 : 1) * sizeof(double);
     DevBuf din, dout, err;
-    din.alloc(n_in);
     dout.alloc(n_out);
-    err.alloc(4);
-    HIP_CHECK(hipMemset(err.p, 0, 4));
-    HIP_CHECK(hipMemcpy(din.p, in, n_in, hipMemcpyHostToDevice));
+    err.zeros(4);
+    din.upload(in, n_in);
     hipLaunchKernelGGL(env_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, view, mode, n, (const double*)din.p, (double*)dout.p, (int*)err.p);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpy(out, dout.p, n_out, hipMemcpyDeviceToHost));
+    dout.download(out, n_out);
 }
 void debug_area_eval_device(const rt_scene& s, int mode, size_t n, const double* in, double* out) {
     if (!s.committed) throw RtError(RT_ERR_NOT_COMMITTED, "scene not committed");
     if (s.flat.view.off_area == 0u) throw RtError(RT_ERR_ARG, "the scene has no area lights (rt_scene_set_area_lights)");
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    FlatView view = s.flat.view;
-    view.base = device_blob(s, dev);
+    const FlatView view = device_view(s).view;
     const size_t n_in = n * (mode == 0 ? 7 : 6) * sizeof(double), n_out = n * (mode == 0 ? 4 : 1) * sizeof(double);
     DevBuf din, dout;
-    din.alloc(n_in);
     dout.alloc(n_out);
-    HIP_CHECK(hipMemcpy(din.p, in, n_in, hipMemcpyHostToDevice));
+    din.upload(in, n_in);
     hipLaunchKernelGGL(area_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, view, mode, n, (const double*)din.p, (double*)dout.p);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpy(out, dout.p, n_out, hipMemcpyDeviceToHost));
+    dout.download(out, n_out);
 }
 void debug_hit_device(const rt_scene& s, int kernel, size_t n, const double* rays, double t_min, double t_max, double* out) {
     if (s.flat.view.kinds_mask & (1u << NK_MSPHERE)) throw RtError(RT_ERR_UNSUPPORTED, "rt_debug_hit_device has no ray time: scenes with moving spheres are not supported");
     if (!s.committed) throw RtError(RT_ERR_NOT_COMMITTED, "scene not committed");
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    FlatView view = s.flat.view;
-    view.base = device_blob(s, dev);
+    const FlatView view = device_view(s).view;
     DevBuf dr, dout, err;
-    dr.alloc(n * 48);
     dout.alloc(n * 96);
-    err.alloc(4);
-    HIP_CHECK(hipMemset(err.p, 0, 4));
-    HIP_CHECK(hipMemcpy(dr.p, rays, n * 48, hipMemcpyHostToDevice));
+    err.zeros(4);
+    dr.upload(rays, n * 48);
     if (kernel < 1 || kernel > 7 || kernel == 4) throw RtError(RT_ERR_ARG, "rt_debug_hit_device: kernel 1, 2, 3, 5, 6 or 7");
     // 7: mode 3's table with the pads of a render whose origins are these rays' (common/tighten.h): O_r = 2 max(ew, largest |origin coordinate|
     // of the batch); as in a render, a scene with instances keeps the stored pads, and so does a batch that reaches origin_limit2
@@ -5493,6 +5568,8 @@ void debug_hit_device(const rt_scene& s, int kernel, size_t n, const double* ray
         shrink = box_shrink(view.origin_limit2, render_origin_bound(view.origin_limit2, o_abs), view.n_inst2 == 0u);
         kernel = 3;
     }
+    // (the parts of accel2_usable that a diagnostic on the caller's own rays can answer for, each with its own message: the origins are the
+    // caller's, as rtamd.h says, and stacks beyond LDS fail the launch)
     if (kernel != 1 && !view.accel_ok) throw RtError(RT_ERR_UNSUPPORTED, "no accel for this scene");
     if (kernel != 1 && !(t_min >= 0.)) throw RtError(RT_ERR_UNSUPPORTED, "kernel 2 needs t_min >= 0 (box32)");
     if ((kernel == 5 || kernel == 6) && (view.coop_data_ok == 0 || view.n_inst2 < 1 || view.n_inst2 > (uint32_t)COOP_MAX_INST))
@@ -5502,22 +5579,16 @@ void debug_hit_device(const rt_scene& s, int kernel, size_t n, const double* ray
     size_t smem = (kernel == 2 || kernel == 3) ? walk_stack_bytes(view.stack2, 64) : 0;
     if (kernel == 5 || kernel == 6) smem = walk_stack_bytes(coop_stack_rows(view), 64);
     if (kernel == 3) {  // kernel 2's LDS node table (NodeW, box32w) in isolation: the table must fit beside the stacks
-        smem += ((size_t)(view.n_nodes2 + NODEW_CHUNK - 1) / NODEW_CHUNK) * 3 * NODEW_FAR;
+        smem += nodew_bytes(view);
         if (smem > 160 * 1024) throw RtError(RT_ERR_UNSUPPORTED, "the NodeW table of this scene does not fit in LDS");
-        if (smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)hit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     }
-    if (s.flat.xf_nest != 0u) {  // nested Transforms: the chain walk (kernels 5 / 6 were refused above: nested scenes have no compact data)
-        if (smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)hit_kernel_nest, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        hipLaunchKernelGGL(hit_kernel_nest, dim3((unsigned)((n + 63) / 64)), dim3(64), smem, 0, view, kernel, shrink, n, (const double*)dr.p, t_min, t_max,
-                           (double*)dout.p, (int*)err.p);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(out, dout.p, n * 96, hipMemcpyDeviceToHost));
-        return;
-    }
-    hipLaunchKernelGGL(hit_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), smem, 0, view,
-                       kernel, shrink, n, (const double*)dr.p, t_min, t_max, (double*)dout.p, (int*)err.p);
+    // nested Transforms: the chain walk (kernels 5 / 6 were refused above: nested scenes have no compact data)
+    const auto fn = s.flat.xf_nest != 0u ? hit_kernel_nest : hit_kernel;
+    if (kernel == 3 || s.flat.xf_nest != 0u) set_dynamic_lds((const void*)fn, smem);
+    hipLaunchKernelGGL(fn, dim3((unsigned)((n + 63) / 64)), dim3(64), smem, 0, view, kernel, shrink, n, (const double*)dr.p, t_min, t_max, (double*)dout.p,
+                       (int*)err.p);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpy(out, dout.p, n * 96, hipMemcpyDeviceToHost));
+    dout.download(out, n * 96);
 }
 
 }  // namespace rtamd

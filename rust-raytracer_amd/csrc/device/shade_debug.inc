@@ -78,24 +78,19 @@ __global__ void light_eval_kernel(FlatView sv, int mode, size_t n, const double*
 // (the scene and the index columns were checked by abi.cpp)  Runs `launch(view, d_in, d_keys, d_out, d_err)` over n rows and folds every row's unit-zero flag into out[row * n_out + status_col]
 template <class F>
 static void shade_debug_run(const rt_scene& s, size_t n, const double* in, size_t n_in, const uint64_t* keys, double* out, size_t n_out, int status_col, F launch) {
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    FlatView view = s.flat.view;
-    view.base = device_blob(s, dev);
+    const FlatView view = device_view(s).view;
     DevBuf din, dkeys, dout, derr;
-    din.alloc(n * n_in * sizeof(double));
-    dkeys.alloc(n * 3 * sizeof(uint64_t));
+    din.upload(in, n * n_in * sizeof(double));
+    if (keys) dkeys.upload(keys, n * 3 * sizeof(uint64_t));
+    else dkeys.alloc(n * 3 * sizeof(uint64_t));
     dout.alloc(n * n_out * sizeof(double));
-    derr.alloc(n * sizeof(int));
-    HIP_CHECK(hipMemset(derr.p, 0, n * sizeof(int)));
-    HIP_CHECK(hipMemcpy(din.p, in, n * n_in * sizeof(double), hipMemcpyHostToDevice));
-    if (keys) HIP_CHECK(hipMemcpy(dkeys.p, keys, n * 3 * sizeof(uint64_t), hipMemcpyHostToDevice));
+    derr.zeros(n * sizeof(int));
     launch(view, (const double*)din.p, (const uint64_t*)dkeys.p, (double*)dout.p, (int*)derr.p);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpy(out, dout.p, n * n_out * sizeof(double), hipMemcpyDeviceToHost));
+    dout.download(out, n * n_out * sizeof(double));
     if (status_col >= 0) {
         std::vector<int> e(n);
-        HIP_CHECK(hipMemcpy(e.data(), derr.p, n * sizeof(int), hipMemcpyDeviceToHost));
+        derr.download(e.data(), n * sizeof(int));
         for (size_t k = 0; k < n; k++) out[k * n_out + (size_t)status_col] = (e[k] & 1) ? 1. : 0.;
     }
 }

@@ -17,9 +17,9 @@ void upload_photons(PhotonStore& ps, const double* rows, unsigned int n) {
             power[3 * i + a] = rows[9 * i + 3 + a];
             norm[3 * i + a] = rows[9 * i + 6 + a];
         }
-    HIP_CHECK(hipMemcpy(ps.pos.p, pos.data(), pos.size() * 8, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(ps.power.p, power.data(), power.size() * 8, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(ps.norm.p, norm.data(), norm.size() * 8, hipMemcpyHostToDevice));
+    dev_copy_to_device(ps.pos.p, pos.data(), pos.size() * 8);
+    dev_copy_to_device(ps.power.p, power.data(), power.size() * 8);
+    dev_copy_to_device(ps.norm.p, norm.data(), norm.size() * 8);
 }
 // what build_grid made of a map, and the two tables where the caller gave buffers for them
 void report_grid(const Grid& g, unsigned int n, rt_debug_grid& out) {
@@ -32,11 +32,11 @@ void report_grid(const Grid& g, unsigned int n, rt_debug_grid& out) {
     const size_t n_scan = (size_t)g.k.dim[0] * g.k.dim[1] * g.k.dim[2] + 1;
     if (out.cell_start) {
         if (out.cell_start_capacity < n_scan) throw RtError(RT_ERR_ARG, "rt_debug_sppm_gather_device: cell_start_capacity is below the grid's cells + 1");
-        HIP_CHECK(hipMemcpy(out.cell_start, g.cell_start.p, n_scan * 4, hipMemcpyDeviceToHost));
+        g.cell_start.download(out.cell_start, n_scan * 4);
     }
     if (out.index) {
         if (out.index_capacity < n) throw RtError(RT_ERR_ARG, "rt_debug_sppm_gather_device: index_capacity is below the map's photons");
-        HIP_CHECK(hipMemcpy(out.index, g.index.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        g.index.download(out.index, (size_t)n * 4);
     }
 }
 }  // namespace
@@ -51,13 +51,10 @@ bool debug_sppm_gather_device(rt_debug_sppm_gather& io) {
     upload_photons(sg, io.global, ng);
     upload_photons(sc, io.caustic, nc);
     DevBuf d_gp, d_stats, d_est, d_err;
-    d_gp.alloc(m * 7 * 8);
-    d_stats.alloc(m * 10 * 8);
+    d_gp.upload(io.points, m * 7 * 8);
+    d_stats.upload(io.stats, m * 10 * 8);
     d_est.alloc(m * 6 * 8);
-    d_err.alloc(4);
-    HIP_CHECK(hipMemset(d_err.p, 0, 4));
-    HIP_CHECK(hipMemcpy(d_gp.p, io.points, m * 7 * 8, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_stats.p, io.stats, m * 10 * 8, hipMemcpyHostToDevice));
+    d_err.zeros(4);
     SppmK sk{};
     sk.width = (int)m; sk.height = 1;  // gather_kernel's pixel count
     sk.k_global = io.k_global; sk.k_caustic = io.k_caustic; sk.alpha = io.alpha; sk.S = io.shift;
@@ -76,11 +73,9 @@ bool debug_sppm_gather_device(rt_debug_sppm_gather& io) {
     hipLaunchKernelGGL(estimate_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, (const double*)d_stats.p, m, io.n_emitted,
                        (double*)d_est.p);
     HIP_CHECK(hipGetLastError());
-    int h_err = 0;
-    HIP_CHECK(hipMemcpyAsync(&h_err, d_err.p, 4, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
-    HIP_CHECK(hipMemcpy(io.stats, d_stats.p, m * 10 * 8, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(io.estimates, d_est.p, m * 6 * 8, hipMemcpyDeviceToHost));
+    const int h_err = wait_error_word(d_err.p, stream);
+    d_stats.download(io.stats, m * 10 * 8);
+    d_est.download(io.estimates, m * 6 * 8);
     report_grid(gg, ng, io.grid_global);
     report_grid(gc, nc, io.grid_caustic);
     return (h_err & 1) != 0;

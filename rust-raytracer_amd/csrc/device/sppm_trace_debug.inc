@@ -11,9 +11,9 @@ namespace {
 void download_photons(const PhotonStore& ps, unsigned int n, double* rows) {
     if (n == 0) return;
     std::vector<double> pos(3 * (size_t)n), power(3 * (size_t)n), norm(3 * (size_t)n);
-    HIP_CHECK(hipMemcpy(pos.data(), ps.pos.p, pos.size() * 8, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(power.data(), ps.power.p, power.size() * 8, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(norm.data(), ps.norm.p, norm.size() * 8, hipMemcpyDeviceToHost));
+    ps.pos.download(pos.data(), pos.size() * 8);
+    ps.power.download(power.data(), power.size() * 8);
+    ps.norm.download(norm.data(), norm.size() * 8);
     for (size_t i = 0; i < n; i++)
         for (int a = 0; a < 3; a++) {
             rows[9 * i + a] = pos[3 * i + a];
@@ -45,8 +45,7 @@ bool debug_sppm_trace_device(const rt_scene& s, const CameraDev& cam, rt_debug_s
     if (io.global || io.caustic) {
         DevBuf d_cursor, d_err_p;
         d_cursor.alloc(4);
-        d_err_p.alloc(4);
-        HIP_CHECK(hipMemset(d_err_p.p, 0, 4));
+        d_err_p.zeros(4);
         PhotonStore sg, sc;
         unsigned int cap_g = io.capacity_global, cap_c = io.capacity_caustic;
         sppm_capacities(io.photons_per_iter, tun, cap_g, cap_c);
@@ -77,18 +76,13 @@ bool debug_sppm_trace_device(const rt_scene& s, const CameraDev& cam, rt_debug_s
     if (io.points) {
         DevBuf d_cam, d_gp, d_err;
         CamK ck = to_camk(cam);
-        d_cam.alloc(sizeof(CamK));
-        HIP_CHECK(hipMemcpy(d_cam.p, &ck, sizeof(CamK), hipMemcpyHostToDevice));
-        d_err.alloc(4);
-        HIP_CHECK(hipMemset(d_err.p, 0, 4));
-        d_gp.alloc(npix * 7 * 8);
-        HIP_CHECK(hipMemset(d_gp.p, 0, npix * 7 * 8));  // the kernel writes only `valid` of a pixel without a gather point
+        d_cam.upload(&ck, sizeof(CamK));
+        d_err.zeros(4);
+        d_gp.zeros(npix * 7 * 8);  // the kernel writes only `valid` of a pixel without a gather point
         sppm_launch_eye(L, (const CamK*)d_cam.p, sk, (double*)d_gp.p, (int*)d_err.p, stream);
         HIP_CHECK(hipGetLastError());
-        int h_err = 0;
-        HIP_CHECK(hipMemcpyAsync(&h_err, d_err.p, 4, hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        HIP_CHECK(hipMemcpy(io.points, d_gp.p, npix * 7 * 8, hipMemcpyDeviceToHost));
+        const int h_err = wait_error_word(d_err.p, stream);
+        d_gp.download(io.points, npix * 7 * 8);
         unit_zero = unit_zero || (h_err & 1) != 0;
     }
     if (too_small) throw RtError(RT_ERR_ARG, "rt_debug_sppm_trace_device: a photon buffer holds fewer rows than its map (n_global, n_caustic are set)");

@@ -11,7 +11,7 @@
 
 namespace rtamd {
 
-static_assert(NODEW_CHUNK == 129u && NODEW_FAR == 4128u, "debug_walk_lds_bytes (device.h) restates nodew_bytes");
+static_assert(NODEW_CHUNK == 129u && NODEW_FAR == 4128u, "nodew_bytes(const FlatView&) of device.h restates the kernels' nodew_bytes(n_nodes)");
 
 // accel 1: traverse over the reference-order program; 2: the accel walk over the Node2 array in global memory (pt_kernel<false, ..>);
 // 3: over the NodeW table in LDS (pt_kernel<true, ..>'s walk).  times: the scene has moving spheres.
@@ -62,29 +62,23 @@ static walk_fn pick_walk_kernel(int g, bool media) {
 
 // (the arguments, the scene, the accel, the times and the LDS size were checked by abi.cpp)  true: a unit() met a zero vector
 bool debug_walk_device(const rt_scene& s, int kernel, size_t n, const double* rays, const uint64_t* keys, double t_min, double* out) {
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    FlatView view = s.flat.view;
-    view.base = device_blob(s, dev);
+    const FlatView view = device_view(s).view;
     const SceneVariant variant = scene_variant(s, false);  // render_tiles' own choice, for integrator 0 and a closed shutter
     const bool moving = variant.moving;
     const walk_fn fn = pick_walk_kernel(variant.g(), variant.media);
     const size_t smem = debug_walk_lds_bytes(view, kernel);
     DevBuf dr, dk, dout, derr;
-    dr.alloc(n * 7 * sizeof(double));
-    dk.alloc(n * 3 * sizeof(uint64_t));
+    dr.upload(rays, n * 7 * sizeof(double));
+    dk.upload(keys, n * 3 * sizeof(uint64_t));
     dout.alloc(n * 14 * sizeof(double));
-    derr.alloc(sizeof(int));
-    HIP_CHECK(hipMemset(derr.p, 0, sizeof(int)));
-    HIP_CHECK(hipMemcpy(dr.p, rays, n * 7 * sizeof(double), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dk.p, keys, n * 3 * sizeof(uint64_t), hipMemcpyHostToDevice));
-    if (smem > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    derr.zeros(sizeof(int));
+    set_dynamic_lds((const void*)fn, smem);
     hipLaunchKernelGGL(fn, dim3((unsigned)((n + 63) / 64)), dim3(64), smem, 0, view, kernel, moving ? 1 : 0, n, (const double*)dr.p, (const uint64_t*)dk.p, t_min,
                        (double*)dout.p, (int*)derr.p);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpy(out, dout.p, n * 14 * sizeof(double), hipMemcpyDeviceToHost));
+    dout.download(out, n * 14 * sizeof(double));
     int unit_zero = 0;  // materialize's unit() met a vector of length 0 on some row: every row is written, and the call says so
-    HIP_CHECK(hipMemcpy(&unit_zero, derr.p, sizeof(int), hipMemcpyDeviceToHost));
+    derr.download(&unit_zero, sizeof(int));
     return (unit_zero & 1) != 0;
 }
 

@@ -879,6 +879,88 @@ int rt_debug_sppm_trace_device(const rt_scene* s, const rt_camera* cam, int devi
  * RT_ERR_UNSUPPORTED where an extent is negative or not finite. */
 int rt_debug_grid_shape(const double* lo3, const double* hi3, uint64_t n, double* cell, int32_t* dim3);
 
+/* ---- temporal accumulation across camera frames (no reference counterpart) ------------------------------------------- */
+/* One step of temporal accumulation with reprojection: the current frame is blended into a history that the previous frame left, each
+ * pixel fetching its history from where its first hit was on screen under the previous camera.  A scene is immutable after
+ * rt_scene_commit, so only the camera moves between frames and the reprojection of a diffuse surface is exact.  f64, one thread per
+ * pixel, no contraction; only + - * / floor fmin fmax fabs and comparisons, in the order written here: tests/temporal_ref.py restates
+ * the step bit for bit.
+ *   buffers  rgb[H][W][3]; aov[H][W][8] as rt_render_aov writes it = {normal[3], t, albedo[3], coverage}; variance[H][W] = the variance
+ *            of the pixel's mean luminance as rt_denoised_render returns it (may be NULL); history[H][W][6] = {r, g, b, m1, m2, n}: the
+ *            accumulated colour, the first and second moment of the luminance, the history length (an integer-valued double);
+ *            out_variance[H][W] (may be NULL).  prev_history, prev_aov and cam_prev are all given or all NULL (the first frame).
+ *            Outputs must not be inputs.
+ *   helpers  dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z; cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x);
+ *            l = (0.2126 r + 0.7152 g) + 0.0722 b; centre(cam, x, y, t): u = ((double)x + 0.5) / (double)(W - 1),
+ *            v = ((double)y + 0.5) / (double)(H - 1), st = 1.0 - v, d = ((llc + hor u) + ver st) - origin, P = origin + d t.  Of an
+ *            rt_camera_frame only origin, lower_left_corner, horizontal and vertical are read: the lens is ignored (t is the guides'
+ *            mean parameter along the pixel's rays).
+ *   rule     per pixel (x, y); "reset" means out = {rgb, l, l l, 1.0}:
+ *   1. reset when there is no previous frame or aov.coverage is not > 0 (pixels that see the background restart);
+ *   2. P = centre(cur, x, y, aov.t), q = P - origin_prev, D0 = llc_prev - origin_prev, N0 = cross(hor_prev, ver_prev),
+ *      s = dot(q, N0) / dot(D0, N0); reset unless s > 0 (a point behind the previous camera, NaN);
+ *   3. r = q / s - D0, u' = dot(r, hor_prev) / dot(hor_prev, hor_prev), st' = dot(r, ver_prev) / dot(ver_prev, ver_prev),
+ *      fx = u' (double)(W - 1) - 0.5, fy = (1.0 - st') (double)(H - 1) - 0.5; reset unless fx > -1.0 && fx < (double)W && fy > -1.0 &&
+ *      fy < (double)H; only then x0 = floor(fx), y0 = floor(fy) become integers (in [-1, W - 1] and [-1, H - 1]);
+ *   4. wx = fx - x0, wy = fy - y0, reach2 = dot(P - origin_cur, P - origin_cur).  The four bilinear taps (j, i) = (0,0), (0,1), (1,0),
+ *      (1,1) at pixel (x0 + i, y0 + j) have the weight b = (i ? wx : 1.0 - wx) * (j ? wy : 1.0 - wy).  A tap is valid iff it lies inside
+ *      the image, b > 0, its history n > 0, its prev_aov.coverage > 0, dn dn <= (plane_tolerance plane_tolerance) reach2 with
+ *      Pq = centre(prev, xq, yq, prev_aov.t), e = Pq - P, dn = dot(e, normal_cur) (the tap's point lies near the pixel's tangent
+ *      plane), dot(normal_cur, normal_q) >= normal_min and (|dr| + |dg|) + |db| <= albedo_tolerance of the guide albedos.  Valid taps
+ *      add Wsum += b and A_c += b h_c for c = r, g, b, m1, m2, from 0.0 in tap order; nmin is the least n of the valid taps;
+ *   5. reset unless Wsum >= min_weight; otherwise h = A / Wsum, n = fmin(nmin + 1.0, (double)max_history), a = fmax(alpha, 1.0 / n),
+ *      out_c = (1.0 - a) h_c + a rgb_c, m1 = (1.0 - a) h_m1 + a l, m2 = (1.0 - a) h_m2 + a (l l);
+ *   6. out_variance = Vf a (a = 1.0 on a reset), the variance of the accumulated mean luminance: Vf = variance[pix] where n < 4.0 and a
+ *      variance was given (a short history has no temporal estimate), otherwise Vf = fmax(0.0, m2 - m1 m1).
+ * Limits: background pixels restart; specular and glass surfaces reproject by their first hit; the lens is ignored; nothing in a scene
+ * moves.  RT_ERR_ARG, before any device is touched: a null cfg, cam_cur, rgb, aov or out_history; width or height < 2; a config value
+ * out of its range or NaN; reserved != 0; only some of cam_prev, prev_history, prev_aov; an output that is an input.  Then
+ * RT_ERR_NO_DEVICE. */
+typedef struct rt_temporal_config {
+    double alpha;            /* 0..1: least weight of the new frame; 0 = plain running mean up to max_history; default 0.2 */
+    double plane_tolerance;  /* > 0: a tap's point may lie this far from the pixel's tangent plane, relative to the pixel's distance from the camera; default 0.02 */
+    double normal_min;       /* -1..1: least dot product of the two guide normals; default 0.9 */
+    double albedo_tolerance; /* >= 0, +inf allowed: largest (|dr| + |dg|) + |db| of the guide albedos; default 0.25 */
+    double min_weight;       /* > 0, <= 1: least sum of valid bilinear weights for a pixel to keep its history; default 0.25 */
+    int32_t max_history;     /* 1..65536: cap of the history length; default 32 */
+    int32_t reserved[5];     /* must be 0 */
+} rt_temporal_config;
+void rt_default_temporal_config(rt_temporal_config* c);
+/* HOST memory */
+int rt_temporal_accumulate(const rt_temporal_config* cfg, int32_t width, int32_t height, const rt_camera_frame* cam_prev,
+                           const rt_camera_frame* cam_cur, const double* rgb, const double* aov, const double* variance,
+                           const double* prev_history, const double* prev_aov, double* out_history, double* out_variance);
+/* the same on DEVICE memory of the current device, queued on `hip_stream` (hipStream_t as void*, NULL = default stream); returns after
+ * the work has completed on that stream */
+int rt_temporal_accumulate_device(const rt_temporal_config* cfg, int32_t width, int32_t height, const rt_camera_frame* cam_prev,
+                                  const rt_camera_frame* cam_cur, const double* d_rgb, const double* d_aov, const double* d_variance,
+                                  const double* d_prev_history, const double* d_prev_aov, double* d_out_history, double* d_out_variance,
+                                  void* hip_stream);
+
+/* A device-resident sequence of frames of one width x height on one device (-1: the device current at the sequence's first frame): the history,
+ * the previous frame's guides and the previous camera stay on the device between frames.  cfg NULL = rt_default_temporal_config.  One
+ * thread uses a sequence at a time.  rt_sequence_frame renders one frame:
+ *   A  rt_denoised_render's first three stages, unchanged: the noisy frame (rt_render's bits), the two-half variance, the guides;
+ *   B  rt_temporal_accumulate with stage A's variance against the sequence's history (the first frame after a reset resets every pixel);
+ *   C  luma_mode -1: out_rgb is the accumulated colour; 0 / 1: rt_denoise / rt_denoise_sym over (accumulated colour, stage B's variance,
+ *      guides) under dn (NULL = rt_default_denoise_config).  The history keeps the unfiltered accumulation.
+ * out_rgb[H][W][3] (required), out_accum[H][W][3], out_history[H][W][6], out_variance[H][W] (stage B's) may be NULL; HOST memory;
+ * nothing else leaves the device.  p->seed is used as it is: a host that passes one seed for every frame repeats its noise (the bindings
+ * default to base seed + frame index).  The sequence remembers rt_scene_fingerprint(s): a frame of another scene resets first.
+ * RT_ERR_ARG, before the device: a null q, s, cam, p or out_rgb; p->width / p->height other than the sequence's; aov_spp < 1 (the step
+ * needs guides); luma_mode outside -1..1; everything rt_denoised_render refuses as an argument.  Then what rt_denoised_render returns
+ * for the scene (media and moving spheres: RT_ERR_UNSUPPORTED).  p->device is not read: the sequence's device is used.  stats as
+ * rt_denoised_render's.  rt_sequence_create: RT_ERR_ARG for a null out, width or height < 2 or beyond 2^31 pixels, device < -1, a config
+ * rt_temporal_accumulate refuses; no device is touched before the first frame. */
+typedef struct rt_sequence rt_sequence;
+int rt_sequence_create(int32_t width, int32_t height, int32_t device, const rt_temporal_config* cfg, rt_sequence** out);
+void rt_sequence_destroy(rt_sequence* q);
+int rt_sequence_reset(rt_sequence* q);          /* the next frame resets every pixel */
+int rt_sequence_frames(const rt_sequence* q);   /* frames since the last reset; RT_ERR_ARG for NULL */
+int rt_sequence_frame(rt_sequence* q, const rt_scene* s, const rt_camera* cam, const rt_params* p, const rt_denoise_config* dn,
+                      int32_t luma_mode, int32_t aov_spp, double* out_rgb, double* out_accum, double* out_history, double* out_variance,
+                      rt_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

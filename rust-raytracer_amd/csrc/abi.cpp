@@ -18,6 +18,7 @@
 #include "device/ao.h"
 #include "device/denoise.h"
 #include "device/device.h"
+#include "device/temporal.h"
 #include "host/frame.h"
 #include "host/scene.h"
 #include "rtamd.h"
@@ -991,6 +992,119 @@ int rt_denoised_render_device(const rt_scene* s, const rt_camera* cam, const rt_
                               int32_t aov_spp, double* d_out_rgb, double* d_out_noisy, double* d_out_variance, double* d_out_aov,
                               void* hip_stream, rt_stats* stats) {
     return render_denoised_entry(s, cam, p, cfg, luma_mode, aov_spp, d_out_rgb, d_out_noisy, d_out_variance, d_out_aov, true, hip_stream, stats);
+}
+
+// ---- temporal accumulation (device/temporal.hip through the weak declarations of device/temporal.h; the driver: host/frame.cpp sequence_frame) ----
+void rt_default_temporal_config(rt_temporal_config* c) {
+    if (!c) return;
+    std::memset(c, 0, sizeof(*c));
+    c->alpha = 0.2;
+    c->plane_tolerance = 0.02;
+    c->normal_min = 0.9;
+    c->albedo_tolerance = 0.25;
+    c->min_weight = 0.25;
+    c->max_history = 32;
+}
+// (every comparison is written so that a NaN fails it)
+static void check_temporal_config(const rt_temporal_config* cfg) {
+    REQUIRE(cfg->alpha >= 0. && cfg->alpha <= 1., "alpha must be 0..1");
+    REQUIRE(cfg->plane_tolerance > 0., "plane_tolerance must be > 0");
+    REQUIRE(cfg->normal_min >= -1. && cfg->normal_min <= 1., "normal_min must be -1..1");
+    REQUIRE(cfg->albedo_tolerance >= 0., "albedo_tolerance must be >= 0 (+inf: no albedo test)");
+    REQUIRE(cfg->min_weight > 0. && cfg->min_weight <= 1., "min_weight must be > 0 and <= 1");
+    REQUIRE(cfg->max_history >= 1 && cfg->max_history <= 65536, "max_history must be 1..65536");
+    for (int32_t r : cfg->reserved) REQUIRE(r == 0, "reserved fields of rt_temporal_config must be 0");
+}
+static void check_temporal_size(int32_t width, int32_t height) {
+    REQUIRE(width >= 2 && height >= 2 && (int64_t)width * height <= (int64_t(1) << 31), "width and height must be at least 2 (at most 2^31 pixels)");
+}
+static void check_temporal_args(const rt_temporal_config* cfg, int32_t width, int32_t height, const rt_camera_frame* cam_prev,
+                                const rt_camera_frame* cam_cur, const double* rgb, const double* aov, const double* variance,
+                                const double* prev_history, const double* prev_aov, const double* out_history, const double* out_variance) {
+    REQUIRE(cfg && cam_cur && rgb && aov && out_history, "null argument");
+    check_temporal_size(width, height);
+    check_temporal_config(cfg);
+    REQUIRE((cam_prev && prev_history && prev_aov) || (!cam_prev && !prev_history && !prev_aov),
+            "cam_prev, prev_history and prev_aov are given together, or all NULL on a first frame");
+    for (const double* o : {out_history, out_variance})
+        REQUIRE(!o || (o != rgb && o != aov && o != variance && o != prev_history && o != prev_aov), "outputs must not be inputs");
+    REQUIRE(out_variance != out_history, "out_history and out_variance must differ");
+}
+int rt_temporal_accumulate(const rt_temporal_config* cfg, int32_t width, int32_t height, const rt_camera_frame* cam_prev,
+                           const rt_camera_frame* cam_cur, const double* rgb, const double* aov, const double* variance,
+                           const double* prev_history, const double* prev_aov, double* out_history, double* out_variance) {
+    return guard([&] {
+        check_temporal_args(cfg, width, height, cam_prev, cam_cur, rgb, aov, variance, prev_history, prev_aov, out_history, out_variance);
+        require_device(temporal_host != nullptr);
+        temporal_host(*cfg, width, height, cam_prev, *cam_cur, rgb, aov, variance, prev_history, prev_aov, out_history, out_variance);
+        return (int)RT_OK;
+    });
+}
+int rt_temporal_accumulate_device(const rt_temporal_config* cfg, int32_t width, int32_t height, const rt_camera_frame* cam_prev,
+                                  const rt_camera_frame* cam_cur, const double* d_rgb, const double* d_aov, const double* d_variance,
+                                  const double* d_prev_history, const double* d_prev_aov, double* d_out_history, double* d_out_variance,
+                                  void* hip_stream) {
+    return guard([&] {
+        check_temporal_args(cfg, width, height, cam_prev, cam_cur, d_rgb, d_aov, d_variance, d_prev_history, d_prev_aov, d_out_history, d_out_variance);
+        require_device(temporal_device != nullptr);
+        temporal_device(*cfg, width, height, cam_prev, *cam_cur, d_rgb, d_aov, d_variance, d_prev_history, d_prev_aov, d_out_history, d_out_variance,
+                        hip_stream);
+        return (int)RT_OK;
+    });
+}
+
+int rt_sequence_create(int32_t width, int32_t height, int32_t device, const rt_temporal_config* cfg, rt_sequence** out) {
+    return guard([&] {
+        REQUIRE(out, "null argument");
+        *out = nullptr;
+        check_temporal_size(width, height);
+        REQUIRE(device >= -1, "device must be a HIP device ordinal or -1 (the device current at the first frame)");
+        rt_temporal_config tc;
+        if (cfg) tc = *cfg;
+        else rt_default_temporal_config(&tc);
+        check_temporal_config(&tc);
+        rt_sequence* q = new rt_sequence();
+        q->width = width;
+        q->height = height;
+        q->device = device;
+        q->cfg = tc;
+        *out = q;
+        return (int)RT_OK;
+    });
+}
+void rt_sequence_destroy(rt_sequence* q) { delete q; }
+int rt_sequence_reset(rt_sequence* q) {
+    return guard([&] {
+        REQUIRE(q, "null sequence");
+        q->frames = 0;
+        return (int)RT_OK;
+    });
+}
+int rt_sequence_frames(const rt_sequence* q) {
+    return guard([&] {
+        REQUIRE(q, "null sequence");
+        return q->frames;
+    });
+}
+int rt_sequence_frame(rt_sequence* q, const rt_scene* s, const rt_camera* cam, const rt_params* p, const rt_denoise_config* dn, int32_t luma_mode,
+                      int32_t aov_spp, double* out_rgb, double* out_accum, double* out_history, double* out_variance, rt_stats* stats) {
+    return guard([&] {
+        REQUIRE(q && s && cam && p && out_rgb, "null argument");
+        REQUIRE(p->width == q->width && p->height == q->height, "width / height differ from the sequence's (a sequence has one frame size)");
+        REQUIRE(p->spp >= 2 && p->spp % 2 == 0, "rt_sequence_frame needs an even spp >= 2 (two half-frames)");
+        REQUIRE(p->world == 1 && p->rank == 0, "rt_sequence_frame renders whole frames: world must be 1 and rank 0");
+        REQUIRE(luma_mode >= -1 && luma_mode <= 1, "luma_mode must be -1 (no filter), 0 (rt_denoise) or 1 (rt_denoise_sym)");
+        REQUIRE(aov_spp >= 1, "aov_spp must be >= 1: the temporal step needs guides");
+        rt_denoise_config dc;
+        if (dn) dc = *dn;
+        else rt_default_denoise_config(&dc);
+        check_denoise_config(&dc);
+        const double* outs[4] = {out_rgb, out_accum, out_history, out_variance};
+        for (int i = 0; i < 4; i++)
+            for (int j = 0; j < i; j++) REQUIRE(!outs[i] || outs[i] != outs[j], "the outputs must be distinct buffers");
+        sequence_frame(*q, *s, *cam, *p, dc, luma_mode, aov_spp, out_rgb, out_accum, out_history, out_variance, stats);
+        return (int)RT_OK;
+    });
 }
 
 int rt_tonemap_u8(const double* rgb, size_t n_channels, uint8_t* out) {

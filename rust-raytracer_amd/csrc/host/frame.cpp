@@ -12,6 +12,7 @@
 #include "device/adaptive.h"
 #include "device/denoise.h"
 #include "device/region.h"
+#include "device/temporal.h"
 
 namespace rtamd {
 
@@ -308,28 +309,22 @@ void render_adaptive(const rt_scene& s, const rt_camera& cam, const rt_params& p
 }
 
 // ---- one call from scene to clean frame ----
-void render_denoised(const rt_scene& s, const rt_camera& cam, const rt_params& p, const rt_denoise_config& cfg, int luma_mode, int aov_spp,
-                     double* out_rgb, double* out_noisy, double* out_variance, double* out_aov, bool on_device, void* stream, rt_stats* stats) {
-    RenderPlan pl = make_plan(&p);
+void denoised_refuse(const rt_scene& s, const rt_params& p, int aov_spp) {
     require_committed(s);
     if (p.kernel == 6 || p.integrator == 2)
         throw RtError(RT_ERR_UNSUPPORTED, "rt_denoised_render runs with kernels 0 / 1 / 2 / 5 and integrators 0 / 1 (those of rt_render_accumulate_device)");
     if (aov_spp > 0) aov_refuse(s);  // (before the frame is rendered; such scenes pass aov_spp = 0)
-    require_device(adaptive_copy_tiles != nullptr && denoise_split_halves != nullptr && render_aov_device != nullptr && denoise_device != nullptr &&
-                   denoise_sym_device != nullptr);
-    const CallClock clock;
-    DeviceScope dev_scope(p.device);  // (device outputs and the stream must belong to it)
-    const CameraDev cd = make_camera(cam);
-    const size_t npix = (size_t)pl.width * (size_t)pl.height;
+}
+static bool denoised_linked() {
+    return adaptive_copy_tiles != nullptr && denoise_split_halves != nullptr && render_aov_device != nullptr && denoise_device != nullptr &&
+           denoise_sym_device != nullptr;
+}
+// The first three stages of rt_denoised_render on the current device: the frame in two sample ranges into one accumulator with a snapshot
+// between them, the split into d_noisy and d_var, and the guides into d_aov (aov_spp > 0).  Returns the stats of the two ranges.
+static rt_stats render_noisy_stage(const rt_scene& s, const CameraDev& cd, const rt_params& p, RenderPlan pl, int aov_spp, double* d_noisy,
+                                   double* d_var, double* d_aov, void* stream) {
     const size_t acc_bytes = row_doubles(pl.tiles_total) * sizeof(double);
-    // the running sums S and their snapshot S_h after the first half; then whatever the caller did not give device memory for
-    DevBuf acc(acc_bytes), half(acc_bytes), own_rgb(on_device ? 16 : npix * 3 * sizeof(double)),
-        own_noisy((on_device && out_noisy) ? 16 : npix * 3 * sizeof(double)), own_var((on_device && out_variance) ? 16 : npix * sizeof(double)),
-        own_aov((aov_spp == 0 || (on_device && out_aov)) ? 16 : npix * 8 * sizeof(double));
-    double* d_rgb = on_device ? out_rgb : own_rgb.f64();
-    double* d_noisy = (on_device && out_noisy) ? out_noisy : own_noisy.f64();
-    double* d_var = (on_device && out_variance) ? out_variance : own_var.f64();
-    double* d_aov = aov_spp == 0 ? nullptr : (on_device && out_aov) ? out_aov : own_aov.f64();
+    DevBuf acc(acc_bytes), half(acc_bytes);  // the running sums S and their snapshot S_h after the first half
     const int h = pl.spp / 2;
     rt_stats sum{};
     for (int range = 0; range < 2; range++) {
@@ -349,6 +344,27 @@ void render_denoised(const rt_scene& s, const rt_camera& cam, const rt_params& p
     denoise_split_halves(pl, acc.f64(), half.f64(), d_noisy, d_var, stream);
     if (aov_spp > 0)
         render_aov_device(s, cd, pl.width, pl.height, pl.seed, pl.t_min, (p.kernel == 1 || p.kernel == 2) ? p.kernel : 0, aov_spp, d_aov, stream, nullptr);
+    return sum;
+}
+
+void render_denoised(const rt_scene& s, const rt_camera& cam, const rt_params& p, const rt_denoise_config& cfg, int luma_mode, int aov_spp,
+                     double* out_rgb, double* out_noisy, double* out_variance, double* out_aov, bool on_device, void* stream, rt_stats* stats) {
+    const RenderPlan pl = make_plan(&p);
+    denoised_refuse(s, p, aov_spp);
+    require_device(denoised_linked());
+    const CallClock clock;
+    DeviceScope dev_scope(p.device);  // (device outputs and the stream must belong to it)
+    const CameraDev cd = make_camera(cam);
+    const size_t npix = (size_t)pl.width * (size_t)pl.height;
+    // whatever the caller did not give device memory for
+    DevBuf own_rgb(on_device ? 16 : npix * 3 * sizeof(double)), own_noisy((on_device && out_noisy) ? 16 : npix * 3 * sizeof(double)),
+        own_var((on_device && out_variance) ? 16 : npix * sizeof(double)),
+        own_aov((aov_spp == 0 || (on_device && out_aov)) ? 16 : npix * 8 * sizeof(double));
+    double* d_rgb = on_device ? out_rgb : own_rgb.f64();
+    double* d_noisy = (on_device && out_noisy) ? out_noisy : own_noisy.f64();
+    double* d_var = (on_device && out_variance) ? out_variance : own_var.f64();
+    double* d_aov = aov_spp == 0 ? nullptr : (on_device && out_aov) ? out_aov : own_aov.f64();
+    const rt_stats sum = render_noisy_stage(s, cd, p, pl, aov_spp, d_noisy, d_var, d_aov, stream);
     (luma_mode == 1 ? denoise_sym_device : denoise_device)(cfg, pl.width, pl.height, d_noisy, d_var, d_aov, d_rgb, nullptr, stream);
     if (!on_device) {
         dev_copy_to_host(out_rgb, d_rgb, npix * 3 * sizeof(double));
@@ -356,6 +372,78 @@ void render_denoised(const rt_scene& s, const rt_camera& cam, const rt_params& p
         if (out_variance) dev_copy_to_host(out_variance, d_var, npix * sizeof(double));
         if (out_aov) dev_copy_to_host(out_aov, d_aov, npix * 8 * sizeof(double));
     }
+    clock.finish(stats, sum, pixels_in_image(pl) * (uint64_t)pl.spp);
+}
+
+// ---- a device-resident sequence of frames with temporal accumulation ----
+}  // namespace rtamd
+rt_sequence::~rt_sequence() {
+    if (!history[0]) return;  // (nothing was allocated: no frame ran)
+    try {
+        rtamd::DeviceScope dev_scope(device);
+        for (double* b : {history[0], history[1], aov[0], aov[1], noisy, variance, acc_variance, accum, filtered})
+            if (b) rtamd::dev_free(b);
+    } catch (...) {
+    }
+}
+namespace rtamd {
+static rt_camera_frame camera_frame_of(const CameraDev& d) {
+    rt_camera_frame f;
+    for (int i = 0; i < 3; i++) {
+        f.origin[i] = d.origin[i]; f.lower_left_corner[i] = d.llc[i]; f.horizontal[i] = d.horizontal[i];
+        f.vertical[i] = d.vertical[i]; f.u[i] = d.u[i]; f.v[i] = d.v[i]; f.w[i] = d.w[i];
+    }
+    f.lens_radius = d.lens_radius;
+    return f;
+}
+void sequence_frame(rt_sequence& q, const rt_scene& s, const rt_camera& cam, const rt_params& p_in, const rt_denoise_config& cfg, int luma_mode,
+                    int aov_spp, double* out_rgb, double* out_accum, double* out_history, double* out_variance, rt_stats* stats) {
+    const RenderPlan pl = make_plan(&p_in);
+    denoised_refuse(s, p_in, aov_spp);
+    require_device(denoised_linked() && temporal_device != nullptr && temporal_history_colour != nullptr);
+    const CallClock clock;
+    if (q.device < 0) q.device = dev_get_device();
+    rt_params p = p_in;
+    p.device = q.device;
+    DeviceScope dev_scope(q.device);
+    const size_t npix = (size_t)q.width * (size_t)q.height;
+    if (!q.history[0]) {  // the first frame of the sequence: its buffers, all or none
+        double* b[9] = {};
+        const size_t doubles[9] = {6, 6, 8, 8, 3, 1, 1, 3, 3};
+        try {
+            for (int i = 0; i < 9; i++) b[i] = (double*)dev_alloc(npix * doubles[i] * sizeof(double));
+        } catch (...) {
+            for (double* x : b)
+                if (x) dev_free(x);
+            throw;
+        }
+        q.history[0] = b[0]; q.history[1] = b[1]; q.aov[0] = b[2]; q.aov[1] = b[3];
+        q.noisy = b[4]; q.variance = b[5]; q.acc_variance = b[6]; q.accum = b[7]; q.filtered = b[8];
+    }
+    const uint64_t fp = rt_scene_fingerprint(&s);
+    if (fp != q.fingerprint) q.frames = 0;  // another scene: its surfaces are not those the history saw
+    const CameraDev cd = make_camera(cam);
+    const rt_camera_frame cam_cur = camera_frame_of(cd);
+    const int cur = q.cur, prev = cur ^ 1;
+    const bool first = q.frames == 0;
+    const rt_stats sum = render_noisy_stage(s, cd, p, pl, aov_spp, q.noisy, q.variance, q.aov[cur], nullptr);
+    temporal_device(q.cfg, q.width, q.height, first ? nullptr : &q.cam_prev, cam_cur, q.noisy, q.aov[cur], q.variance, first ? nullptr : q.history[prev],
+                    first ? nullptr : q.aov[prev], q.history[cur], q.acc_variance, nullptr);
+    temporal_history_colour((int64_t)npix, q.history[cur], q.accum, nullptr);
+    const double* d_rgb = q.accum;
+    if (luma_mode >= 0) {
+        (luma_mode == 1 ? denoise_sym_device : denoise_device)(cfg, q.width, q.height, q.accum, q.acc_variance, q.aov[cur], q.filtered, nullptr, nullptr);
+        d_rgb = q.filtered;
+    }
+    dev_copy_to_host(out_rgb, d_rgb, npix * 3 * sizeof(double));
+    if (out_accum) dev_copy_to_host(out_accum, q.accum, npix * 3 * sizeof(double));
+    if (out_history) dev_copy_to_host(out_history, q.history[cur], npix * 6 * sizeof(double));
+    if (out_variance) dev_copy_to_host(out_variance, q.acc_variance, npix * sizeof(double));
+    // the frame is complete: only now does it become the sequence's previous one (a throw above leaves the last good state)
+    q.cam_prev = cam_cur;
+    q.fingerprint = fp;
+    q.cur = prev;
+    if (q.frames < INT32_MAX) q.frames++;
     clock.finish(stats, sum, pixels_in_image(pl) * (uint64_t)pl.spp);
 }
 

@@ -1,7 +1,7 @@
 // The frame-level host driver: what a render call does around the kernels -- the plan of a launch, the tile arithmetic of a partition,
 // the device buffers of a frame and the stitch into the caller's memory, and the drivers themselves (one frame on one GPU, resumable
 // rendering with host-held state, the pass loop of tile-adaptive sampling, pixel regions, the fan-out over the GPUs of a node, the SPPM
-// frame).  Plain C++17: the device is reached through device/device.h, device/adaptive.h, device/region.h and device/denoise.h only.  Everything throws RtError;
+// frame).  Plain C++17: the device is reached through device/device.h, device/adaptive.h, device/region.h, device/denoise.h and device/temporal.h only.  Everything throws RtError;
 // the extern "C" boundary (abi.cpp) checks its arguments, calls in here and turns exceptions into status codes.
 #pragma once
 #include <chrono>
@@ -13,6 +13,25 @@
 
 #define REQUIRE(c, msg) \
     if (!(c)) throw rtamd::RtError(RT_ERR_ARG, msg)
+
+// rt_sequence (rtamd.h): the state a sequence of frames keeps on its device.  Nothing is allocated before the first frame.
+struct rt_sequence {
+    int width = 0, height = 0;
+    int device = -1;  // -1 until the first frame has resolved it to the device that was current then
+    rt_temporal_config cfg{};
+    int frames = 0;            // since the last reset: 0 = the next frame has no previous one
+    uint64_t fingerprint = 0;  // rt_scene_fingerprint of the scene of the last frame
+    rt_camera_frame cam_prev{};
+    int cur = 0;  // the slot of history / aov the NEXT frame writes; the other one holds the previous frame's
+    // [npix][6] x 2, [npix][8] x 2 (ping-pong), then stage A's noisy [npix][3] and variance [npix], stage B's variance [npix], the
+    // accumulated colour and the filtered frame [npix][3]
+    double *history[2] = {nullptr, nullptr}, *aov[2] = {nullptr, nullptr}, *noisy = nullptr, *variance = nullptr, *acc_variance = nullptr,
+           *accum = nullptr, *filtered = nullptr;
+    rt_sequence() = default;
+    rt_sequence(const rt_sequence&) = delete;
+    rt_sequence& operator=(const rt_sequence&) = delete;
+    ~rt_sequence();  // (host/frame.cpp: frees the buffers on their device)
+};
 
 namespace rtamd {
 
@@ -107,6 +126,14 @@ void render_adaptive(const rt_scene& s, const rt_camera& cam, const rt_params& p
 // checks begin at RT_ERR_NOT_COMMITTED / RT_ERR_UNSUPPORTED: the entry point has checked the arguments and the config.
 void render_denoised(const rt_scene& s, const rt_camera& cam, const rt_params& p, const rt_denoise_config& cfg, int luma_mode, int aov_spp,
                      double* out_rgb, double* out_noisy, double* out_variance, double* out_aov, bool on_device, void* stream, rt_stats* stats);
+// what rt_denoised_render refuses after its argument checks and before the device, with its codes and messages (rt_sequence_frame
+// refuses the same)
+void denoised_refuse(const rt_scene& s, const rt_params& p, int aov_spp);
+// rt_sequence_frame: stage A = render_denoised's first three stages, stage B = the temporal step against the sequence's
+// device-resident history, stage C = the filter over the accumulated colour (luma_mode -1: none).  The outputs are HOST memory; all but
+// out_rgb may be null.  Its checks begin where render_denoised's do; cfg has been validated.
+void sequence_frame(rt_sequence& q, const rt_scene& s, const rt_camera& cam, const rt_params& p, const rt_denoise_config& cfg, int luma_mode,
+                    int aov_spp, double* out_rgb, double* out_accum, double* out_history, double* out_variance, rt_stats* stats);
 // rt_region_*: pixel regions of a frame.  check_regions is the argument check all four entry points share (RT_ERR_ARG for
 // a null pointer, whatever make_plan refuses, a partition, n_regions outside 1..65536, a region that is empty or leaves the frame) and
 // returns the whole frame's plan; region_pixels = the pixels of the packed output (regions counted one by one); region_tile_list = the

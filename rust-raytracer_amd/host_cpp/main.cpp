@@ -4,7 +4,7 @@
 //   rtamd_render [--scene cornell|FILE.json|FILE.yaml] [--cube data/mesh/cube.obj] [-w W] [-h H] [--spp N]
 //                [--depth D] [--seed S] [--aspect A] [--integrator 0|1] [--sppm ITERATIONS PHOTONS_PER_ITER]
 //                [--gpus N | --devices 0,1,...] [--background r,g,b | --sky] [--env-sampling] [--region x0,y0,x1,y1] [-o out.png]
-//                [--denoise [--aov-spp N] [--luma-mode M]] [--ao FILE.png [--ao-rays K] [--ao-distance D]] [--describe] [--vec3-selftest]
+//                [--denoise [--aov-spp N] [--luma-mode M]] [--sequence N [--orbit-step DEG]] [--ao FILE.png [--ao-rays K] [--ao-distance D]] [--describe] [--vec3-selftest]
 // --gpus N spreads the frame over N GPUs of this node inside ONE capture_image call (rt_render_multi: tiles dealt round-robin, RCCL
 // gather; 0 = all visible); --devices names the HIP ordinal of every rank (an ordinal may repeat).
 // `rtamd_render --cube data/mesh/cube.obj --sppm 50 500000` is the reference binary: SPPM pre-pass + 256 spp, output/test.png
@@ -16,6 +16,9 @@
 // --denoise renders the frame and filters it in one call (rt_denoised_render: --spp must be even) and writes the denoised PNG; --aov-spp N
 // guide rays per pixel (default 4; 0: none, for scenes with media or moving spheres), --luma-mode 1 (default) the energy-preserving
 // symmetric luminance stop, 0 rt_denoise's
+// --sequence N renders N frames with temporal accumulation (rt_sequence_frame: --spp samples per frame, even; --aov-spp guide rays, at
+// least 1; --luma-mode 1 / 0 filters the accumulation, -1 writes it unfiltered; frame f runs with seed --seed + f).  Between frames the
+// camera turns about its look_at point around the y axis by --orbit-step DEG (default 0), and frame f goes to NAME_%03d.png for -o NAME.png
 // --ao FILE.png writes the ambient-occlusion pass of the frame (rt_ao_render: 4 camera rays per pixel, --ao-rays K occlusion rays per hit,
 // default 4, that reach no farther than --ao-distance D, default unlimited) as the grey image visibility * coverage, and nothing else
 #include <chrono>
@@ -67,6 +70,8 @@ int main(int argc, char** argv) {
     bool crop = false;
     bool denoise_frame = false;
     int aov_spp = 4, luma_mode = 1;
+    int sequence_frames = 0;
+    double orbit_step = 0.;
     std::string ao_out;
     int ao_rays = 4;
     double ao_distance = INFINITY;
@@ -105,6 +110,8 @@ int main(int argc, char** argv) {
         else if (a == "--denoise") denoise_frame = true;
         else if (a == "--aov-spp") aov_spp = std::atoi(next());
         else if (a == "--luma-mode") luma_mode = std::atoi(next());
+        else if (a == "--sequence") sequence_frames = std::atoi(next());
+        else if (a == "--orbit-step") orbit_step = std::atof(next());
         else if (a == "--ao") ao_out = next();
         else if (a == "--ao-rays") ao_rays = std::atoi(next());
         else if (a == "--ao-distance") ao_distance = std::atof(next());
@@ -166,6 +173,34 @@ int main(int argc, char** argv) {
             img.save(ao_out);
             std::printf("ambient occlusion (%d rays per hit): %llu camera rays, kernel %d, %.1f ms, %.3fs\n", ao_rays, (unsigned long long)st.samples,
                         st.kernel_used, st.kernel_ms, st.seconds);
+            return 0;
+        }
+        if (sequence_frames > 0) {
+            Sequence seq(cfg.width, cfg.height);
+            const Camera cam0 = world->cam;
+            const size_t dot = out.rfind('.');
+            const std::string stem = dot == std::string::npos ? out : out.substr(0, dot), ext = dot == std::string::npos ? ".png" : out.substr(dot);
+            for (int f = 0; f < sequence_frames; f++) {
+                // look_from turned about look_at around the y axis by f * orbit_step degrees
+                Camera cam = cam0;
+                const double a = orbit_step * (double)f * 3.14159265358979323846 / 180.0, c = std::cos(a), s = std::sin(a);
+                const double dx = cam0.c.look_from[0] - cam0.c.look_at[0], dz = cam0.c.look_from[2] - cam0.c.look_at[2];
+                cam.c.look_from[0] = cam0.c.look_at[0] + (c * dx + s * dz);
+                cam.c.look_from[2] = cam0.c.look_at[2] + (-s * dx + c * dz);
+                Config fc = cfg;
+                fc.seed = cfg.seed + (uint64_t)f;
+                const std::vector<double> rad = seq.frame(*world, cam, fc, aov_spp, luma_mode, nullptr, nullptr, nullptr, nullptr, 0, &st);
+                RgbImage img;
+                img.width = cfg.width;
+                img.height = cfg.height;
+                img.data.resize(rad.size());
+                check(rt_tonemap_u8(rad.data(), rad.size(), img.data.data()));
+                char num[16];
+                std::snprintf(num, sizeof(num), "_%03d", f);
+                img.save(stem + num + ext);
+                std::printf("frame %d of %d (%.2f degrees, seed %llu): %llu samples, kernel %.1f ms, %.3fs\n", f, sequence_frames, orbit_step * f,
+                            (unsigned long long)fc.seed, (unsigned long long)st.samples, st.kernel_ms, st.seconds);
+            }
             return 0;
         }
         if (denoise_frame) {

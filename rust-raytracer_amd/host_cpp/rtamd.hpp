@@ -633,6 +633,68 @@ inline std::vector<double> denoise(int width, int height, const std::vector<doub
     return out;
 }
 
+// One step of temporal accumulation (rt_temporal_accumulate) on host buffers: rgb [height][width][3], aov
+// [height][width][8] and variance [height][width] (may be empty) of the current frame under cam_cur; prev_history [height][width][6],
+// prev_aov and cam_prev of the previous frame (all empty / NULL on a first frame); cfg NULL = rt_default_temporal_config.  Returns the
+// history [height][width][6] = {r, g, b, m1, m2, n}; out_variance (if given) receives the variance of the accumulated mean luminance.
+inline std::vector<double> temporal_accumulate(int width, int height, const rt_camera_frame& cam_cur, const std::vector<double>& rgb,
+                                               const std::vector<double>& aov, const std::vector<double>& variance = {},
+                                               const rt_camera_frame* cam_prev = nullptr, const std::vector<double>& prev_history = {},
+                                               const std::vector<double>& prev_aov = {}, const rt_temporal_config* cfg = nullptr,
+                                               std::vector<double>* out_variance = nullptr) {
+    const size_t n = (size_t)(width > 0 ? width : 0) * (size_t)(height > 0 ? height : 0);
+    if (rgb.size() != n * 3 || aov.size() != n * 8 || (!variance.empty() && variance.size() != n) ||
+        (!prev_history.empty() && prev_history.size() != n * 6) || (!prev_aov.empty() && prev_aov.size() != n * 8))
+        throw Error(RT_ERR_ARG, "temporal_accumulate: buffer sizes do not match the frame");
+    rt_temporal_config tc;
+    rt_default_temporal_config(&tc);
+    if (cfg) tc = *cfg;
+    std::vector<double> out(n * 6);
+    if (out_variance) out_variance->assign(n, 0.);
+    check(rt_temporal_accumulate(&tc, width, height, cam_prev, &cam_cur, rgb.data(), aov.data(), variance.empty() ? nullptr : variance.data(),
+                                 prev_history.empty() ? nullptr : prev_history.data(), prev_aov.empty() ? nullptr : prev_aov.data(), out.data(),
+                                 out_variance ? out_variance->data() : nullptr));
+    return out;
+}
+
+// A device-resident sequence of frames (rt_sequence): every frame() renders cfg.sample_per_pixel (even) samples through
+// `cam`, accumulates them into the history that the earlier frames left on the device (reprojected through the previous camera) and
+// filters the accumulation.  Only the camera moves between frames; a frame of another World resets the history.
+class Sequence {
+   public:
+    Sequence(int width, int height, int device = -1, const rt_temporal_config* cfg = nullptr) : width_(width), height_(height) {
+        check(rt_sequence_create(width, height, device, cfg, &q_));
+    }
+    ~Sequence() { rt_sequence_destroy(q_); }
+    Sequence(const Sequence&) = delete;
+    Sequence& operator=(const Sequence&) = delete;
+    void reset() { check(rt_sequence_reset(q_)); }          // the next frame resets every pixel
+    int frames() const { return check(rt_sequence_frames(q_)); }  // frames since the last reset
+    // luma_mode 1: rt_denoise_sym over the accumulation, 0: rt_denoise, -1: no filter; cfg.seed is used as it is (give every frame its own).
+    // Returns the frame's linear radiance [height][width][3]; accum [h][w][3] (the unfiltered accumulation), history [h][w][6] and
+    // variance [h][w] are filled where given.
+    std::vector<double> frame(const World& world, const Camera& cam, const Config& cfg, int aov_spp = 4, int luma_mode = 1,
+                              const rt_denoise_config* dcfg = nullptr, std::vector<double>* accum = nullptr, std::vector<double>* history = nullptr,
+                              std::vector<double>* variance = nullptr, int kernel = 0, rt_stats* stats = nullptr) {
+        rt_params p;
+        rt_default_params(&p);
+        p.width = cfg.width; p.height = cfg.height; p.spp = cfg.sample_per_pixel; p.max_depth = cfg.max_depth;
+        p.t_min = cfg.t_min; p.seed = cfg.seed; p.integrator = cfg.integrator; p.kernel = kernel;
+        const size_t n = (size_t)width_ * (size_t)height_;
+        std::vector<double> rad(n * 3);
+        if (accum) accum->assign(n * 3, 0.);
+        if (history) history->assign(n * 6, 0.);
+        if (variance) variance->assign(n, 0.);
+        check(rt_sequence_frame(q_, world.handle(), &cam.c, &p, dcfg, luma_mode, aov_spp, rad.data(), accum ? accum->data() : nullptr,
+                                history ? history->data() : nullptr, variance ? variance->data() : nullptr, stats));
+        return rad;
+    }
+
+   private:
+    rt_sequence* q_ = nullptr;
+    int width_, height_;
+};
+
 // scene.rs:16-112 cornell_box_scene(), written against the mirrored types exactly as the reference writes it
 inline std::unique_ptr<World> cornell_box_scene(const std::string& cube_obj, double aspect_ratio = 1.0, uint64_t bvh_seed = 1,
                                                 const rt_background* bg = nullptr, const rt_env_sampling* env = nullptr) {

@@ -95,6 +95,11 @@ class rt_denoise_config(C.Structure):
                 ("sigma_luma", C.c_double), ("eps", C.c_double), ("guides", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
+class rt_temporal_config(C.Structure):
+    _fields_ = [("alpha", C.c_double), ("plane_tolerance", C.c_double), ("normal_min", C.c_double), ("albedo_tolerance", C.c_double),
+                ("min_weight", C.c_double), ("max_history", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
 class rt_ao_config(C.Structure):
     _fields_ = [("ao_spp", C.c_int32), ("rays_per_hit", C.c_int32), ("max_distance", C.c_double), ("reserved", C.c_int32 * 4)]
 
@@ -232,6 +237,18 @@ _SIGS = [
                                      _dp, _dp, _dp, _dp, C.POINTER(rt_stats)]),
     ("rt_denoised_render_device", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_denoise_config), C.c_int32,
                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(rt_stats)]),
+    ("rt_default_temporal_config", None, [C.POINTER(rt_temporal_config)]),
+    ("rt_temporal_accumulate", C.c_int, [C.POINTER(rt_temporal_config), C.c_int32, C.c_int32, C.POINTER(rt_camera_frame), C.POINTER(rt_camera_frame),
+                                         _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    ("rt_temporal_accumulate_device", C.c_int, [C.POINTER(rt_temporal_config), C.c_int32, C.c_int32, C.POINTER(rt_camera_frame),
+                                                C.POINTER(rt_camera_frame), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]),
+    ("rt_sequence_create", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(rt_temporal_config), C.POINTER(C.c_void_p)]),
+    ("rt_sequence_destroy", None, [C.c_void_p]),
+    ("rt_sequence_reset", C.c_int, [C.c_void_p]),
+    ("rt_sequence_frames", C.c_int, [C.c_void_p]),
+    ("rt_sequence_frame", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_denoise_config), C.c_int32,
+                                    C.c_int32, _dp, _dp, _dp, _dp, C.POINTER(rt_stats)]),
     ("rt_default_ao_config", None, [C.POINTER(rt_ao_config)]),
     ("rt_ao_render", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_ao_config), _dp, C.POINTER(rt_stats)]),
     ("rt_ao_render_device", C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_ao_config), C.c_void_p, C.c_void_p,
@@ -1197,6 +1214,122 @@ def denoise_device(width, height, d_rgb_ptr, d_out_ptr, d_variance_ptr=None, d_a
     fn = lib().rt_denoise_sym_device if symmetric else lib().rt_denoise_device
     _chk(fn(C.byref(c), int(width), int(height), C.c_void_p(d_rgb_ptr), C.c_void_p(d_variance_ptr or 0), C.c_void_p(d_aov_ptr or 0),
             C.c_void_p(d_out_ptr), C.c_void_p(d_out_variance_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+
+def temporal_config(**fields):
+    """rt_default_temporal_config with `fields` (rt_temporal_config names) set"""
+    c = rt_temporal_config()
+    lib().rt_default_temporal_config(C.byref(c))
+    for k, v in fields.items():
+        if k == "reserved" or not hasattr(c, k):
+            raise TypeError("unknown temporal setting %r" % k)
+        setattr(c, k, v)
+    return c
+
+
+def _camera_frame(cam):
+    """an rt_camera_frame of a Camera, or the rt_camera_frame itself"""
+    return cam if isinstance(cam, rt_camera_frame) or cam is None else cam.frame()
+
+
+def temporal_accumulate(rgb, aov, cam_cur, variance=None, prev_history=None, prev_aov=None, cam_prev=None, return_variance=False, **cfg):
+    """rt_temporal_accumulate: one step of temporal accumulation with reprojection on host arrays (include/rtamd.h has the rule).
+    rgb [H, W, 3], aov [H, W, 8] from World.render_aov, variance [H, W] (None: none) of the current frame; cam_cur / cam_prev a Camera or an
+    rt_camera_frame; prev_history [H, W, 6], prev_aov [H, W, 8] and cam_prev of the previous frame, all None on a first frame.  cfg:
+    rt_temporal_config fields.  Returns the history [H, W, 6] = {r, g, b, m1, m2, n}, and with return_variance also the variance [H, W] of
+    the accumulated mean luminance."""
+    c = temporal_config(**cfg)
+    rgb = np.ascontiguousarray(rgb, dtype=np.float64)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError("rgb must be [H, W, 3]")
+    h, w = rgb.shape[:2]
+
+    def arr(a, shape, name):
+        if a is None:
+            return None, None
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != shape:
+            raise ValueError("%s must be %r" % (name, list(shape)))
+        return a, a.ctypes.data_as(_dp)
+    aov, aov_p = arr(aov, (h, w, 8), "aov")
+    variance, var_p = arr(variance, (h, w), "variance")
+    prev_history, hist_p = arr(prev_history, (h, w, 6), "prev_history")
+    prev_aov, paov_p = arr(prev_aov, (h, w, 8), "prev_aov")
+    f_cur, f_prev = _camera_frame(cam_cur), _camera_frame(cam_prev)
+    out = np.zeros((h, w, 6), dtype=np.float64)
+    out_var = np.zeros((h, w), dtype=np.float64) if return_variance else None
+    _chk(lib().rt_temporal_accumulate(C.byref(c), w, h, C.byref(f_prev) if f_prev is not None else None,
+                                      C.byref(f_cur) if f_cur is not None else None, rgb.ctypes.data_as(_dp), aov_p, var_p, hist_p, paov_p,
+                                      out.ctypes.data_as(_dp), out_var.ctypes.data_as(_dp) if out_var is not None else None))
+    return (out, out_var) if return_variance else out
+
+
+def temporal_accumulate_device(width, height, cam_cur, d_rgb_ptr, d_aov_ptr, d_out_history_ptr, d_variance_ptr=None, d_prev_history_ptr=None,
+                               d_prev_aov_ptr=None, cam_prev=None, d_out_variance_ptr=None, stream_ptr=None, **cfg):
+    """rt_temporal_accumulate_device: raw device pointers (e.g. torch tensor .data_ptr()) of the current device; returns when the step is done"""
+    c = temporal_config(**cfg)
+    f_cur, f_prev = _camera_frame(cam_cur), _camera_frame(cam_prev)
+    _chk(lib().rt_temporal_accumulate_device(C.byref(c), int(width), int(height), C.byref(f_prev) if f_prev is not None else None, C.byref(f_cur),
+                                             C.c_void_p(d_rgb_ptr), C.c_void_p(d_aov_ptr), C.c_void_p(d_variance_ptr or 0),
+                                             C.c_void_p(d_prev_history_ptr or 0), C.c_void_p(d_prev_aov_ptr or 0), C.c_void_p(d_out_history_ptr),
+                                             C.c_void_p(d_out_variance_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+
+class Sequence:
+    """rt_sequence: frames of one world and size on one device, accumulated over time.  The history, the previous guides
+    and the previous camera stay on the device; cfg: rt_temporal_config fields."""
+
+    RETURNS = ("rgb", "accum", "history", "variance", "stats")
+
+    def __init__(self, world, width, height, device=-1, **cfg):
+        self.L = lib()
+        self.world, self.width, self.height = world, int(width), int(height)
+        self.h = C.c_void_p()
+        c = temporal_config(**cfg)
+        _chk(self.L.rt_sequence_create(self.width, self.height, int(device), C.byref(c), C.byref(self.h)))
+        self._next_seed_offset = 0
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.rt_sequence_destroy(self.h)
+            self.h = None
+
+    @property
+    def frames(self):
+        """frames since the last reset"""
+        return _chk(self.L.rt_sequence_frames(self.h))
+
+    def reset(self):
+        """the next frame resets every pixel"""
+        _chk(self.L.rt_sequence_reset(self.h))
+
+    def frame(self, camera, spp, seed=None, aov_spp=4, luma_mode=1, denoise=None, returns=("rgb",), world=None, max_depth=50, t_min=1e-3,
+              kernel=0, integrator=0):
+        """rt_sequence_frame: one frame of `spp` samples through `camera`, accumulated into the history and filtered (luma_mode 1:
+        rt_denoise_sym, 0: rt_denoise, -1: no filter).  seed None: 1 + the number of frames this Sequence has rendered, so that frames do
+        not repeat their noise.  denoise: a dict of rt_denoise_config fields.  returns: which of "rgb" (the frame), "accum" (the unfiltered
+        accumulation [H, W, 3]), "history" [H, W, 6], "variance" [H, W], "stats" come back, in that order (a single name: that array)."""
+        names = (returns,) if isinstance(returns, str) else tuple(returns)
+        for n in names:
+            if n not in self.RETURNS:
+                raise ValueError("unknown output %r (one of %s)" % (n, ", ".join(self.RETURNS)))
+        if seed is None:
+            seed = 1 + self._next_seed_offset
+        w = world if world is not None else self.world
+        p = default_params(width=self.width, height=self.height, spp=int(spp), max_depth=max_depth, t_min=t_min, seed=int(seed), kernel=kernel,
+                           integrator=integrator)
+        dn = denoise_config(**(denoise or {}))
+        shapes = {"rgb": (self.height, self.width, 3), "accum": (self.height, self.width, 3), "history": (self.height, self.width, 6),
+                  "variance": (self.height, self.width)}
+        out = {k: np.zeros(shapes[k], dtype=np.float64) for k in shapes if k == "rgb" or k in names}
+        ptr = lambda k: out[k].ctypes.data_as(_dp) if k in out else None
+        st = rt_stats()
+        _chk(self.L.rt_sequence_frame(self.h, w.h, C.byref(camera.c), C.byref(p), C.byref(dn), int(luma_mode), int(aov_spp), ptr("rgb"), ptr("accum"),
+                                      ptr("history"), ptr("variance"), C.byref(st)))
+        self._next_seed_offset += 1
+        out["stats"] = st.as_dict()
+        res = tuple(out[n] for n in names)
+        return res[0] if isinstance(returns, str) else res
 
 
 def tonemap_u8(rgb):

@@ -202,6 +202,25 @@ pub struct rt_denoise_config {
     pub reserved: [i32; 5],
 }
 
+/// include/rtamd.h rt_temporal_config (rt_default_temporal_config fills it)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct rt_temporal_config {
+    pub alpha: c_double,
+    pub plane_tolerance: c_double,
+    pub normal_min: c_double,
+    pub albedo_tolerance: c_double,
+    pub min_weight: c_double,
+    pub max_history: i32,
+    pub reserved: [i32; 5],
+}
+
+/// include/rtamd.h rt_sequence: opaque
+#[repr(C)]
+pub struct rt_sequence {
+    _private: [u8; 0],
+}
+
 /// include/rtamd.h rt_background (rt_scene_set_background; kind 0 = none, the default)
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -402,6 +421,14 @@ extern "C" {
     pub fn rt_denoise_sym_device(cfg: *const rt_denoise_config, width: i32, height: i32, d_rgb: *const c_double, d_variance: *const c_double, d_aov: *const c_double, d_out_rgb: *mut c_double, d_out_variance: *mut c_double, hip_stream: *mut c_void) -> c_int;
     pub fn rt_denoised_render(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, cfg: *const rt_denoise_config, luma_mode: i32, aov_spp: i32, out_rgb: *mut c_double, out_noisy: *mut c_double, out_variance: *mut c_double, out_aov: *mut c_double, stats: *mut rt_stats) -> c_int;
     pub fn rt_denoised_render_device(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, cfg: *const rt_denoise_config, luma_mode: i32, aov_spp: i32, d_out_rgb: *mut c_double, d_out_noisy: *mut c_double, d_out_variance: *mut c_double, d_out_aov: *mut c_double, hip_stream: *mut c_void, stats: *mut rt_stats) -> c_int;
+    pub fn rt_default_temporal_config(c: *mut rt_temporal_config);
+    pub fn rt_temporal_accumulate(cfg: *const rt_temporal_config, width: i32, height: i32, cam_prev: *const rt_camera_frame, cam_cur: *const rt_camera_frame, rgb: *const c_double, aov: *const c_double, variance: *const c_double, prev_history: *const c_double, prev_aov: *const c_double, out_history: *mut c_double, out_variance: *mut c_double) -> c_int;
+    pub fn rt_temporal_accumulate_device(cfg: *const rt_temporal_config, width: i32, height: i32, cam_prev: *const rt_camera_frame, cam_cur: *const rt_camera_frame, d_rgb: *const c_double, d_aov: *const c_double, d_variance: *const c_double, d_prev_history: *const c_double, d_prev_aov: *const c_double, d_out_history: *mut c_double, d_out_variance: *mut c_double, hip_stream: *mut c_void) -> c_int;
+    pub fn rt_sequence_create(width: i32, height: i32, device: i32, cfg: *const rt_temporal_config, out: *mut *mut rt_sequence) -> c_int;
+    pub fn rt_sequence_destroy(q: *mut rt_sequence);
+    pub fn rt_sequence_reset(q: *mut rt_sequence) -> c_int;
+    pub fn rt_sequence_frames(q: *const rt_sequence) -> c_int;
+    pub fn rt_sequence_frame(q: *mut rt_sequence, s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, dn: *const rt_denoise_config, luma_mode: i32, aov_spp: i32, out_rgb: *mut c_double, out_accum: *mut c_double, out_history: *mut c_double, out_variance: *mut c_double, stats: *mut rt_stats) -> c_int;
     pub fn rt_render_sppm(s: *const rt_scene, cam: *const rt_camera, p: *const rt_params, cfg: *const rt_sppm_config, out_rgb: *mut c_double, stats_out: *mut c_double, photons_stored: *mut u64, stats: *mut rt_stats) -> c_int;
     pub fn rt_region_doubles(p: *const rt_params, n_regions: c_int, regions: *const rt_region) -> i64;
     pub fn rt_region_tiles(p: *const rt_params, n_regions: c_int, regions: *const rt_region, capacity: i64, out_tiles: *mut i32) -> i64;
@@ -1037,6 +1064,49 @@ impl DescribeHitable for XZRectLight {
 
 // ------------------------------------------------------------------ capture_image ----
 /// camera.rs:12-21: the stored frame of a constructed Camera
+/// rt_sequence: frames of one size on one device, accumulated over time.  The history, the previous guides and the
+/// previous camera stay on the device; only the camera moves between frames, and a frame of another Scene resets the history.
+pub struct Sequence {
+    raw: *mut rt_sequence,
+    width: i32,
+    height: i32,
+}
+unsafe impl Send for Sequence {} // rtamd.h: one thread uses a sequence at a time
+impl Drop for Sequence {
+    fn drop(&mut self) {
+        unsafe { rt_sequence_destroy(self.raw) }
+    }
+}
+impl Sequence {
+    /// device -1 = the device current at the first frame; cfg None = rt_default_temporal_config
+    pub fn new(width: i32, height: i32, device: i32, cfg: Option<&rt_temporal_config>) -> Result<Sequence, RtError> {
+        let mut raw: *mut rt_sequence = std::ptr::null_mut();
+        check(unsafe { rt_sequence_create(width, height, device, cfg.map_or(std::ptr::null(), |c| c as *const rt_temporal_config), &mut raw) })?;
+        Ok(Sequence { raw, width, height })
+    }
+    /// the next frame resets every pixel
+    pub fn reset(&mut self) -> Result<(), RtError> {
+        check(unsafe { rt_sequence_reset(self.raw) }).map(|_| ())
+    }
+    /// frames since the last reset
+    pub fn frames(&self) -> i32 {
+        unsafe { rt_sequence_frames(self.raw) }
+    }
+    /// rt_sequence_frame: p.spp (even) samples through cam, accumulated into the history and filtered (luma_mode 1 = rt_denoise_sym,
+    /// 0 = rt_denoise, -1 = no filter); p.seed is used as it is.  Returns the frame [h][w][3], the history [h][w][6] and stats.
+    pub fn frame(&mut self, scene: &Scene, cam: &rt_camera, p: &rt_params, dn: Option<&rt_denoise_config>, luma_mode: i32, aov_spp: i32) -> Result<(Vec<f64>, Vec<f64>, rt_stats), RtError> {
+        let n = (self.width as usize) * (self.height as usize);
+        let mut out = vec![0.0f64; n * 3];
+        let mut history = vec![0.0f64; n * 6];
+        let mut st = rt_stats::default();
+        check(unsafe {
+            rt_sequence_frame(self.raw, scene.raw, cam, p, dn.map_or(std::ptr::null(), |c| c as *const rt_denoise_config), luma_mode, aov_spp, out.as_mut_ptr(),
+                              std::ptr::null_mut(), history.as_mut_ptr(), std::ptr::null_mut(), &mut st)
+        })?;
+        Ok((out, history, st))
+    }
+}
+
 /// rt_denoise: the edge-aware a-trous filter on host buffers (rgb [h][w][3]; variance [h][w] and aov [h][w][8] optional);
 /// cfg None = rt_default_denoise_config
 pub fn denoise(width: i32, height: i32, rgb: &[f64], variance: Option<&[f64]>, aov: Option<&[f64]>, cfg: Option<&rt_denoise_config>) -> Result<Vec<f64>, RtError> {

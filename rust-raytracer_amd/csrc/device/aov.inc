@@ -24,16 +24,13 @@ __global__ void __launch_bounds__(64) aov_kernel(FlatView sv, CamK cam, int widt
     double n0 = 0., n1 = 0., n2 = 0., tt = 0., a0 = 0., a1 = 0., a2 = 0.;
     int hits = 0;
     for (int s = 0; s < aov_spp; s++) {
-        // camera.rs:97-99 + Camera::get_ray camera.rs:57-64, as pt_kernel draws them
+        // pt_kernel's camera ray
         Rng rng;
         rng.seed_stream(seed, (uint64_t)y * (uint64_t)width + (uint64_t)x, (uint64_t)s);
-        double u = ((double)x + rng.gen_f64()) / (double)(width - 1);
-        double v = ((double)y + rng.gen_f64()) / (double)(height - 1);
-        double st = 1.0 - v;
-        D3 rd = muls(random_in_unit_disk(rng), cam.lens_radius);
-        D3 offset = add(muls(cam.u, rd.x), muls(cam.v, rd.y));
-        D3 o = add(cam.origin, offset);
-        D3 d = sub(sub(add(add(cam.llc, muls(cam.horizontal, u)), muls(cam.vertical, st)), cam.origin), offset);
+        double u, st;
+        D3 rd, o, d;
+        camera_draw(cam, width, height, x, y, rng, u, st, rd);
+        camera_ray(cam, u, st, rd, o, d);
         const Hit h = ACCEL ? traverse2<GENERAL, false, false>(A, stk, (int)blockDim.x, o, d, t_min, INFINITY) : traverse<GENERAL>(A, o, d, t_min, INFINITY);
         if (h.node < 0) continue;
         const Rec rec = materialize<GENERAL, true>(A, h, o, d, err);

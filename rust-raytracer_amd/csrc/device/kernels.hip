@@ -280,6 +280,23 @@ struct RenderK {
     float box_shrink;        // kernel 2 with the scene in LDS: the NodeW rows' planes move inward by this much while staging (common/tighten.h); 0: as stored
 };
 
+// The primary ray of pixel (x, y), camera.rs:97-99 + Camera::get_ray camera.rs:57-64, in two steps, so that a D9 time draw can stand
+// between them: camera_draw() takes the jitter and the lens sample from the sample's stream (seeded by the caller: the passes key their
+// streams differently), camera_ray() builds the ray from them.  aov.inc and ao.inc call them.  pt_kernel (twice), pt_kernel_coop,
+// pt_kernel_wf and sppm.inc's eye_body keep the same text written out, because every form of a helper tried there changed their
+// instructions: a change here is a change there.
+DEV void camera_draw(const CamK& cam, int width, int height, int x, int y, Rng& rng, double& u, double& st, D3& rd) {
+    u = ((double)x + rng.gen_f64()) / (double)(width - 1);
+    const double v = ((double)y + rng.gen_f64()) / (double)(height - 1);
+    st = 1.0 - v;
+    rd = muls(random_in_unit_disk(rng), cam.lens_radius);  // drawn even for aperture 0 (Q4)
+}
+DEV void camera_ray(const CamK& cam, double u, double st, D3 rd, D3& o, D3& d) {
+    const D3 offset = add(muls(cam.u, rd.x), muls(cam.v, rd.y));
+    o = add(cam.origin, offset);
+    d = sub(sub(add(add(cam.llc, muls(cam.horizontal, u)), muls(cam.vertical, st)), cam.origin), offset);
+}
+
 // ------------------------------------------------------ intersection ------
 // AABB::hit, aabb.rs:15-32, with 1/dir hoisted out of the node loop (same values).
 // min only grows and max only shrinks across the three axes, so testing `max <= min`
@@ -841,6 +858,15 @@ DEV void ray32_wide_addr(Ray32& r, uint32_t n2w_lds) {
 DEV uint32_t wide_ref(uint32_t ref) {
     return (ref >> REF_TAG_SHIFT) == 0u ? (ref / NODEW_CHUNK) * (3u * NODEW_FAR) + (ref % NODEW_CHUNK) * 32u : ref;
 }
+// The workgroup copies N16 16-byte units from SRC to DST (LDS): every staging loop of the kernels.  The caller synchronises.  A macro: the
+// count stays an expression of the loop's condition, as every site had it written out, which keeps the kernels' instructions (as a
+// function, whose argument is evaluated in front of the loop, photon_kernel and wf_walk_kernel already compiled to other code)
+#define LDS_COPY16(DST, SRC, N16)                                                   \
+    do {                                                                            \
+        const uint4* src = (const uint4*)(SRC);                                     \
+        uint4* dst = (uint4*)(DST);                                                 \
+        for (uint32_t i = threadIdx.x; i < (N16); i += blockDim.x) dst[i] = src[i]; \
+    } while (0)
 // The workgroup expands the blob's Node2 array into the NodeW rows at `n2w` (LDS).  shrink > 0: every child box is tightened to the
 // render's own origin bound on the way (common/tighten.h; the host hands 0 wherever the stored pads must stay: scenes with instances,
 // hit_kernel's mode 3).  The caller synchronises.
@@ -2139,6 +2165,39 @@ __device__ __forceinline__ UnitInfo uniform_unit(const UnitInfo& v) {
     u.cur_slot = __builtin_amdgcn_readfirstlane(v.cur_slot); u.finished = __builtin_amdgcn_readfirstlane(v.finished);
     return u;
 }
+// Folds the complete unit in slot SL of a wave's pool into its tile: accumulator += the unit's samples, in sample order, then the tile's
+// ticket moves on and the slot is free.  This is the code that defines the frame's bits (fold_units is its FIFO twin, with batched loads).
+// It reads the caller's rmeta, accum, wring, first_launch and lane.  A macro, for next_unit_pool and wavefront.inc's next_unit_wf: the one
+// reaches the bookkeeping and global memory through AS_L / AS_G pointers, the other through generic ones (M32, G64: the pointee types;
+// LD, ST: the agent-scope accessors of that flavour), and each keeps its instructions -- as a template on the pointer types the same
+// text compiled to other code in both (profiles/r18)
+#define FOLD_POOL_SLOT(M32, G64, LD, ST, TICKETS, SL)                                                                     \
+    do {                                                                                                                  \
+        const M32* m = rmeta + 4 * (SL);                                                                                  \
+        const uint32_t tile = m[0], blk = m[1], ns = m[2] & 0xffu;                                                        \
+        G64* acc = (G64*)accum + ((size_t)tile * TILE_PIX + (size_t)lane) * 3;                                            \
+        double ax = 0., ay = 0., az = 0.;                                                                                 \
+        if (!(blk == 0u && first_launch)) {                                                                               \
+            ax = __longlong_as_double(LD(acc));                                                                           \
+            ay = __longlong_as_double(LD(acc + 1));                                                                       \
+            az = __longlong_as_double(LD(acc + 2));                                                                       \
+        }                                                                                                                 \
+        const G64* p = (const G64*)wring + ((size_t)(SL) * UNIT_SPP * TILE_PIX + (size_t)lane) * 3;                       \
+        for (uint32_t si = 0; si < ns; si++) { /* pixel_color += sample, in sample order (camera.rs:96-101) */            \
+            ax = ax + __longlong_as_double(LD(p));                                                                        \
+            ay = ay + __longlong_as_double(LD(p + 1));                                                                    \
+            az = az + __longlong_as_double(LD(p + 2));                                                                    \
+            p += TILE_PIX * 3;                                                                                            \
+        }                                                                                                                 \
+        ST(acc, __double_as_longlong(ax));                                                                                \
+        ST(acc + 1, __double_as_longlong(ay));                                                                            \
+        ST(acc + 2, __double_as_longlong(az));                                                                            \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); /* accumulator stores done before the ticket moves */           \
+        if (lane == 0) {                                                                                                  \
+            __hip_atomic_store(&(TICKETS)[tile], blk + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                   \
+            rmeta[4 * (SL) + 2] = 0u; /* slot free */                                                                     \
+        }                                                                                                                 \
+    } while (0)
 // next_unit() for launches of single-unit jobs (RenderK::pool_mode, the POOL variants of the kernels; a rank that owns fewer tiles than
 // the GPU has waves): the wave's unit
 // buffers are a POOL.  With the FIFO a complete unit at the head whose tile's ticket has not come keeps every unit behind it from being
@@ -2177,30 +2236,7 @@ __device__ __attribute__((noinline)) UnitInfo next_unit_pool(uint32_t* wst_, uin
         while (mask != 0ull) {
             const int sl = __ffsll((long long)mask) - 1;
             mask &= mask - 1ull;
-            const AS_L uint32_t* m = rmeta + 4 * sl;
-            const uint32_t tile = m[0], blk = m[1], ns = m[2] & 0xffu;
-            AS_G uint64_t* acc = (AS_G uint64_t*)accum + ((size_t)tile * TILE_PIX + (size_t)lane) * 3;
-            double ax = 0., ay = 0., az = 0.;
-            if (!(blk == 0u && first_launch)) {
-                ax = __longlong_as_double(ld_agent_g(acc));
-                ay = __longlong_as_double(ld_agent_g(acc + 1));
-                az = __longlong_as_double(ld_agent_g(acc + 2));
-            }
-            const AS_G uint64_t* p = (const AS_G uint64_t*)wring + ((size_t)sl * UNIT_SPP * TILE_PIX + (size_t)lane) * 3;
-            for (uint32_t si = 0; si < ns; si++) {  // pixel_color += sample, in sample order (camera.rs:96-101)
-                ax = ax + __longlong_as_double(ld_agent_g(p));
-                ay = ay + __longlong_as_double(ld_agent_g(p + 1));
-                az = az + __longlong_as_double(ld_agent_g(p + 2));
-                p += TILE_PIX * 3;
-            }
-            st_agent_g(acc, __double_as_longlong(ax));
-            st_agent_g(acc + 1, __double_as_longlong(ay));
-            st_agent_g(acc + 2, __double_as_longlong(az));
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // accumulator stores done before the ticket moves
-            if (lane == 0) {
-                __hip_atomic_store(&tk_g[tile], blk + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                rmeta[4 * sl + 2] = 0u;  // slot free
-            }
+            FOLD_POOL_SLOT(AS_L uint32_t, AS_G uint64_t, ld_agent_g, st_agent_g, tk_g, sl);
             n_used--;
             folded++;
         }
@@ -2366,6 +2402,16 @@ __device__ __attribute__((noinline)) UnitInfo next_unit(uint32_t* wst_, uint32_t
     return u;
 }
 
+// The launch constants all three schedulers (next_unit, next_unit_pool, wavefront.inc's next_unit_wf) read, written by one thread of the
+// workgroup; the caller synchronises.  pt_kernel and pt_kernel_coop add the job lists, the schedule's levels and the tile list
+DEV void fill_cfg(int* cfg, const RenderK& rk, int ring_units) {
+    cfg[CFG_N_JOBS] = rk.n_units; cfg[CFG_TILES_OWNED] = rk.tiles_owned; cfg[CFG_JOB_UNITS] = rk.job_units;
+    cfg[CFG_SUBS_PER_TILE] = rk.subs_per_tile; cfg[CFG_WORLD] = rk.world; cfg[CFG_RANK] = rk.rank; cfg[CFG_TILES_X] = rk.tiles_x;
+    cfg[CFG_S_BEGIN] = rk.s_begin; cfg[CFG_S_END] = rk.s_end; cfg[CFG_SUB_SPP] = rk.sub_spp; cfg[CFG_WIDTH] = rk.width;
+    cfg[CFG_HEIGHT] = rk.height;
+    cfg[CFG_RING_UNITS] = ring_units;
+}
+
 // GENERAL: 0 = spheres under BVH nodes only, 1 = every primitive of the reference, 2 = 1 + the book-2 extensions (D9: moving spheres, noise textures, an open shutter)
 // A/B switch, ON in the product (round 7): 0 leaves the NodeW rows of kernel 2 with the blob's pads (box_shrink = 0 in every launch)
 #ifndef RT_TIGHTEN_BOXES
@@ -2416,9 +2462,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
                 dst[i] = w;
             }
         } else {
-            const uint4* src = (const uint4*)(sv.base + st_begin);
-            uint4* dst = (uint4*)smem;
-            for (uint32_t i = threadIdx.x; i < lo_bytes / 16; i += blockDim.x) dst[i] = src[i];
+            LDS_COPY16(smem, sv.base + st_begin, lo_bytes / 16);
         }
         char* n2w = smem + lo_bytes;
         stage_nodew(sv, n2w, rk.box_shrink);
@@ -2432,18 +2476,14 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
             A.boxes = (const double2*)(sv.base + sv.off_boxes);
         }
     } else if (LDS) {
-        const uint4* src = (const uint4*)(sv.base + st_begin);
-        uint4* dst = (uint4*)smem;
-        for (uint32_t i = threadIdx.x; i < (st_end - st_begin) / 16; i += blockDim.x) dst[i] = src[i];
+        LDS_COPY16(smem, sv.base + st_begin, (st_end - st_begin) / 16);
         staged = st_end - st_begin;
         __syncthreads();
         A = make_acc(smem - st_begin, sv.base, sv);
     } else {
         A = make_acc(sv.base, sv.base, sv);
         if (ACCEL == 2 && rk.n_top > 0) {  // scene in L2/HBM: the shallowest levels of every BVH (depth-sorted array) in LDS
-            const uint4* src = (const uint4*)(sv.base + sv.off_n2);
-            uint4* dst = (uint4*)smem;
-            for (uint32_t i = threadIdx.x; i < (uint32_t)rk.n_top * NODE2_F4; i += blockDim.x) dst[i] = src[i];
+            LDS_COPY16(smem, sv.base + sv.off_n2, (uint32_t)rk.n_top * NODE2_F4);
             __syncthreads();
             A.n2_top = (const AS_L f32x4*)smem;
             A.n2_top_count = (uint32_t)rk.n_top;
@@ -2467,11 +2507,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
     if (lane < 8) wst[lane] = (lane == 6) ? 1u : 0u;  // nothing in flight, no job yet, jobs left
     if (POOL && lane < RING_UNITS * 4) rmeta[lane] = 0u;  // no slot in use (next_unit_pool reads the flags of slots it never wrote)
     if (threadIdx.x == 0) {
-        cfg[CFG_N_JOBS] = rk.n_units; cfg[CFG_TILES_OWNED] = rk.tiles_owned; cfg[CFG_JOB_UNITS] = rk.job_units;
-        cfg[CFG_SUBS_PER_TILE] = rk.subs_per_tile; cfg[CFG_WORLD] = rk.world; cfg[CFG_RANK] = rk.rank; cfg[CFG_TILES_X] = rk.tiles_x;
-        cfg[CFG_S_BEGIN] = rk.s_begin; cfg[CFG_S_END] = rk.s_end; cfg[CFG_SUB_SPP] = rk.sub_spp; cfg[CFG_WIDTH] = rk.width;
-        cfg[CFG_HEIGHT] = rk.height;
-        cfg[CFG_RING_UNITS] = RING_UNITS;
+        fill_cfg(cfg, rk, RING_UNITS);
         cfg[CFG_JOB_LISTS] = 1;
 #pragma unroll
         for (int i = 0; i < 25; i++) cfg[CFG_LVL + i] = rk.lvl[i / 5][i % 5];
@@ -2572,7 +2608,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
                             const int gx = tx * TILE_W + (lane & (TILE_W - 1)), gy = ty * TILE_H + (lane >> 3);
                             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                             if (gx < rk.width && gy < rk.height) {  // (a pixel of an edge tile outside the image gets no entry)
-                                // camera.rs:97-99 + Camera::get_ray camera.rs:57-64
+                                // camera_draw() + camera_ray(), written out
                                 Rng g;
                                 g.seed_stream(rk.seed, (uint64_t)gy * (uint64_t)rk.width + (uint64_t)gx, (uint64_t)(s0 + b));
                                 const double u = ((double)gx + g.gen_f64()) / (double)(rk.width - 1);
@@ -2616,7 +2652,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
                         int pix = k & (TILE_PIX - 1), s = s0 + (k >> 6);
                         int x = tx * TILE_W + (pix & (TILE_W - 1)), y = ty * TILE_H + (pix >> 3);
                         if (x < rk.width && y < rk.height) {
-                            // camera.rs:97-99 + Camera::get_ray camera.rs:57-64
+                            // camera_draw(), the D9 time draw, camera_ray(), written out
                             rng.seed_stream(rk.seed, (uint64_t)y * (uint64_t)rk.width + (uint64_t)x, (uint64_t)s);
                             double u = ((double)x + rng.gen_f64()) / (double)(rk.width - 1);
                             double v = ((double)y + rng.gen_f64()) / (double)(rk.height - 1);
@@ -3382,9 +3418,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel_coop(FlatView sv, CamK cam
     const double* qgrid_lds = nullptr;
     {
         auto stage = [&](uint32_t off, uint32_t bytes) {
-            const uint4* src = (const uint4*)(sv.base + off);
-            uint4* dst = (uint4*)(smem + staged);
-            for (uint32_t i = threadIdx.x; i < coop_a16(bytes) / 16; i += blockDim.x) dst[i] = src[i];
+            LDS_COPY16(smem + staged, sv.base + off, coop_a16(bytes) / 16);
             const char* at = smem + staged;
             staged += coop_a16(bytes);
             return at;
@@ -3401,9 +3435,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel_coop(FlatView sv, CamK cam
     }
     const uint32_t lds_top = staged;
     if (rk.n_top > 0) {
-        const uint4* src = (const uint4*)(sv.base + sv.off_n2);
-        uint4* dst = (uint4*)(smem + staged);
-        for (uint32_t i = threadIdx.x; i < (uint32_t)rk.n_top * NODE2_F4; i += blockDim.x) dst[i] = src[i];
+        LDS_COPY16(smem + staged, sv.base + sv.off_n2, (uint32_t)rk.n_top * NODE2_F4);
         A.n2_top = (const AS_L f32x4*)(smem + staged);
         A.n2_top_count = (uint32_t)rk.n_top;
         staged += (uint32_t)rk.n_top * (uint32_t)sizeof(Node2);
@@ -3412,12 +3444,8 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel_coop(FlatView sv, CamK cam
     const uint4* n2q_lds = (const uint4*)(smem + staged);
     // the entry walk stays in the first COOP_ENTRY_NODES cached nodes (measured: 16 / 64 nodes 870, 256 866, 1024 860, all cached 856 Msamples/s)
     const uint32_t entry_top = min((uint32_t)rk.n_topq, (uint32_t)COOP_ENTRY_NODES);
-    {
-        const uint4* src = (const uint4*)(sv.base + sv.off_n2q);
-        uint4* dst = (uint4*)(smem + staged);
-        for (uint32_t i = threadIdx.x; i < (uint32_t)rk.n_topq * 2u; i += blockDim.x) dst[i] = src[i];
-        staged += (uint32_t)rk.n_topq * (uint32_t)sizeof(NodeQ);
-    }
+    LDS_COPY16(smem + staged, sv.base + sv.off_n2q, (uint32_t)rk.n_topq * 2u);
+    staged += (uint32_t)rk.n_topq * (uint32_t)sizeof(NodeQ);
     uint32_t* stk = (uint32_t*)(smem + staged) + threadIdx.x;
     const int stk_stride = (int)blockDim.x;
     const int lane = threadIdx.x & 63;
@@ -3440,11 +3468,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel_coop(FlatView sv, CamK cam
     if (lane < 8) wst[lane] = (lane == 6) ? 1u : 0u;
     if (EARLY && lane < RING_UNITS * 4) rmeta[lane] = 0u;  // no slot in use (next_unit_pool)
     if (threadIdx.x == 0) {
-        cfg[CFG_N_JOBS] = rk.n_units; cfg[CFG_TILES_OWNED] = rk.tiles_owned; cfg[CFG_JOB_UNITS] = rk.job_units;
-        cfg[CFG_SUBS_PER_TILE] = rk.subs_per_tile; cfg[CFG_WORLD] = rk.world; cfg[CFG_RANK] = rk.rank; cfg[CFG_TILES_X] = rk.tiles_x;
-        cfg[CFG_S_BEGIN] = rk.s_begin; cfg[CFG_S_END] = rk.s_end; cfg[CFG_SUB_SPP] = rk.sub_spp; cfg[CFG_WIDTH] = rk.width;
-        cfg[CFG_HEIGHT] = rk.height;
-        cfg[CFG_RING_UNITS] = RING_UNITS;
+        fill_cfg(cfg, rk, RING_UNITS);
         cfg[CFG_JOB_LISTS] = (int)JOB_LISTS;
 #pragma unroll
         for (int i = 0; i < 25; i++) cfg[CFG_LVL + i] = rk.lvl[i / 5][i % 5];
@@ -3538,7 +3562,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel_coop(FlatView sv, CamK cam
             if (!alive && k < pool) {
                 int pix = k & (TILE_PIX - 1), s = s0 + (k >> 6);
                 int x = tx * TILE_W + (pix & (TILE_W - 1)), y = ty * TILE_H + (pix >> 3);
-                if (x < rk.width && y < rk.height) {  // camera.rs:97-99 + Camera::get_ray camera.rs:57-64
+                if (x < rk.width && y < rk.height) {  // camera_draw() + camera_ray(), written out
                     rng.seed_stream(rk.seed, (uint64_t)y * (uint64_t)rk.width + (uint64_t)x, (uint64_t)s);
                     double u = ((double)x + rng.gen_f64()) / (double)(rk.width - 1);
                     double v = ((double)y + rng.gen_f64()) / (double)(rk.height - 1);

@@ -83,9 +83,7 @@ DEV void photon_body(FlatView sv, SppmK sk, LightK lk, PhotonBuf all, PhotonBuf 
     uint32_t hot = 0;
     if (ACCEL && LDS) {
         hot = sv.stage2_end - sv.stage2_begin;
-        const uint4* src = (const uint4*)(sv.base + sv.stage2_begin);
-        uint4* dst = (uint4*)smem;
-        for (uint32_t i = threadIdx.x; i < hot / 16; i += blockDim.x) dst[i] = src[i];
+        LDS_COPY16(smem, sv.base + sv.stage2_begin, hot / 16);
         __syncthreads();
         A = make_acc(smem - sv.stage2_begin, sv.base, sv);
         if (MEDIA) {  // the media's boundary subtrees are walked in the reference-order program, which is not staged (as in pt_kernel)
@@ -329,6 +327,7 @@ DEV void eye_body(FlatView sv, const CamK* __restrict__ camp, SppmK sk, double* 
         const CamK cam = *camp;
         Rng rng;
         rng.seed_stream(sk.seed ^ SALT_EYE, (uint64_t)pix, (uint64_t)sk.iteration);
+        // camera_draw() + camera_ray(), written out
         double u = ((double)x + rng.gen_f64()) / (double)(sk.width - 1);
         double v = ((double)y + rng.gen_f64()) / (double)(sk.height - 1);
         double st = 1.0 - v;

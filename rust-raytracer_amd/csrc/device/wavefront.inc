@@ -99,30 +99,7 @@ __device__ __attribute__((noinline)) UnitInfo next_unit_wf(uint32_t* wst, uint32
             while (mask != 0ull) {
                 const int sl = base + __ffsll((long long)mask) - 1;
                 mask &= mask - 1ull;
-                const uint32_t* m = rmeta + 4 * sl;
-                const uint32_t tile = m[0], blk = m[1], ns = m[2] & 0xffu;
-                uint64_t* acc = (uint64_t*)accum + ((size_t)tile * TILE_PIX + (size_t)lane) * 3;
-                double ax = 0., ay = 0., az = 0.;
-                if (!(blk == 0u && first_launch)) {
-                    ax = __longlong_as_double(ld_agent(acc));
-                    ay = __longlong_as_double(ld_agent(acc + 1));
-                    az = __longlong_as_double(ld_agent(acc + 2));
-                }
-                const uint64_t* p = (const uint64_t*)wring + ((size_t)sl * UNIT_SPP * TILE_PIX + (size_t)lane) * 3;
-                for (uint32_t si = 0; si < ns; si++) {  // pixel_color += sample, in sample order (camera.rs:96-101)
-                    ax = ax + __longlong_as_double(ld_agent(p));
-                    ay = ay + __longlong_as_double(ld_agent(p + 1));
-                    az = az + __longlong_as_double(ld_agent(p + 2));
-                    p += TILE_PIX * 3;
-                }
-                st_agent(acc, __double_as_longlong(ax));
-                st_agent(acc + 1, __double_as_longlong(ay));
-                st_agent(acc + 2, __double_as_longlong(az));
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // accumulator stores done before the ticket moves
-                if (lane == 0) {
-                    __hip_atomic_store(&tickets[tile], blk + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    rmeta[4 * sl + 2] = 0u;  // slot free
-                }
+                FOLD_POOL_SLOT(uint32_t, uint64_t, ld_agent, st_agent, tickets, sl);
                 n_used--;
                 any = true;
             }
@@ -186,9 +163,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel_wf(FlatView sv, CamK cam, 
     const double* qgrid_lds = nullptr;
     {
         auto stage = [&](uint32_t off, uint32_t bytes) {
-            const uint4* src = (const uint4*)(sv.base + off);
-            uint4* dst = (uint4*)(smem + staged);
-            for (uint32_t i = threadIdx.x; i < coop_a16(bytes) / 16; i += blockDim.x) dst[i] = src[i];
+            LDS_COPY16(smem + staged, sv.base + off, coop_a16(bytes) / 16);
             const char* at = smem + staged;
             staged += coop_a16(bytes);
             return at;
@@ -201,21 +176,15 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel_wf(FlatView sv, CamK cam, 
         qgrid_lds = (const double*)stage(sv.off_qgrid, (uint32_t)sizeof(QGrid) * sv.n_inst2);
     }
     if (rk.n_top > 0) {
-        const uint4* src = (const uint4*)(sv.base + sv.off_n2);
-        uint4* dst = (uint4*)(smem + staged);
-        for (uint32_t i = threadIdx.x; i < (uint32_t)rk.n_top * NODE2_F4; i += blockDim.x) dst[i] = src[i];
+        LDS_COPY16(smem + staged, sv.base + sv.off_n2, (uint32_t)rk.n_top * NODE2_F4);
         A.n2_top = (const AS_L f32x4*)(smem + staged);
         A.n2_top_count = (uint32_t)rk.n_top;
         staged += (uint32_t)rk.n_top * (uint32_t)sizeof(Node2);
     }
     const uint4* n2q_lds = (const uint4*)(smem + staged);
     const uint32_t entry_top = (uint32_t)rk.n_topq;  // NodeQ indices below this are walked by the parking lane itself
-    {
-        const uint4* src = (const uint4*)(sv.base + sv.off_n2q);
-        uint4* dst = (uint4*)(smem + staged);
-        for (uint32_t i = threadIdx.x; i < (uint32_t)rk.n_topq * 2u; i += blockDim.x) dst[i] = src[i];
-        staged += (uint32_t)rk.n_topq * (uint32_t)sizeof(NodeQ);
-    }
+    LDS_COPY16(smem + staged, sv.base + sv.off_n2q, (uint32_t)rk.n_topq * 2u);
+    staged += (uint32_t)rk.n_topq * (uint32_t)sizeof(NodeQ);
     uint32_t* stk = (uint32_t*)(smem + staged) + threadIdx.x;
     const int stk_stride = (int)blockDim.x;
     const int lane = threadIdx.x & 63;
@@ -235,11 +204,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel_wf(FlatView sv, CamK cam, 
         for (uint32_t i = threadIdx.x; i < (uint32_t)WF_BOOK_WORDS; i += blockDim.x) book[i] = book_save[i];
     }
     if (threadIdx.x == 0) {
-        cfg[CFG_N_JOBS] = rk.n_units; cfg[CFG_TILES_OWNED] = rk.tiles_owned; cfg[CFG_JOB_UNITS] = rk.job_units;
-        cfg[CFG_SUBS_PER_TILE] = rk.subs_per_tile; cfg[CFG_WORLD] = rk.world; cfg[CFG_RANK] = rk.rank; cfg[CFG_TILES_X] = rk.tiles_x;
-        cfg[CFG_S_BEGIN] = rk.s_begin; cfg[CFG_S_END] = rk.s_end; cfg[CFG_SUB_SPP] = rk.sub_spp; cfg[CFG_WIDTH] = rk.width;
-        cfg[CFG_HEIGHT] = rk.height;
-        cfg[CFG_RING_UNITS] = (int)wa.ring_units;
+        fill_cfg(cfg, rk, (int)wa.ring_units);
         wfc[0] = 0u;
         wfc[1] = 0u;
         wfc[2] = wa.first ? 0u : wa.cnt_a[blockIdx.x];
@@ -343,7 +308,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel_wf(FlatView sv, CamK cam, 
             if (!alive && k < pool) {
                 int pix = k & (TILE_PIX - 1), s = s0 + (k >> 6);
                 int x = tx * TILE_W + (pix & (TILE_W - 1)), y = ty * TILE_H + (pix >> 3);
-                if (x < rk.width && y < rk.height) {  // camera.rs:97-99 + Camera::get_ray camera.rs:57-64
+                if (x < rk.width && y < rk.height) {  // camera_draw() + camera_ray(), written out
                     rng.seed_stream(rk.seed, (uint64_t)y * (uint64_t)rk.width + (uint64_t)x, (uint64_t)s);
                     double u = ((double)x + rng.gen_f64()) / (double)(rk.width - 1);
                     double v = ((double)y + rng.gen_f64()) / (double)(rk.height - 1);
@@ -549,9 +514,7 @@ __global__ void __launch_bounds__(WF_WALK_BLOCK) wf_walk_kernel(FlatView sv, WfW
     ServeCtx X;
     {
         auto stage = [&](uint32_t off, uint32_t bytes) {
-            const uint4* src = (const uint4*)(sv.base + off);
-            uint4* dst = (uint4*)(smem + staged);
-            for (uint32_t i = threadIdx.x; i < coop_a16(bytes) / 16; i += blockDim.x) dst[i] = src[i];
+            LDS_COPY16(smem + staged, sv.base + off, coop_a16(bytes) / 16);
             AS_L char* at = (AS_L char*)(smem + staged);
             staged += coop_a16(bytes);
             return at;

@@ -704,7 +704,7 @@ int rt_debug_math_device(int op, size_t n, const double* a_host, const double* b
  * world-space walk with the large instances deferred, then their object-space walks over the Node2 / item records (5: the in-lane
  * fallback of kernel 5) or over the compact NodeQ / Tri32 copies (6: what the serving waves of kernels 5 / 6 walk), with the exact-tie rule;
  * 7 = 3 with the table's boxes tightened as a render tightens them, for the origin bound 2 * max(scene extent, largest |origin coordinate| of
- * this batch); a scene with instances keeps the stored boxes, as in a render): rays n*6 (orig,dir);
+ * this batch); a scene with instances keeps the stored boxes, as in a render; 8 = 3 begun at the root's dominant leaf child where csrc/common/walk_start.h finds one, as pt_kernel's sphere-only LDS variants begin, RT_ERR_UNSUPPORTED with nested Transforms): rays n*6 (orig,dir);
  * out n*12 = {hit, t, p[3], normal[3], front_face, u, v, leaf index in the reference-order program}.
  * RT_ERR_UNSUPPORTED: a scene with moving spheres or a ConstantMedium (rt_debug_walk_device asks those); a kernel other than 1 on a scene
  * without an accel; kernels 5 / 6 on a scene without 1..64 instances of which one holds only f32-vertex triangles (so on every scene with

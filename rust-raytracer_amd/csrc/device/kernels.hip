@@ -37,6 +37,7 @@
 #include "../common/rng.h"
 #include "../common/schedule.h"
 #include "../common/tighten.h"
+#include "../common/walk_start.h"
 #include "device.h"
 
 namespace rtamd {
@@ -893,6 +894,15 @@ DEV void stage_nodew(const FlatView& sv, char* n2w, float shrink) {
         ((uint4*)(w + 2 * NODEW_FAR))[0] = lo0; ((uint4*)(w + 2 * NODEW_FAR))[1] = lo1;
     }
 }
+// START walks (traverse2): ONE thread evaluates the start rule (common/walk_start.h) on the root's Node2 record as the blob
+// stores it and leaves {start ref, push ref}, in the table's own refs, in the child-ref words of the root's THIRD block row -- the copy of
+// the first that exists for the far planes' sake; every walk reads the refs at + 24 of the first or second row (cur + r.ax, above), so
+// nothing reads these two words but the entry of a START walk.  After the barrier behind stage_nodew (whose thread for the root writes
+// the row), and in front of another before the first walk: the caller's.
+DEV void stage_walk_start(const FlatView& sv, char* n2w) {
+    const WalkStart ws = walk_start(((const Node2*)(sv.base + sv.off_n2))[sv.root2], sv.root2);
+    *(uint2*)(n2w + wide_ref(sv.root2) + 2 * NODEW_FAR + 24) = make_uint2(wide_ref(ws.start_ref), wide_ref(ws.push_ref));  // (wide_ref leaves WALK_START_NONE as it is)
+}
 // one child of a NodeW: near / far planes already selected
 DEV bool box32w(float nx, float ny, float nz, float fx, float fy, float fz, const Ray32& r, float& entry) {
     const float px = __builtin_fmaf(nx, r.ix, -r.cx), qx = __builtin_fmaf(fx, r.ix, -r.cx);
@@ -994,6 +1004,9 @@ DEV bool box32(float lox, float loy, float loz, float hix, float hiy, float hiz,
 //     is sized max_depth + 2 rows or more (FlatView::stack2 = max_depth + 2, stack2_inline likewise for the world-and-inline-
 //     instances part; kernels 5 / 6 take the larger of that and world_depth2 + 2): the sentinel fits with a row to spare and
 //     no size changed with it.  One row too few would not reach a neighbour's column but the ring / job bookkeeping behind the stacks.
+//     START (below) begins at a leaf child of the root, depth 1, with the other child as one entry: still entries <= depth(cur).  The
+//     leaf section ends with the pop of that entry, which leaves the walk at the other child, depth 1, with NO entry; from there on
+//     entries <= depth(cur) - 1, so a START walk uses a row less than the plain one, and no size changes with it either.
 // walk_stack_bytes / coop_stack_rows: the one place the launches and the kernels size these columns from.
 // (walk_stack_bytes itself lives in device.h since round 17: abi.cpp sizes the same columns before it touches a device)
 __host__ __device__ inline uint32_t coop_stack_rows(const FlatView& v) {  // kernel 5 (its two walks never share a stack) and the hit queries of kernels 5 / 6
@@ -1049,6 +1062,10 @@ DEV void leaf_items_addr(uint32_t ia, uint32_t cnt, D3 o, D3 d, double a, double
         });
     } while (ia != ie);
 }
+// START (WIDE only): the walk begins at the ref stage_walk_start left in the node table, with the ref beside it as its
+// one stack entry -- the root's dominant leaf child and the other child, where common/walk_start.h finds such a leaf.  The first trip through
+// the loop then finds no inner node, runs the leaf section for every live lane of the wave in step, pops the other child and descends with
+// the bound that leaf gave.  The loop's body is the plain walk's to the line.  On for the ITEMA variants and hit_kernel_start.
 // ITEMA (pt_kernel's sphere-only LDS variants; with WIDE and GENERAL == 0 only): the staged item table's first words
 // are not `kind | payload << 4` but the LDS byte address of the item's 32-byte sphere row (pt_kernel's staging rewrites them in the LDS copy; the
 // blob keeps its words, and so does every other kernel).  The item step then reads the sphere through that word as it comes, has no
@@ -1056,7 +1073,7 @@ DEV void leaf_items_addr(uint32_t ia, uint32_t cnt, D3 o, D3 d, double a, double
 // end address, and joins nothing with the root: it is used where sphere_root accepted it.  Hit::kp of such a walk is that address;
 // materialize<0, .., true> reads the row through it and takes the sphere's index from its distance to the table.
 template <int GENERAL, bool DEFER = false, bool TOP = true, bool WIDE = false, class PEND = uint32_t, bool LIMIT = false, bool ENTER = !DEFER, bool TRACK = false, bool RESOLVE = true,
-          bool TIEDEF = false, bool ITEMA = false>
+          bool TIEDEF = false, bool ITEMA = false, bool START = false>
 DEV Hit traverse2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, double t_min, double t_max, PEND* pend = nullptr, uint32_t order_limit = 0xFFFFFFFFu,
                   MediaTrack* track = nullptr) {
     D3 o = wo, d = wd;
@@ -1080,6 +1097,16 @@ DEV Hit traverse2(const Acc& A, uint32_t* stk, const int stride, D3 wo, D3 wd, d
     uint32_t spw = WIDE ? (uint32_t)(uintptr_t)(AS_L uint32_t*)stk + spw_step : 0u;
     if (WIDE) *(AS_L uint32_t*)stk = REF_DONE;
     uint32_t cur = WIDE ? wide_ref(A.root2) : A.root2;
+    if constexpr (START) {
+        static_assert(!START || WIDE, "START: the start words live in the LDS node table");
+        // the walk begins where stage_walk_start says: at the root's dominant leaf child with the other child in row 1, or at the root
+        // with nothing pushed.  Row 1 is written either way (it is free: the first push would overwrite it) and the stack pointer moves
+        // past it by a select, so no path leaves anything unwritten and the loop below is entered exactly as before.
+        const u32x2 ws = *(const AS_L u32x2*)(uintptr_t)(A.n2w_lds + cur + 2u * NODEW_FAR + 24u);
+        *(AS_L uint32_t*)(uintptr_t)spw = ws.y;
+        spw += ws.y != WALK_START_NONE ? spw_step : 0u;
+        cur = ws.x;
+    }
     for (;;) {
         while ((cur >> REF_TAG_SHIFT) == 0u) {  // inner node: test both children
             PH_EV(10);
@@ -2471,6 +2498,10 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
         A = make_acc(smem - st_begin, sv.base, sv);
         A.n2 = nullptr;
         A.n2w_lds = (uint32_t)(uintptr_t)(AS_L char*)n2w;
+        // ITEMA walks are START walks (traverse2): their start, behind the barrier above and in front of the one below the bookkeeping
+        if constexpr (ITEMA) {
+            if (threadIdx.x == 0) stage_walk_start(sv, n2w);
+        }
         if (MEDIA) {  // the media's boundary subtrees are walked in the reference-order program, which this kernel does not stage
             A.meta = (const uint2*)(sv.base + sv.off_meta);
             A.boxes = (const double2*)(sv.base + sv.off_boxes);
@@ -2688,7 +2719,7 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_kernel(FlatView sv, CamK cam, Ren
                 PH_EV(13);
                 PH_BEGIN(ph_t0);
                 Hit h = (ACCEL == 2) ? (MEDIA ? traverse2_media<GENERAL, !LDS, LDS>(A, sv.n_media, stk, stk_stride, o, d, rk.t_min, rng)
-                                              : traverse2<GENERAL, false, !LDS, LDS, uint32_t, false, true, false, true, false, ITEMA>(A, stk, stk_stride, o, d, rk.t_min, INFINITY))
+                                              : traverse2<GENERAL, false, !LDS, LDS, uint32_t, false, true, false, true, false, ITEMA, ITEMA>(A, stk, stk_stride, o, d, rk.t_min, INFINITY))
                                      : traverse<GENERAL, MEDIA>(A, o, d, rk.t_min, INFINITY, &rng);
                 PH_END(1, ph_t0);
                 PH_BEGIN(ph_p0);
@@ -3981,6 +4012,27 @@ __global__ void hit_kernel(FlatView sv, int accel, float box_shrink, size_t n, c
     for (int k = 0; k < 12; k++) q[k] = 0.;
     if (h.node < 0) return;
     Rec rec = materialize<true, true>(A, h, o, d, err);  // with uv for every primitive: the render kernels compute it only for image textures
+    hit_row(q, h, rec);
+}
+// hit_kernel's mode 3 as a START walk (the host's mode 8): the start rule of common/walk_start.h staged as pt_kernel's ITEMA variants stage
+// it, the stored pads, the general item step.  A kernel of its own, so that hit_kernel stays what it was.
+__global__ void hit_kernel_start(FlatView sv, size_t n, const double* rays, double t_min, double t_max, double* out, int* err) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    Acc A = make_acc(sv.base, sv.base, sv);
+    stage_nodew(sv, smem, 0.f);
+    __syncthreads();
+    if (threadIdx.x == 0) stage_walk_start(sv, smem);
+    __syncthreads();
+    A.n2w_lds = (uint32_t)(uintptr_t)(AS_L char*)smem;
+    if (i >= n) return;
+    D3 o = mk(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]), d = mk(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
+    uint32_t* stk = (uint32_t*)(smem + nodew_bytes(sv.n_nodes2)) + threadIdx.x;
+    const Hit h = traverse2<true, false, false, true, uint32_t, false, true, false, true, false, false, true>(A, stk, (int)blockDim.x, o, d, t_min, t_max);
+    double* q = out + 12 * i;
+    for (int k = 0; k < 12; k++) q[k] = 0.;
+    if (h.node < 0) return;
+    Rec rec = materialize<true, true>(A, h, o, d, err);
     hit_row(q, h, rec);
 }
 // hit_kernel's kernels 1, 2 and 3 for scenes with nested Transforms (the chain walk, GENERAL == 3)
@@ -5580,7 +5632,7 @@ void debug_hit_device(const rt_scene& s, int kernel, size_t n, const double* ray
     dout.alloc(n * 96);
     err.zeros(4);
     dr.upload(rays, n * 48);
-    if (kernel < 1 || kernel > 7 || kernel == 4) throw RtError(RT_ERR_ARG, "rt_debug_hit_device: kernel 1, 2, 3, 5, 6 or 7");
+    if (kernel < 1 || kernel > 8 || kernel == 4) throw RtError(RT_ERR_ARG, "rt_debug_hit_device: kernel 1, 2, 3, 5, 6, 7 or 8");
     // 7: mode 3's table with the pads of a render whose origins are these rays' (common/tighten.h): O_r = 2 max(ew, largest |origin coordinate|
     // of the batch); as in a render, a scene with instances keeps the stored pads, and so does a batch that reaches origin_limit2
     float shrink = 0.f;
@@ -5592,6 +5644,10 @@ void debug_hit_device(const rt_scene& s, int kernel, size_t n, const double* ray
         shrink = box_shrink(view.origin_limit2, render_origin_bound(view.origin_limit2, o_abs), view.n_inst2 == 0u);
         kernel = 3;
     }
+    // 8: mode 3 as a START walk (hit_kernel_start).  Not for nested Transforms: the start rule is the world BVH's, and no render walks it there
+    const bool start = kernel == 8;
+    if (start && s.flat.xf_nest != 0u) throw RtError(RT_ERR_UNSUPPORTED, "rt_debug_hit_device: kernel 8 walks no scene with nested Transforms");
+    if (start) kernel = 3;
     // (the parts of accel2_usable that a diagnostic on the caller's own rays can answer for, each with its own message: the origins are the
     // caller's, as rtamd.h says, and stacks beyond LDS fail the launch)
     if (kernel != 1 && !view.accel_ok) throw RtError(RT_ERR_UNSUPPORTED, "no accel for this scene");
@@ -5608,6 +5664,13 @@ void debug_hit_device(const rt_scene& s, int kernel, size_t n, const double* ray
     }
     // nested Transforms: the chain walk (kernels 5 / 6 were refused above: nested scenes have no compact data)
     const auto fn = s.flat.xf_nest != 0u ? hit_kernel_nest : hit_kernel;
+    if (start) {
+        set_dynamic_lds((const void*)hit_kernel_start, smem);
+        hipLaunchKernelGGL(hit_kernel_start, dim3((unsigned)((n + 63) / 64)), dim3(64), smem, 0, view, n, (const double*)dr.p, t_min, t_max, (double*)dout.p, (int*)err.p);
+        HIP_CHECK(hipGetLastError());
+        dout.download(out, n * 96);
+        return;
+    }
     if (kernel == 3 || s.flat.xf_nest != 0u) set_dynamic_lds((const void*)fn, smem);
     hipLaunchKernelGGL(fn, dim3((unsigned)((n + 63) / 64)), dim3(64), smem, 0, view, kernel, shrink, n, (const double*)dr.p, t_min, t_max, (double*)dout.p,
                        (int*)err.p);

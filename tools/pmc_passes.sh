@@ -21,6 +21,6 @@ for SET in "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCL
   timeout -k 10 400 rocprofv3 --pmc $SET -d $OUT/pmc_$C --output-format csv -- $CMD > $OUT/pmc_$C.json 2>>$OUT/err.log || { tail -5 $OUT/err.log; exit 1; }
 done
 python3 tools/pmc_summary.py $OUT/pmc_* > $OUT/pmc_summary_$NAME.csv
-python3 tools/make_pt_model.py --samples $N --source "profiles/r18/pmc_summary_$NAME.csv (rocprofv3 --pmc, separate passes: $CMD)" --out $OUT/model_$NAME.json $OUT/pmc_* \
+python3 tools/make_pt_model.py --samples $N --source "profiles/r19/pmc_summary_$NAME.csv (rocprofv3 --pmc, separate passes: $CMD)" --out $OUT/model_$NAME.json $OUT/pmc_* \
   | grep -E "valu_insts_per_sample|lane_util|valu_busy_measured|kernel_ms|hbm_bytes_per|share_sq_wait_any" | tr '\n' ' '
 echo " <- $NAME"

@@ -10,7 +10,13 @@
 //   build/walk_model build/s500.txt                       the product's pad (|o|max = 64 x extent), while-while
 //   build/walk_model build/s500.txt --omax-extents 2      the pad of a render from inside the scene (O_r = 2 x extent)
 //   build/walk_model build/s500.txt --exit-k8 7           leave the node loop once lanes at a leaf >= 7/8 lanes still walking
+//   build/walk_model build/s500m.txt --omax-extents 2 --start-leaf    every walk begins where csrc/common/walk_start.h says
+// A line of the list may carry a fifth column, the sphere's material: L Lambertian, M Metal, D Dielectric, E DiffuseLight (s500m.txt: the
+// command above with  ,n['material']['type'][0] if n['material']['type']!='DiffuseLight' else 'E'  added to the print, and no sort).  A
+// list with that column is shaded by it: L diffuse with albedo 0.5, M mirror with albedo 0.8, D straight on with 12 % mirror and no
+// absorption, E ends the path (a light scatters nothing); a list without it gets the stock mix below.
 // options: --omax-extents F  --exit-k8 K  --tiles N (8x8-pixel tiles of primary rays, default 400)  --spp N (16)  --depth N (50)  --seed N
+//          --start-leaf
 //          --cam lx ly lz ax ay az vfov  --regen N (8: free lanes before a wave takes new paths)  --costs node item section test (38 78 10 1)
 // The paths: primary rays per tile through a pinhole, then per sphere (by index) 80 % diffuse, 12 % mirror, 8 % glass-like (straight on),
 // the ground diffuse; a path ends on a miss, at the depth limit, or by absorption (albedo 0.5 .. 0.9).
@@ -21,6 +27,10 @@
 #include <cstring>
 #include <fstream>
 #include <random>
+#include <sstream>
+#include <string>
+
+#include "common/walk_start.h"
 
 namespace rtamd {
 Tuning tuning() { return Tuning{}; }
@@ -35,7 +45,7 @@ static double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 static V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 static V3 unit(V3 a) { return a * (1. / std::sqrt(dot(a, a))); }
 
-struct Sph { V3 c; double r; };
+struct Sph { V3 c; double r; char mat; };  // mat: L, M, D, E, or 0 = the stock mix
 static std::vector<Sph> S;
 static AccelBuild AB;
 static uint32_t ROOT;
@@ -94,12 +104,14 @@ static void item_test(Lane& L, uint32_t item) {
 int main(int argc, char** argv) {
     if (argc < 2) { fprintf(stderr, "usage: walk_model SPHERES.txt [options]  (see the head of tools/walk_model.cpp)\n"); return 2; }
     double omax_ext = 64., cam[7] = {-6, 2, -6, 0, 0, -1, 45}, cost[4] = {38, 78, 10, 1};
+    bool start_leaf = false;
     int k8 = 0, tiles = 400, spp = 16, max_depth = 50, regen = 8;
     uint64_t seed = 1;
     for (int i = 2; i < argc; i++) {
         auto next = [&](int n) { if (i + n >= argc) { fprintf(stderr, "%s needs %d value(s)\n", argv[i], n); exit(2); } };
         if (!strcmp(argv[i], "--omax-extents")) { next(1); omax_ext = atof(argv[++i]); }
         else if (!strcmp(argv[i], "--exit-k8")) { next(1); k8 = atoi(argv[++i]); }
+        else if (!strcmp(argv[i], "--start-leaf")) start_leaf = true;
         else if (!strcmp(argv[i], "--tiles")) { next(1); tiles = atoi(argv[++i]); }
         else if (!strcmp(argv[i], "--spp")) { next(1); spp = atoi(argv[++i]); }
         else if (!strcmp(argv[i], "--depth")) { next(1); max_depth = atoi(argv[++i]); }
@@ -110,8 +122,16 @@ int main(int argc, char** argv) {
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     std::ifstream in(argv[1]);
-    Sph s;
-    while (in >> s.c.x >> s.c.y >> s.c.z >> s.r) S.push_back(s);
+    bool with_mat = false;
+    for (std::string line; std::getline(in, line);) {
+        std::istringstream ls(line);
+        Sph s;
+        s.mat = 0;
+        if (!(ls >> s.c.x >> s.c.y >> s.c.z >> s.r)) continue;
+        std::string m;
+        if (ls >> m) { s.mat = m[0]; with_mat = true; }
+        S.push_back(s);
+    }
     if (S.empty()) { fprintf(stderr, "no spheres in %s (lines of: cx cy cz r)\n", argv[1]); return 1; }
     std::vector<AccelItem> items(S.size());
     double ew = 0.;
@@ -124,6 +144,8 @@ int main(int argc, char** argv) {
     const double pad = 3. * std::ldexp(omax_ext * ew, -22);  // as build_bvhs pads for |o|max (the pad does not enter the SAH: the same tree)
     ROOT = accel_build_bvh(AB, items, pad, 0);
     if (!AB.ok) { fprintf(stderr, "the builder gave up\n"); return 1; }
+    // where a walk begins: the root, or (--start-leaf) what the kernels' own rule says for this root
+    const WalkStart begin = start_leaf ? walk_start(AB.nodes[ROOT], ROOT) : WalkStart{ROOT, WALK_START_NONE};
 
     // camera (pinhole): 1200-pixel-wide image, tile t = the t-th 8x8 tile of a stride that spreads the tiles over the frame
     const V3 from = {cam[0], cam[1], cam[2]}, w = unit(from - V3{cam[3], cam[4], cam[5]}), u = unit(cross(V3{0, 1, 0}, w)), v = cross(w, u);
@@ -164,8 +186,9 @@ int main(int argc, char** argv) {
         if (!busy) break;
         iters++;
         for (auto& L : wave) {
-            L.cur = L.active ? ROOT : REF_DONE;
+            L.cur = L.active ? begin.start_ref : REF_DONE;
             L.stack.clear();
+            if (L.active && begin.push_ref != WALK_START_NONE) L.stack.push_back(begin.push_ref);
             L.best = INFINITY;
             L.hit = -1;
             L.inv = {1. / L.d.x, 1. / L.d.y, 1. / L.d.z};
@@ -216,6 +239,15 @@ int main(int argc, char** argv) {
             if (L.hit < 0 || ++L.depth >= max_depth) { L.active = false; continue; }
             const Sph& sp = S[L.hit];
             const V3 p = L.o + L.d * L.best, n = (p - sp.c) * (1. / sp.r);
+            if (with_mat) {
+                if (sp.mat == 'E') { L.active = false; continue; }
+                const double alb = sp.mat == 'D' ? 1. : sp.mat == 'M' ? 0.8 : 0.5;
+                if (U(gen) > alb) { L.active = false; continue; }
+                L.o = p;
+                if (sp.mat == 'M' || (sp.mat == 'D' && U(gen) < 0.12)) L.d = L.d - n * (2. * dot(L.d, n));
+                else if (sp.mat != 'D') L.d = (dot(n, L.d) < 0 ? n : n * -1.) + rand_unit();
+                continue;
+            }
             const uint32_t h = (uint32_t)L.hit * 2654435761u;
             const double kind = sp.r > 10. ? 0. : (h >> 8 & 0xffff) / 65536., albedo = 0.5 + 0.4 * ((h >> 4 & 0xff) / 256.);
             if (U(gen) > albedo) { L.active = false; continue; }
@@ -227,6 +259,8 @@ int main(int argc, char** argv) {
     }
     const double it = (double)iters;
     printf("spheres %zu  nodes %zu  extent %g  pad %.3g (|o|max = %g x extent)  exit-k8 %d  paths %ld  iterations %ld\n", S.size(), AB.nodes.size(), ew, pad, omax_ext, k8, n_paths, iters);
+    printf("materials: %s  walks begin at 0x%08x with 0x%08x pushed%s\n", with_mat ? "the list's column" : "the stock mix", begin.start_ref, begin.push_ref,
+           begin.push_ref == WALK_START_NONE ? " (nothing: the root)" : "");
     const char* nm[3] = {"inner-node steps", "leaf items", "leaf sections"};
     for (int k = 0; k < 3; k++) printf("%-18s wave-exec/iter %8.3f  lanes/exec %5.1f\n", nm[k], ws[k] / it, ws[k] ? ls[k] / ws[k] : 0.);
     printf("node steps with one lane: %.1f %%\n", ws[0] ? 100. * one_lane_steps / ws[0] : 0.);
